@@ -19,7 +19,13 @@ libniqki_hip.so (niqki_group_*); torch.distributed only carries the group id
 and the timing barrier.  Every rank brings its own --batch query genomes per step ("scaling": "weak"; --scaling
 strong cuts one batch over the ranks).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the gather-histogram kernel
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: the index build, the warm-up, the
+K timed steps and the line (`metric`, `value`, `unit`, `ms_per_step`, `config`, the kernel classes of the timed steps);
+--dump-outputs DIR also writes the hit lists of the last timed step (what a caller of the step receives) as
+DIR/hit_offsets.npy, DIR/hit_counts.npy and DIR/hit_gids.npy (float64, at most 64 MB together: a fixed, seeded sample
+of the hits beyond that).  Everything below -- and for N > 1 the whole-range check of --verify -- needs --full.
+
+--full: `roofline` is for the gather-histogram kernel
 (the HBM-bound kernel SURVEY.md 8d grades), timed live with HIP events on the
 engine's stream in a few steps of the same run WITHOUT the overlapped sketch kernel
 (beside it the launch time is no roofline figure); `kernels` lists every kernel class; `sketch_kernel` holds the
@@ -32,7 +38,7 @@ and the matrix path, each with its own in-run parity check.
                                       (slots [0, F/8), the full query batch): the
                                       compute half of the 1 -> 8 scaling curve
 
-The whole default run keeps to a wall-clock budget (--budget-s, default 140 s from the start of the process): the
+The whole --full run keeps to a wall-clock budget (--budget-s, default 140 s from the start of the process): the
 headline, `roofline` and `cpu_baseline` always run, every other leg starts only while its time is left, child processes
 get min(their own limit, what is left), and `budget.dropped` names what did not run.
 """
@@ -100,11 +106,18 @@ def main():
                     help="wall-clock budget of the whole run in seconds, from the start of the process (see the module docstring)")
     ap.add_argument("--verify", action="store_true", help=argparse.SUPPRESS)        # (the default for N > 1 since round 6)
     ap.add_argument("--no-verify", action="store_true",
-                    help="N > 1: do NOT check every rank's hit lists of its last step against a whole-range handle that it builds "
+                    help="N > 1 with --full: do NOT check every rank's hit lists of its last step against a whole-range handle that it builds "
                          "beside its shard (all genomes sketched once more on every rank: seconds at 100 000 genomes)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline (see the module docstring): PMC passes, the roofline / kernels / "
+                         "sketch_kernel steps, ALU probes, the CPU baseline and parity legs, end_to_end_d2h, the extra workloads, "
+                         "and for N > 1 the whole-range check of --verify")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit lists of the last timed step (rank 0's) as DIR/hit_offsets.npy, hit_counts.npy, hit_gids.npy")
     args = ap.parse_args()
     if args.pmc_child:
         args.no_legs = args.no_overlap = True      # (counters per kernel: every launch has the device to itself)
+        args.full = True                           # (the launches of the run the counters stand for)
     if args.no_legs:
         args.no_cpu = args.no_extra = args.no_pmc = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -113,10 +126,10 @@ def main():
 
     # HBM bytes per launch of the gather path, measured now: two rocprofv3 --pmc passes (FETCH_SIZE,
     # WRITE_SIZE: passes of their own, no trace flags) over a 3-launch run of this same command, as
-    # child processes started BEFORE this process touches the GPU.  Full default runs on one GPU only.
+    # child processes started BEFORE this process touches the GPU.  Taken by --full runs on one GPU only.
     budget = Budget(args.budget_s, T_START)
     live_traffic = None
-    if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.shard_of and not args.no_cpu
+    if (args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.shard_of and not args.no_cpu
             and not args.no_extra and not args.no_pmc and os.environ.get("NIQKI_BENCH_PMC", "1") != "0"
             and budget.want("pmc_passes", 90)):
         live_traffic = measure_counters(args, budget)
@@ -448,20 +461,26 @@ def main():
     if overlap:
         prof["sketch"] = sk_eng.profile_read(niqki_amd.KC_SKETCH)
         sk_eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the N > 1 roofline steps below reuse hc / hg
+        si = n_steps_all - 1
+        dump_outputs(args.dump_outputs, hit_off[si], hc, hg, args.seed)
 
     # N > 1 with the next batch sketched beside the exchange: the gather launches of the timed steps share the
     # device with a sketch kernel, their durations say nothing about the kernel.  Its roofline figure comes from a
     # few more steps of this same run without the overlapped sketch (every rank takes them: the exchange is collective).
     roofline_from = None
-    kernels_overlapped = None
+    kernels_timed = {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in prof.items()}
     roof_steps = list(range(args.warmup, n_steps_all))     # the steps whose gather launches `roofline` is taken from
     roof_gather = None
-    if ahead:
+    # the kernels' own figures (`roofline`, `kernels`, `sketch_kernel`): --full, or --shard-of, whose line is the
+    # shard's gather launch
+    figures = args.full or emu
+    if ahead and figures:
         # one GPU: the gather launches of the timed steps ran beside the next batch's sketch kernel.  The kernels'
         # own times -- `roofline`, `kernels`, `sketch_kernel` -- come from n_r more steps of this run that sketch and
         # query one after the other on the handle's stream (hits into buffers of their own: hc / hg keep the last
         # timed step's for the parity legs); these also leave every ring batch's sketches in qsk
-        kernels_overlapped = {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in prof.items()}
         off2 = torch.zeros(per + 1, dtype=torch.int64, device=dev)
         hc2, hg2 = torch.zeros_like(hc), torch.zeros_like(hg)
         eng.query_ahead_dev(off2, hc2, hg2, cap)        # (the batch the last timed step sketched beyond the run)
@@ -485,7 +504,7 @@ def main():
         roofline_from = ("%d more steps of this run with the sketch kernel BEFORE the query instead of beside it (%.2f ms per step); "
                          "the timed steps' launches share the device with the next batch's sketch kernel" % (n_r, t_serial * 1e3))
         del off2, hc2, hg2
-    if use_dist and overlap:
+    if use_dist and overlap and figures:
         n_r = min(3, args.steps)
         eng.profile(True)
         eng.profile_reset()
@@ -504,7 +523,7 @@ def main():
     # --verify (N > 1, small indexes): this rank's hit lists of the last timed step against a whole-range
     # handle that holds every genome of the index
     verify = None
-    if use_dist and (args.verify or (world > 1 and not args.no_verify)):
+    if use_dist and (args.verify or (args.full and world > 1 and not args.no_verify)):
         # The local half may fail on one rank only (an allocation, say): it is caught and counted as "not equal", so
         # that every rank still reaches the two collectives below -- a check beside the line must not hang the job.
         si = n_steps_all - 1
@@ -553,7 +572,7 @@ def main():
     # ---- roofline of the gather kernel: algorithmic bytes 4T + 20F per query ----
     f_local = se - sb
     T = 0
-    for si in roof_steps:
+    for si in (roof_steps if figures else []):
         bi = si % n_batches
         if use_dist:   # measurement only: whole sketches of every rank, this shard's slots are what counts
             if on_gloo:
@@ -592,13 +611,13 @@ def main():
             pass
 
     # ---- what a streaming copy reaches on this device, now (the practical HBM ceiling beside the 8 TB/s spec) ----
-    copy_gbs = eng.measure_alu(4) / 1e9 if (rank == 0 and not args.no_legs) else None
+    copy_gbs = eng.measure_alu(4) / 1e9 if (rank == 0 and args.full and not args.no_legs) else None
 
     # ---- sketch kernel against integer-ALU ceilings measured now, on this device ----
     kmers = args.steps * per * max(L - K, 0)
     sk_rate = kmers / (prof["sketch"][0] * 1e-3) if prof["sketch"][0] else 0.0
     alu = None
-    if rank == 0 and not args.no_legs:
+    if rank == 0 and args.full and not args.no_legs:
         adds, muls, arith, vop3 = eng.measure_alu(0), eng.measure_alu(1), eng.measure_alu(2), eng.measure_alu(3)
         # vector instructions per k-mer: counted in this run (SQ_INSTS_VALU pass of measure_counters) or, where the
         # run took no counter passes, the committed figure of the same kernel
@@ -678,25 +697,29 @@ def main():
                 "tile_genomes": eng.tile_genomes(), "index_build_s": round(t_index, 2),
                 "hits_per_query": total_hits / max(1, args.steps * per), "hit_overflow": overflow,
             },
-            "roofline": roofline_record(achieved, traffic, traffic_source, live_traffic, gather_ms, gather_launches, alg_bytes, layout_min,
-                                        copy_gbs, roofline_from, T, n_q_local, False),
-            "kernels": {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in prof.items()},
-            # the sketch kernel is integer-ALU bound (4 64-bit multiplies per k-mer, DESIGN.md 4.1):
-            # its rate in k-mers, the HBM bytes it needs (1 byte per base + the sketch) and the ALU ceilings
-            "sketch_kernel": {
-                "gkmers_per_s": sk_rate / 1e9,
-                "hbm_gbs": (args.steps * per * (L + 4 * F)) / (prof["sketch"][0] * 1e-3) / 1e9 if prof["sketch"][0] else 0.0,
-                "bound": "valu", "alu": alu,
-            },
             "cpu_baseline": None,
             "end_to_end_d2h": None,
         }
-        if ahead:
+        if figures:
+            out["roofline"] = roofline_record(achieved, traffic, traffic_source, live_traffic, gather_ms, gather_launches, alg_bytes,
+                                              layout_min, copy_gbs, roofline_from, T, n_q_local, False)
+            out["kernels"] = {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in prof.items()}
+            # the sketch kernel is integer-ALU bound (4 64-bit multiplies per k-mer, DESIGN.md 4.1):
+            # its rate in k-mers, the HBM bytes it needs (1 byte per base + the sketch) and the ALU ceilings
+            out["sketch_kernel"] = {
+                "gkmers_per_s": sk_rate / 1e9,
+                "hbm_gbs": (args.steps * per * (L + 4 * F)) / (prof["sketch"][0] * 1e-3) / 1e9 if prof["sketch"][0] else 0.0,
+                "bound": "valu", "alu": alu,
+            }
+        else:
+            # the kernel classes' device time inside the timed steps, which took it anyway
+            out["kernels_beside_each_other" if ahead else "kernels"] = kernels_timed
+        if ahead and figures:
             out["kernels_note"] = ("kernels / roofline / sketch_kernel: each kernel's own time, from %d steps of this run that sketch and query "
                                    "one after the other (scaled to %d steps); kernels_beside_each_other: the same classes inside the timed "
                                    "steps, where batch i + 1's sketch kernel shares the device with batch i's gather and hit kernels"
                                    % (len(roof_steps), args.steps))
-            out["kernels_beside_each_other"] = kernels_overlapped
+            out["kernels_beside_each_other"] = kernels_timed
             out["serial_step"] = {"ms_per_step": t_serial * 1e3, "value": per / t_serial, "unit": "genomes/s", "steps": len(roof_steps),
                                   "note": "sketch kernel, then the query, on one stream (bench.py --no-overlap times this as the line)"}
 
@@ -730,7 +753,7 @@ def main():
                 out["budget"]["hard_stop"] = True
             os.write(real_stdout, (json.dumps(out) + "\n").encode())
         budget.lap("index_steps_roofline")
-        if world == 1 and not emu and not args.no_legs:
+        if world == 1 and not emu and args.full and not args.no_legs:
             budget.arm(45.0, emit)
             legs(out, budget, eng, niqki_amd, torch, dev, args, qseq, qsk, hit_off, hc, hg, stride_b, L, N, per, (K, S, W, H, J), cap,
                  n_batches, d_ro, ms_median, ahead)
@@ -743,6 +766,25 @@ def main():
     eng.close()
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, off, hc, hg, seed, limit=64_000_000):
+    """The hit lists of one step -- offsets (n + 1), counts and genome ids -- as float64 .npy files (32-bit values and
+    offsets below 2^53: exact).  Beyond `limit` bytes together (headers included), the hits at fixed, seeded positions
+    (in hit_sample_positions.npy) stand for all of them."""
+    os.makedirs(path, exist_ok=True)
+    off = off.cpu().numpy()
+    n = min(int(off[-1]), hc.numel())          # (an overflowing step stored `capacity` hits)
+    c, g = hc[:n].cpu().numpy(), hg[:n].cpu().numpy()
+    room = (limit - 4 * 128 - 8 * len(off)) // 16       # (an .npy header takes 128 bytes)
+    if n > room:
+        room = (limit - 4 * 128 - 8 * len(off)) // 24   # (the positions take 8 bytes per hit too)
+        pos = np.sort(np.random.default_rng(seed).choice(n, room, replace=False))
+        c, g = c[pos], g[pos]
+        np.save(os.path.join(path, "hit_sample_positions.npy"), pos.astype(np.float64))
+    np.save(os.path.join(path, "hit_offsets.npy"), off.astype(np.float64))
+    np.save(os.path.join(path, "hit_counts.npy"), c.astype(np.float64))
+    np.save(os.path.join(path, "hit_gids.npy"), g.astype(np.float64))
 
 
 def legs(out, budget, eng, niqki_amd, torch, dev, args, qseq, qsk, hit_off, hc, hg, stride_b, L, N, per, prm, cap, n_batches, d_ro,

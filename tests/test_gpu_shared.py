@@ -99,13 +99,15 @@ def test_stream_priority_option_changes_no_result(native, po):
 def test_bench_modes_on_a_small_index(tmp_path, mode):
     """bench.py's other modes at a small size (the timed-steps-only run that tools/profile_round.sh traces -- the default
     step with the next batch's sketch kernel beside the query, the same one after the other, the default with priority
-    streams -- and a run with the legs): one JSON line with the record's fields; the roofline fraction is a fraction."""
+    streams -- and a run with the legs), all with --full: one JSON line with the record's fields; the roofline fraction
+    is a fraction."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--genomes", "3000", "--batch", "256", "--steps", "3", "--warmup", "1"] + mode
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--genomes", "3000", "--batch", "256", "--steps", "3",
+           "--warmup", "1"] + mode
     r = subprocess.run(cmd, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -125,6 +127,43 @@ def test_bench_modes_on_a_small_index(tmp_path, mode):
         assert j["cpu_baseline"] is None and j["end_to_end_d2h"] is None and "extra_workloads" not in j
     else:
         assert j["end_to_end_d2h"]["value"] > 0
+
+
+@pytest.mark.parametrize("mode", [[], ["--no-overlap"]])
+def test_plain_bench_run_and_its_outputs(tmp_path, mode):
+    """bench.py without --full: the timed steps and the line alone (no roofline steps, probes or legs), --steps timed
+    steps, and --dump-outputs writes the hit lists of the last timed step -- the same ones a --full run writes."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(extra, out):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--genomes", "3000", "--batch", "256", "--steps", "4", "--warmup", "1",
+               "--dump-outputs", str(out)] + mode + extra
+        r = subprocess.run(cmd, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    j = run([], tmp_path / "plain")
+    assert j["metric"].startswith("query genomes/sec") and j["unit"] == "genomes/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "u64" and j["steps"] == 4 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert "roofline" not in j and "sketch_kernel" not in j and "serial_step" not in j and "extra_workloads" not in j
+    assert j["cpu_baseline"] is None and j["end_to_end_d2h"] is None
+    timed = j["kernels"] if "--no-overlap" in mode else j["kernels_beside_each_other"]
+    assert timed["gather"]["launches"] == 4 and timed["sketch"]["launches"] == 4
+    j_full = run(["--full", "--no-legs"], tmp_path / "full")
+    assert "roofline" in j_full and j_full["steps"] == 4
+    names = ("hit_offsets", "hit_counts", "hit_gids")
+    plain = {n: np.load(tmp_path / "plain" / (n + ".npy")) for n in names}
+    full = {n: np.load(tmp_path / "full" / (n + ".npy")) for n in names}
+    off = plain["hit_offsets"]
+    assert len(off) == 257 and off[0] == 0 and np.all(np.diff(off) >= 0) and 0 < off[-1] == len(plain["hit_counts"])
+    assert len(plain["hit_gids"]) == off[-1] and np.all(plain["hit_gids"] < 3000) and not (tmp_path / "plain" / "hit_sample_positions.npy").exists()
+    for n in names:
+        assert plain[n].dtype == np.float64 and np.array_equal(plain[n], full[n]), n
 
 
 def test_shared_entry_points_under_mixed_load(native, po):

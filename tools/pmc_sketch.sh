@@ -2,7 +2,8 @@
 # SQ counters of the sketch kernel (run on the GPU box from the repo root).
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-sk}
-OUT=$R/gpurun_out/pmc_$TAG
+RES=${NIQKI_RESULTS:-$R/results}
+OUT=$RES/pmc_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 i=0
@@ -11,9 +12,9 @@ for grp in \
  "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" \
  "GRBM_GUI_ACTIVE" ; do
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/g$i -- python3 $R/bench.py --no-cpu --steps 2 --genomes 20000 > $OUT/g$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/g$i -- python3 $R/bench.py --full --no-cpu --steps 2 --genomes 20000 > $OUT/g$i.log 2>&1
 done
 cd $R
-python tools/prof_summary.py $OUT | grep -E "sketch_kernel|^==" > $R/gpurun_out/pmc_$TAG.summary.txt
+python tools/prof_summary.py $OUT | grep -E "sketch_kernel|^==" > $RES/pmc_$TAG.summary.txt
 rm -rf $OUT
-cat $R/gpurun_out/pmc_$TAG.summary.txt
+cat $RES/pmc_$TAG.summary.txt
