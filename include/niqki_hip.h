@@ -106,7 +106,8 @@ typedef struct niqki_params {
   uint32_t tile_genomes; /* genomes per counter tile (0 = choose); see DESIGN.md */
   uint32_t resident_mib; /* > 0: paged index, as option "resident_bytes" (in MiB) from the start --
                             the way to load a dump into a paged handle */
-  uint32_t reserved[2];
+  uint32_t top_k;      /* > 0: a query's hits are the first min(k, n) of its full list (option "top_k") */
+  uint32_t reserved[1];
 } niqki_params;
 
 int niqki_abi_version(void);
@@ -140,7 +141,8 @@ int niqki_set_stream(niqki_index *ix, void *hip_stream);
 void *niqki_get_stream(const niqki_index *ix);
 int niqki_synchronize(niqki_index *ix);
 
-/* Tuning knobs (no reference counterpart; none of them changes a result):
+/* Tuning knobs (no reference counterpart; none of them changes a result, except "min_score" and "top_k", the two
+ * options that set what a query returns):
  * "gather_variant" (launch shape of the gather kernel, 0 = choose .. 5), "query_batch",
  * "tile_genomes" (multiple of 64, <= 65536; takes effect at the next build),
  * "bucket_align_log2" (-1 = choose, 0..6: buckets start on multiples of 2^a ids),
@@ -148,7 +150,10 @@ int niqki_synchronize(niqki_index *ix);
  * genomes are dealt to the tiles round-robin, so a run of related genomes is spread over all
  * tiles; blocks of 32 are 64 bytes of a counter row, the smallest piece HBM writes without
  * a read-modify-write; 0 = tiles are ranges of genome ids),
- * "min_score", "record_len_hint" (average bytes per sketch of NIQKI_MEM_DEVICE
+ * "min_score", "top_k" (0 = default: every hit; k > 0: per query the first min(k, n) entries of the full list of
+ * its n hits, in the same order -- count descending, among equal counts the larger gid first, so equal counts that
+ * straddle the cut keep their largest gids; selected on the device from the counter rows, see "top-k" below),
+ * "record_len_hint" (average bytes per sketch of NIQKI_MEM_DEVICE
  * batches, so that niqki_sketch need not read rec_off back to pick a launch
  * shape; 0 = read it back), "query_order" (1 = default: the queries of a launch
  * are processed in an order that puts similar ones on the same XCD where that pays --
@@ -280,6 +285,14 @@ int niqki_query_shared(niqki_index *ix, const int32_t *sketch, uint64_t *n_hits,
                        uint32_t *hit_gids, uint64_t capacity);
 int niqki_query_sequence_shared(niqki_index *ix, const uint8_t *seq, uint64_t len, uint64_t *n_hits,
                                 uint32_t *hit_counts, uint32_t *hit_gids, uint64_t capacity);
+
+/* ---- top-k (niqki_params.top_k, option "top_k") ---------------------------------------------
+ * With k > 0, niqki_query, niqki_query_sequences, niqki_staged_query, niqki_query_ahead, niqki_query_shared,
+ * niqki_query_sequence_shared, niqki_hits_from_counts (over its [gid_begin, gid_begin + n_gids) range) and the group
+ * query calls return per query the first min(k, n) entries of the list they return with k = 0 (n = hits at or above
+ * min_score; min_score 0: count-0 genomes are hits).  k >= the genome count is the same as k = 0.  The hits of a batch
+ * of nq queries then never exceed nq x k: capacity = nq x k never returns NIQKI_E_CAPACITY.
+ * niqki_matrix_range, niqki_query_counts / niqki_query_counts32 and the dump do not look at it. */
 
 /* Index::query_sketch (src/niqki_index.cpp:633-687), batched: both halves. */
 int niqki_query(niqki_index *ix, const int32_t *sketches, uint32_t nq,
@@ -428,7 +441,8 @@ int niqki_export_dump(niqki_index *ix, uint8_t *buf, uint64_t capacity,
  * parameters stored in the dump override those given (like :67-72), except
  * device / tile_genomes / slot range, which are taken from `params`: a handle
  * created with a slot range keeps only its own slots of the dump (one shard of
- * a multi-GPU index), the bytes of the other slots are walked and skipped. */
+ * a multi-GPU index), the bytes of the other slots are walked and skipped.  top_k and
+ * resident_mib are taken from `params` too (the dump does not hold them). */
 int niqki_import_dump(const niqki_params *params, const uint8_t *buf,
                       uint64_t len, uint64_t *consumed, niqki_index **out);
 
@@ -489,13 +503,14 @@ typedef struct niqki_group niqki_group; /* opaque */
 void niqki_group_slot_range(uint32_t rank, uint32_t world, uint32_t S, uint32_t *slot_begin,
                             uint32_t *slot_end);
 int niqki_group_new_id(uint8_t id[NIQKI_GROUP_ID_BYTES]);
-/* The shards must agree in K, S, W, min_score and genome count and own the slot ranges
+/* The shards must agree in K, S, W, min_score, top_k and genome count and own the slot ranges
  * of their ranks (S = 16: at least two shards).  On failure niqki_last_error(shards[0]) says why. */
 int niqki_group_create(niqki_index *const *shards, uint32_t n_local, uint32_t first_rank,
                        uint32_t world, const uint8_t *id, niqki_group **out);
 void niqki_group_destroy(niqki_group *g); /* the shard handles stay the caller's */
 const char *niqki_group_last_error(const niqki_group *g);
-/* "exchange": 0 = choose (sparse when min_score >= 4 * world), 1 = sparse (candidate
+/* "exchange": 0 = choose (sparse when min_score >= 4 * world; never with top_k > 0, whose batches always take the
+ * dense exchange, stat "sparse" then reads 0), 1 = sparse (candidate
  * genomes only), 2 = dense (reduce-scatter of whole hit vectors); "cand_cap": candidate
  * ids per query and rank of the sparse form, even, default 256 (a step whose lists
  * overflow is redone densely, never answered wrongly); "surv_cap": survivors (genomes with a

@@ -31,7 +31,7 @@ class Params(C.Structure):
     _fields_ = [("K", C.c_uint32), ("S", C.c_uint32), ("W", C.c_uint32), ("H", C.c_uint32),
                 ("min_score", C.c_uint32), ("slot_begin", C.c_uint32), ("slot_end", C.c_uint32),
                 ("device", C.c_int32), ("tile_genomes", C.c_uint32), ("resident_mib", C.c_uint32),
-                ("reserved", C.c_uint32 * 2)]
+                ("top_k", C.c_uint32), ("reserved", C.c_uint32 * 1)]
 
 
 class RawBatch(C.Structure):
@@ -230,13 +230,13 @@ class Engine:
     """One handle = one GPU (or one slot shard of an index)."""
 
     def __init__(self, K=31, S=15, W=12, H=4, J=0.0, min_score_value=None, device=-1,
-                 slot_begin=0, slot_end=0, tile_genomes=0, resident_mib=0, _handle=None):
+                 slot_begin=0, slot_end=0, tile_genomes=0, resident_mib=0, top_k=0, _handle=None):
         self.L = lib()
         if _handle is not None:
             self.h = _handle
         else:
             ms = self.L.niqki_min_score(J, S) if min_score_value is None else min_score_value
-            p = Params(K, S, W, H, ms, slot_begin, slot_end, device, tile_genomes, resident_mib)
+            p = Params(K, S, W, H, ms, slot_begin, slot_end, device, tile_genomes, resident_mib, top_k)
             h = _vp()
             rc = self.L.niqki_create(C.byref(p), C.byref(h))
             if rc:
@@ -247,6 +247,7 @@ class Engine:
         self.L.niqki_get_params(self.h, C.byref(q))
         self.K, self.S, self.W, self.H, self.min_score = q.K, q.S, q.W, q.H, q.min_score
         self.slot_begin, self.slot_end, self.device = q.slot_begin, q.slot_end, q.device
+        self.top_k = q.top_k
         self.F = 1 << self.S
 
     def close(self):
@@ -543,10 +544,10 @@ class Engine:
         return buf.tobytes()
 
     @classmethod
-    def import_dump(cls, data, device=-1, tile_genomes=0, resident_mib=0):
+    def import_dump(cls, data, device=-1, tile_genomes=0, resident_mib=0, top_k=0):
         L = lib()
         buf = np.frombuffer(data, dtype=np.uint8)
-        p = Params(31, 15, 12, 4, 0, 0, 0, device, tile_genomes, resident_mib)
+        p = Params(31, 15, 12, 4, 0, 0, 0, device, tile_genomes, resident_mib, top_k)
         h = _vp()
         consumed = _u64(0)
         rc = L.niqki_import_dump(C.byref(p), _p(buf), buf.size, C.byref(consumed), C.byref(h))

@@ -529,6 +529,11 @@ int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
     return NIQKI_OK;
   }
   if (!std::strcmp(key, "min_score")) { ix->p.min_score = ix->d.min_score = (uint32_t)value; return NIQKI_OK; }
+  if (!std::strcmp(key, "top_k")) {
+    if (value < 0 || value > (int64_t)UINT32_MAX) return fail(ix, NIQKI_E_INVALID, "top_k must be in 0 .. 2^32 - 1");
+    ix->p.top_k = (uint32_t)value;
+    return NIQKI_OK;
+  }
   return fail(ix, NIQKI_E_INVALID, std::string("unknown option ") + key);
 }
 

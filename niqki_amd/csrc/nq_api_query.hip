@@ -227,11 +227,20 @@ int hits_dev(niqki_index *ix, const uint16_t *counts, uint32_t nq, uint64_t stri
     if (total_out) *total_out = 0;
     return NIQKI_OK;
   }
-  int rc = ensure(ix, ix->ws_blk, (size_t)nq * a.n_blk * 4);
+  // top-k (k < n_gids: k >= n_gids cuts nothing): the select replaces the hit count, the output holds <= nq x k entries
+  a.top_k = ix->p.top_k < n_gids ? ix->p.top_k : 0u;
+  const uint64_t room = a.top_k ? std::min<uint64_t>(capacity, (uint64_t)nq * a.top_k) : capacity;
+  const size_t nb = (size_t)nq * a.n_blk;
+  int rc = ensure(ix, ix->ws_blk, (a.top_k ? nb * (2 + nq::kSelBlkWords) + nq : nb) * 4);
   if (rc) return rc;
-  if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
-  if ((rc = ensure(ix, ix->ws_tg, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
+  if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
+  if ((rc = ensure(ix, ix->ws_tg, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
   a.blk_counts = (uint32_t *)ix->ws_blk.p;
+  if (a.top_k) {
+    a.blk_skip = a.blk_counts + nb;
+    a.blk_tmp = a.blk_skip + nb;
+    a.thr = a.blk_tmp + nb * nq::kSelBlkWords;
+  }
   a.tmp_counts = (uint32_t *)ix->ws_tc.p;
   a.tmp_gids = (uint32_t *)ix->ws_tg.p;
   Span sp(ix, NIQKI_KC_HITS);
@@ -271,14 +280,16 @@ int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16
     return hits_dev(ix, c1, nq, stride, 0, N, hit_off, hc, hg, capacity, check_capacity, total_out, c2);
   }
   const uint32_t cap = std::min<uint32_t>((std::max<uint32_t>(ix->hit_list_cap, 1) + 3u) & ~3u, nq::kHitListMaxCap);
+  const uint32_t k = ix->p.top_k < N ? ix->p.top_k : 0u;   // (top-k: a query's segment is the first min(n, k) of its list)
+  const uint64_t room = k ? std::min<uint64_t>(capacity, (uint64_t)nq * k) : capacity;
   if ((rc = ensure(ix, ix->ws_hl, (size_t)nq * cap * 4))) return rc;
   if ((rc = ensure(ix, ix->ws_blk, ((size_t)nq * 2 + 1) * 4))) return rc;   // the lists' sizes, then the overflowing queries
   nq::CandOut co;
   co.hl = (uint32_t *)ix->ws_hl.p;
   co.hl_n = (uint32_t *)ix->ws_blk.p;
   co.hl_over = (uint32_t *)ix->ws_blk.p + nq;
-  if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;   // (lists of > 2048 hits)
-  if ((rc = ensure(ix, ix->ws_tg, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
+  if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;   // (lists of > 2048 hits)
+  if ((rc = ensure(ix, ix->ws_tg, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
   co.hl_cap = cap;
   co.hl_min = ix->d.min_score;
   if ((rc = counts_dev(ix, sketches, ix->d.F, first_slot(ix), nq, c1, stride, nullptr, &co))) return rc;
@@ -296,6 +307,7 @@ int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16
   a.tmp_counts = (uint32_t *)ix->ws_tc.p;
   a.tmp_gids = (uint32_t *)ix->ws_tg.p;
   a.capacity = capacity;
+  a.top_k = k;
   uint32_t *over = (uint32_t *)ix->ws_blk.p + nq;
   Span sp(ix, NIQKI_KC_HITS);
   NQ_HIP(ix, nq::launch_hitlist_scan((const uint32_t *)ix->ws_blk.p, a, cap, over, ix->stream));
@@ -306,7 +318,7 @@ int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16
     if (total_out) *total_out = total;
     if (total > capacity) return NIQKI_E_CAPACITY;
   }
-  NQ_HIP(ix, nq::launch_hitlist_emit(a, (const uint32_t *)ix->ws_hl.p, cap, over, ix->stream));
+  NQ_HIP(ix, nq::launch_hitlist_emit(a, (const uint32_t *)ix->ws_blk.p, (const uint32_t *)ix->ws_hl.p, cap, over, ix->stream));
   return NIQKI_OK;
 }
 

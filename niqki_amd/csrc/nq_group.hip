@@ -946,6 +946,9 @@ int reduce_scatter_u32(niqki_group *g, Buf niqki_group::Ws::*send, Buf niqki_gro
 
 // bytes of one destination's slices of `per` queries (16-byte granular for the pull kernel)
 size_t slice_bytes(uint32_t per, uint32_t w_max) { return (((size_t)per * w_max * 2) + 15) & ~(size_t)15; }
+// option "exchange" as a batch takes it: top-k batches are dense (the sparse candidate exchange does not know the
+// boundary; the dense form ends in nqi::hits_dev on the summed rows, which does)
+int exchange_of(const niqki_group *g) { return g->sh[0]->p.top_k ? 2 : g->exchange; }
 // the decisions and sizes of one query batch (niqki_group_plan_batch: also what the CPU test of the protocol uses)
 void plan_batch(uint32_t G, uint32_t S, uint32_t min_score, int exchange, uint32_t per, uint32_t N, uint32_t C, niqki_group_plan *o) {
   const uint32_t F = 1u << S, nq_ = G * per;
@@ -1074,8 +1077,8 @@ int niqki_group_create(niqki_index *const *shards, uint32_t n_local, uint32_t fi
     if (ix->d.S > 15 && world < 2)
       return bail(NIQKI_E_INVALID, "an S = 16 group needs at least two shards (a shard counts at most 2^15 slots in u16)");
     if (ix->d.K != shards[0]->d.K || ix->d.W != shards[0]->d.W || ix->d.min_score != shards[0]->d.min_score ||
-        ix->n_genomes != shards[0]->n_genomes)
-      return bail(NIQKI_E_INVALID, "the shards of a group must agree in K, W, min_score and genome count");
+        ix->p.top_k != shards[0]->p.top_k || ix->n_genomes != shards[0]->n_genomes)
+      return bail(NIQKI_E_INVALID, "the shards of a group must agree in K, W, min_score, top_k and genome count");
     for (uint32_t m = 0; m < l; ++m) shared_device |= shards[m]->device == ix->device;
   }
   const char *tenv = std::getenv("NIQKI_GROUP_TRANSPORT");
@@ -1200,7 +1203,7 @@ int niqki_group_get_stat(const niqki_group *g, const char *key, uint64_t *value)
   if (!std::strcmp(key, "sparse")) {
     const uint32_t ms = g->sh[0]->d.min_score;
     niqki_group_plan plan;
-    plan_batch(g->world, g->sh[0]->d.S, ms, g->exchange, 1, std::max(1u, g->sh[0]->n_genomes), g->cand_cap, &plan);
+    plan_batch(g->world, g->sh[0]->d.S, ms, exchange_of(g), 1, std::max(1u, g->sh[0]->n_genomes), g->cand_cap, &plan);
     *value = plan.sparse;
     return NIQKI_OK;
   }
@@ -1379,7 +1382,7 @@ int niqki_group_query_begin(niqki_group *g, const int32_t *const *local_sketches
   if (per == 0) return NIQKI_OK;
   const uint32_t min_score = g->sh[0]->d.min_score;
   niqki_group_plan plan;
-  plan_batch(G, g->sh[0]->d.S, min_score, g->exchange, per, N, g->cand_cap, &plan);
+  plan_batch(G, g->sh[0]->d.S, min_score, exchange_of(g), per, N, g->cand_cap, &plan);
   const bool sparse = plan.sparse != 0;
   pd.sparse = sparse;
   int rc = prepare_batch(g, per, N, true, sparse);

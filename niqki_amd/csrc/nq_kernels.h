@@ -214,8 +214,19 @@ struct HitsArgs {
   uint32_t *hit_counts, *hit_gids;
   uint32_t *tmp_counts, *tmp_gids;
   uint64_t capacity;
+  // top-k (k > 0): launch_hits_count takes hits_select_kernel, which finds each query's boundary -- the count T and
+  // how many of the genomes with count T are kept, the largest gids -- and writes per block the entries kept
+  // (blk_counts) and the ties at T dropped at the block's low-gid end (blk_skip: 0 = none, kSkipAllTies = all);
+  // hits_compact_kernel keeps c > T plus the ties blk_skip leaves.  thr == nullptr: c >= min_score, as without top-k.
+  uint32_t top_k = 0;
+  uint32_t *thr = nullptr;        // nq: T of each query
+  uint32_t *blk_skip = nullptr;   // nq * n_blk
+  uint32_t *blk_tmp = nullptr;    // nq * n_blk * kSelBlkWords scratch of the select
 };
 constexpr uint32_t kHitsBlk = 4096;  // genomes per compaction block
+constexpr uint32_t kSkipAllTies = 0xFFFFFFFFu;
+constexpr uint32_t kSelBins = 4352;     // count >> 4 (<= 4096 for counts <= 2^16), padded to 17 per thread of 256
+constexpr uint32_t kSelBlkWords = 17;   // per block: genomes above the boundary bin, then one per count of that bin
 hipError_t launch_candidates(const uint16_t *counts, uint64_t stride, uint32_t nq, uint32_t n_gids, uint32_t thr,
                              uint32_t cap, int32_t *cand, int32_t *n, hipStream_t stream);
 hipError_t launch_hits_count(const HitsArgs &a, hipStream_t stream);
@@ -224,7 +235,9 @@ hipError_t launch_hits_count(const HitsArgs &a, hipStream_t stream);
 // hit_counts / hit_gids, and thresholds + orders the counter row (a.counts) of a query whose list overflowed.
 // over: nq + 1 words of scratch (the queries whose lists overflowed, made by the scan, taken by the emit launch)
 hipError_t launch_hitlist_scan(const uint32_t *n, const HitsArgs &a, uint32_t hl_cap, uint32_t *over, hipStream_t stream);
-hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over, hipStream_t stream);
+// n: the lists' sizes (hl_n of the gather launch); with a.top_k a query's segment holds the first min(n, k) entries
+hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over,
+                               hipStream_t stream);
 hipError_t launch_hits_emit(const HitsArgs &a, hipStream_t stream);
 
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------

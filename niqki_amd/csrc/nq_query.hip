@@ -1411,9 +1411,15 @@ __global__ __launch_bounds__(1024) void hits_scan_kernel(HitsArgs a) {
 __global__ __launch_bounds__(256) void hits_compact_kernel(HitsArgs a) {
   __shared__ uint32_t wsum[4];
   __shared__ uint32_t s_before;
+  __shared__ uint32_t tsum[4];
   const uint32_t q = blockIdx.x / a.n_blk, b = blockIdx.x % a.n_blk;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   if (a.blk_counts[blockIdx.x] == 0) return;  // nothing above the threshold in this block (uniform)
+  // top-k: kept are c > T and the ties c == T from the skip-th of the block on (ascending gid); without top-k, or with
+  // every tie of the block kept, c >= T (T = min_score without top-k: the threshold of src/niqki_index.cpp:662-666)
+  const uint32_t T = a.thr ? a.thr[q] : a.min_score;
+  const uint32_t skip = a.blk_skip ? a.blk_skip[blockIdx.x] : 0u;
+  uint32_t tie_run = 0;   // ties of this block with smaller gid, so far
   if (tid == 0) {
     uint32_t before = 0;
     for (uint32_t i = 0; i < b; ++i) before += a.blk_counts[(uint64_t)q * a.n_blk + i];
@@ -1429,7 +1435,18 @@ __global__ __launch_bounds__(256) void hits_compact_kernel(HitsArgs a) {
   for (uint32_t base = lo; base < hi; base += 256) {
     uint32_t i = base + tid;
     uint32_t c = (i < hi) ? (uint32_t)row[i] + (row2 ? (uint32_t)row2[i] : 0u) : 0u;
-    bool hit = (i < hi) && c >= a.min_score;
+    bool hit = (i < hi) && (skip == 0 ? c >= T : c > T);
+    if (skip != 0 && skip != kSkipAllTies) {   // the block where the ties' quota runs out (one per query at most)
+      const bool tie = (i < hi) && c == T;
+      const uint64_t tb = __ballot(tie);
+      if (lane == 0) tsum[wave] = __popcll(tb);
+      __syncthreads();
+      uint32_t tpre = 0, ttot = 0;
+#pragma unroll
+      for (uint32_t w = 0; w < 4; ++w) { uint32_t x = tsum[w]; if (w < wave) tpre += x; ttot += x; }
+      if (tie && tie_run + tpre + __popcll(tb & ((1ULL << lane) - 1ULL)) >= skip) hit = true;
+      tie_run += ttot;
+    }
     uint64_t bal = __ballot(hit);
     uint32_t rank = __popcll(bal & ((1ULL << lane) - 1ULL));
     if (lane == 0) wsum[wave] = __popcll(bal);
@@ -1447,6 +1464,201 @@ __global__ __launch_bounds__(256) void hits_compact_kernel(HitsArgs a) {
     }
     run += tot;
     __syncthreads();
+  }
+}
+
+// ---- top-k: each query's boundary (T, r) on its counter row ----
+// T = the largest count with at least k hits at or above it, r = how many genomes of count T are kept (the largest
+// gids: the order of src/niqki_index.cpp:685 puts them first).  Radix select by count: pass 1 builds a histogram of
+// count >> 4 over the hits in LDS (the boundary bin bh and the hits above it), pass 2 a histogram of the 16 counts of
+// bin bh.  With n <= k hits nothing is cut: T = min_score, every tie kept (r = kSkipAllTies).
+
+struct SelShared {
+  uint32_t wsum[4];
+  uint32_t h16[16];
+  uint32_t bh, above, T, r;
+};
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+// f(c) for every genome of [lo, hi) that a wave reads; lo is a multiple of kHitsBlk (rows start on 16-byte boundaries
+// for the 8-counter loads where the caller made them so: NIQKI_ROW_STRIDE)
+template <class Fn>
+__device__ __forceinline__ void sel_walk(const uint16_t *row, const uint16_t *row2, uint32_t lo, uint32_t hi, uint32_t lane, Fn f) {
+  if ((((uintptr_t)row) & 15) == 0 && !row2) {
+    for (uint32_t i = lo + lane * 8; i < hi; i += 512) {
+      if (i + 8 <= hi) {
+        const uint4 w = *(const uint4 *)(row + i);
+        f(w.x & 0xFFFFu); f(w.x >> 16); f(w.y & 0xFFFFu); f(w.y >> 16);
+        f(w.z & 0xFFFFu); f(w.z >> 16); f(w.w & 0xFFFFu); f(w.w >> 16);
+      } else {
+        for (uint32_t j = i; j < hi; ++j) f((uint32_t)row[j]);
+      }
+    }
+  } else {
+    for (uint32_t i = lo + lane; i < hi; i += 64) f((uint32_t)row[i] + (row2 ? (uint32_t)row2[i] : 0u));
+  }
+}
+
+// The boundary of one query's row, by the 256 threads of a workgroup (wave w takes blocks w, w+4, ...); hist:
+// kSelBins words of LDS.  Returns n, the query's hit count; T and r only when n > k.  BLK (hits_select_kernel): pass 1
+// also writes the blocks' hit counts to blk_counts (the answer when n <= k) and pass 2 the blocks' genomes above bin
+// bh and their counts in bin bh to blk_tmp (kSelBlkWords per block), from which the kept entries of every block follow
+// once T is known -- the row is read twice here and once more by the compaction.
+template <bool BLK>
+__device__ uint32_t sel_boundary(const uint16_t *row, const uint16_t *row2, uint32_t n_gids, uint32_t min_score, uint32_t k,
+                                 uint32_t *hist, SelShared &sh, uint32_t *blk_counts, uint32_t *blk_skip, uint32_t *blk_tmp,
+                                 uint32_t &T, uint32_t &r) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t n_blk = (n_gids + kHitsBlk - 1) / kHitsBlk;
+  for (uint32_t i = tid; i < kSelBins; i += 256) hist[i] = 0;
+  __syncthreads();
+  uint32_t low = 0;   // hits of bin 0 (counts 0 .. 15: nearly every genome against an unrelated query) in a register
+  for (uint32_t b = wave; b < n_blk; b += 4) {
+    const uint32_t lo = b * kHitsBlk, hi = lo + kHitsBlk < n_gids ? lo + kHitsBlk : n_gids;
+    uint32_t m = 0;
+    sel_walk(row, row2, lo, hi, lane, [&](uint32_t c) {
+      if (c >= min_score) {
+        ++m;
+        if (c < 16) ++low;
+        else atomicAdd(&hist[(c >> 4) < kSelBins ? (c >> 4) : kSelBins - 1], 1u);
+      }
+    });
+    if (BLK) {
+      m = wave_sum_u32(m);
+      if (lane == 0) { blk_counts[b] = m; blk_skip[b] = 0; }
+    }
+  }
+  low = wave_sum_u32(low);
+  if (lane == 0 && low) atomicAdd(&hist[0], low);
+  __syncthreads();
+  // thread t holds bins [17 t, 17 t + 17); the hits above its bins: a suffix sum over the threads
+  uint32_t s = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 17; ++j) s += hist[tid * 17 + j];
+  uint32_t incl = s;   // s of this lane and the lanes above it
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_down(incl, o, 64);
+    if (lane + (uint32_t)o < 64) incl += y;
+  }
+  if (lane == 0) sh.wsum[wave] = incl;
+  if (tid < 16) sh.h16[tid] = 0;
+  __syncthreads();
+  uint32_t above_w = 0, n = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < 4; ++w) { const uint32_t x = sh.wsum[w]; if (w > wave) above_w += x; n += x; }
+  if (n <= k) return n;   // (uniform)
+  const uint32_t excl = above_w + incl - s;
+  if (excl < k && excl + s >= k) {   // the one thread whose bins hold the boundary
+    uint32_t cum = excl;
+    int j = 16;
+    for (; j > 0; --j) {
+      const uint32_t h = hist[tid * 17 + j];
+      if (cum + h >= k) break;
+      cum += h;
+    }
+    sh.bh = tid * 17 + j;
+    sh.above = cum;
+  }
+  __syncthreads();
+  const uint32_t bh = sh.bh;
+  for (uint32_t b = wave; b < n_blk; b += 4) {
+    const uint32_t lo = b * kHitsBlk, hi = lo + kHitsBlk < n_gids ? lo + kHitsBlk : n_gids;
+    uint32_t above = 0, cnt[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) cnt[v] = 0;
+    sel_walk(row, row2, lo, hi, lane, [&](uint32_t c) {
+      if (c >= min_score) {
+        above += (c >> 4) > bh;
+        if ((c >> 4) == bh) {
+#pragma unroll
+          for (uint32_t v = 0; v < 16; ++v) cnt[v] += (c & 15u) == v;
+        }
+      }
+    });
+    above = wave_sum_u32(above);
+    if (BLK && lane == 0) blk_tmp[(size_t)b * kSelBlkWords] = above;
+#pragma unroll
+    for (uint32_t v = 0; v < 16; ++v) {
+      const uint32_t x = wave_sum_u32(cnt[v]);
+      if (lane == 0) {
+        if (BLK) blk_tmp[(size_t)b * kSelBlkWords + 1 + v] = x;
+        if (x) atomicAdd(&sh.h16[v], x);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t cum = sh.above;
+    int v = 15;
+    for (; v > 0; --v) {
+      if (cum + sh.h16[v] >= k) break;
+      cum += sh.h16[v];
+    }
+    sh.T = bh * 16 + (uint32_t)v;
+    sh.r = k - cum;
+  }
+  __syncthreads();
+  T = sh.T;
+  r = sh.r;
+  return n;
+}
+
+// top-k in place of hits_count_kernel: one workgroup per query.  hit_off[q] = min(n, k); blk_counts / blk_skip / thr
+// as hits_compact_kernel takes them.  The ties at T are kept from the top gid down: block b keeps
+// min(eq_b, max(0, r - ties in the blocks above b)) of its eq_b ties, its largest ones.
+__global__ __launch_bounds__(256) void hits_select_kernel(HitsArgs a) {
+  __shared__ uint32_t hist[kSelBins];
+  __shared__ SelShared sh;
+  const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint16_t *row = a.counts + (uint64_t)q * a.stride + a.gid_begin;
+  const uint16_t *row2 = a.counts2 ? a.counts2 + (uint64_t)q * a.stride + a.gid_begin : nullptr;
+  uint32_t *bc = a.blk_counts + (uint64_t)q * a.n_blk, *bs = a.blk_skip + (uint64_t)q * a.n_blk;
+  uint32_t *bt = a.blk_tmp + (uint64_t)q * a.n_blk * kSelBlkWords;
+  uint32_t T = 0, r = 0;
+  const uint32_t n = sel_boundary<true>(row, row2, a.n_gids, a.min_score, a.top_k, hist, sh, bc, bs, bt, T, r);
+  if (n <= a.top_k) {
+    if (tid == 0) { a.thr[q] = a.min_score; a.hit_off[q] = n; }
+    return;
+  }
+  if (tid == 0) { a.thr[q] = T; a.hit_off[q] = a.top_k; }
+  const uint32_t vt = T & 15u;
+  uint32_t run = 0;   // ties in the blocks above the current 256
+  for (uint32_t c0 = 0; c0 < a.n_blk; c0 += 256) {
+    const uint32_t i = c0 + tid;
+    const bool valid = i < a.n_blk;
+    const uint32_t b = valid ? a.n_blk - 1 - i : 0u;   // thread order = descending block
+    uint32_t gt = 0, eq = 0;
+    if (valid) {
+      const uint32_t *t = bt + (size_t)b * kSelBlkWords;
+      gt = t[0];
+      for (uint32_t v = vt + 1; v < 16; ++v) gt += t[1 + v];
+      eq = t[1 + vt];
+    }
+    uint32_t incl = eq;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(incl, o, 64);
+      if (lane >= (uint32_t)o) incl += y;
+    }
+    __syncthreads();   // (sh.wsum of the previous round is read)
+    if (lane == 63) sh.wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) { const uint32_t x = sh.wsum[w]; if (w < wave) before += x; tot += x; }
+    const uint32_t after = run + before + incl - eq;   // ties in the blocks above b
+    const uint32_t kept = r > after ? (r - after < eq ? r - after : eq) : 0u;
+    if (valid) {
+      bc[b] = gt + kept;
+      bs[b] = kept == eq ? 0u : (kept == 0 ? kSkipAllTies : eq - kept);
+    }
+    run += tot;
   }
 }
 
@@ -1571,8 +1783,8 @@ hipError_t launch_plane_sum32(const uint16_t *a, const uint16_t *b, uint32_t *ou
 // hitlist_scan_kernel: hit_off[0..nq] = exclusive prefix of n[0..nq), 4096 queries per workgroup -- a workgroup first
 // adds up what lies before its block (at most a few hundred KB of u32, from L2), then scans its own 4096 -- and the
 // queries whose lists overflowed (n > hl_cap) are collected in over[1 ..], over[0] = how many (preset to 0).
-__global__ __launch_bounds__(1024) void hitlist_scan_kernel(const uint32_t *n, uint32_t nq, uint32_t hl_cap, unsigned long long *hit_off,
-                                                            uint32_t *over) {
+__global__ __launch_bounds__(1024) void hitlist_scan_kernel(const uint32_t *n, uint32_t nq, uint32_t hl_cap, uint32_t k,
+                                                            unsigned long long *hit_off, uint32_t *over) {
   __shared__ unsigned long long wave_tot[16];
   __shared__ unsigned long long s_base;
   __shared__ uint32_t s_over, s_over_base;
@@ -1584,14 +1796,17 @@ __global__ __launch_bounds__(1024) void hitlist_scan_kernel(const uint32_t *n, u
     const uint4 *n4 = (const uint4 *)n;
     const uint32_t m = q0 / 4;
     uint32_t i = tid;
-    for (; i + 3 * 1024 < m; i += 4 * 1024) {
-      const uint4 a0 = n4[i], a1 = n4[i + 1024], a2 = n4[i + 2048], a3 = n4[i + 3072];
-      part += (unsigned long long)a0.x + a0.y + a0.z + a0.w + a1.x + a1.y + a1.z + a1.w;
-      part += (unsigned long long)a2.x + a2.y + a2.z + a2.w + a3.x + a3.y + a3.z + a3.w;
+    if (k == 0) {
+      for (; i + 3 * 1024 < m; i += 4 * 1024) {
+        const uint4 a0 = n4[i], a1 = n4[i + 1024], a2 = n4[i + 2048], a3 = n4[i + 3072];
+        part += (unsigned long long)a0.x + a0.y + a0.z + a0.w + a1.x + a1.y + a1.z + a1.w;
+        part += (unsigned long long)a2.x + a2.y + a2.z + a2.w + a3.x + a3.y + a3.z + a3.w;
+      }
     }
-    for (; i < m; i += 1024) {
+    for (; i < m; i += 1024) {   // (top-k: a query's segment holds min(n, k))
       const uint4 a0 = n4[i];
-      part += (unsigned long long)a0.x + a0.y + a0.z + a0.w;
+      part += k ? (unsigned long long)min(a0.x, k) + min(a0.y, k) + min(a0.z, k) + min(a0.w, k)
+                : (unsigned long long)a0.x + a0.y + a0.z + a0.w;
     }
   }
 #pragma unroll
@@ -1612,6 +1827,12 @@ __global__ __launch_bounds__(1024) void hitlist_scan_kernel(const uint32_t *n, u
   for (int j = 0; j < 4; ++j) {
     x[j] = q + j < nq ? n[q + j] : 0ull;
     n_over += x[j] > hl_cap ? 1u : 0u;
+  }
+  bool ov[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ov[j] = x[j] > hl_cap;
+    if (k && x[j] > k) x[j] = k;
   }
   uint32_t my_over = n_over ? atomicAdd(&s_over, n_over) : 0u;
   const unsigned long long mine = x[0] + x[1] + x[2] + x[3];
@@ -1637,7 +1858,7 @@ __global__ __launch_bounds__(1024) void hitlist_scan_kernel(const uint32_t *n, u
   for (int j = 0; j < 4; ++j) {
     if (q + j < nq) hit_off[q + j] = run;
     run += x[j];
-    if (x[j] > hl_cap) over[1 + s_over_base + my_over++] = q + j;
+    if (ov[j]) over[1 + s_over_base + my_over++] = q + j;
   }
   if (tid == 0 && q0 + 4096u >= nq) hit_off[nq] = base + total;
 }
@@ -1700,15 +1921,18 @@ __device__ __forceinline__ void bitonic_desc_256(uint32_t *keys, uint32_t tid, u
 // workgroup each (grid-stride over the list the scan made): the hits are thresholded from the query's counter row
 // (src/niqki_index.cpp:662-666) into LDS as count << 16 | gid -- distinct keys whose descending order is
 // greater<pair<count, gid>> (:685) -- and ordered there by a bitonic network.  keys: P words of LDS (P >= 256).
-__global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over, uint32_t P) {
-  extern __shared__ __align__(16) uint32_t keys[];
+__global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uint32_t *hn, const uint32_t *hl, uint32_t hl_cap,
+                                                            const uint32_t *over, uint32_t P) {
+  extern __shared__ __align__(16) uint32_t keys[];   // (top-k: at least kSelBins words, the select's histogram)
   __shared__ uint32_t s_n;
+  __shared__ SelShared sh;
   const uint32_t tid = threadIdx.x;
   {
     const uint32_t lane = tid & 63u, q = blockIdx.x * 4 + (tid >> 6);
     if (q < a.nq) {
+      // the segment: the list, or with top-k its first k entries
       const unsigned long long seg0 = a.hit_off[q], n_all = a.hit_off[q + 1] - seg0;
-      if (n_all && n_all <= hl_cap) {
+      if (n_all && hn[q] <= hl_cap) {
         const uint32_t *src = hl + (uint64_t)q * hl_cap;
         for (uint32_t i = lane; i < (uint32_t)n_all; i += 64) {
           const unsigned long long pos = seg0 + i;
@@ -1724,20 +1948,28 @@ __global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uin
   const uint32_t n_over = over[0];
   for (uint32_t k = blockIdx.x; k < n_over; k += gridDim.x) {
     const uint32_t q = over[1 + k];
-    const unsigned long long seg0 = a.hit_off[q], n_all = a.hit_off[q + 1] - seg0;
+    // n_hit: the query's hits; n_all: its segment (min(n_hit, top_k) with top-k)
+    const unsigned long long seg0 = a.hit_off[q], n_all = a.hit_off[q + 1] - seg0, n_hit = hn[q];
     const uint16_t *row = a.counts + (uint64_t)q * a.stride + a.gid_begin;
-    if (n_all > P) {
+    if (n_hit > P) {
       // more hits than the network holds (a threshold that lets a sixth of the index through): one wave thresholds the
-      // row in descending gid and orders it with the stable radix passes of hits_sort_kernel, through tmp_*
+      // row in descending gid and orders it with the stable radix passes of hits_sort_kernel, through tmp_*.  With
+      // top-k the wave keeps c > T and the first r genomes of count T it meets (the largest gids): the select's boundary
+      uint32_t T = a.min_score, r = kSkipAllTies;
+      if (a.top_k && n_hit > a.top_k) sel_boundary<false>(row, nullptr, a.n_gids, a.min_score, a.top_k, keys, sh, nullptr, nullptr, nullptr, T, r);
       if (tid < 64) {
         uint32_t *cur = keys;   // 256 words
         const uint32_t lane = tid;
         const uint64_t lt_mask = (1ULL << lane) - 1ULL;
         unsigned long long run = 0;
+        uint32_t ties = 0;   // genomes of count T met so far
         for (uint32_t top = (a.n_gids + 63u) & ~63u; top > 0; top -= 64) {
           const uint32_t i = top - 1 - lane;
           const uint32_t c = i < a.n_gids ? (uint32_t)row[i] : 0u;
-          const bool hit = i < a.n_gids && c >= a.min_score;
+          const bool tie = i < a.n_gids && c == T;
+          const uint64_t tb = __ballot(tie);
+          const bool hit = i < a.n_gids && (c > T || (tie && ties + __popcll(tb & lt_mask) < r));
+          ties += __popcll(tb);
           const uint64_t bal = __ballot(hit);
           if (hit) {
             const unsigned long long pos = seg0 + run + __popcll(bal & lt_mask);
@@ -1763,7 +1995,7 @@ __global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uin
     if (tid == 0) s_n = 0;
     // the network's size for this query
     uint32_t Pq = 256;
-    while (Pq < n_all) Pq <<= 1;   // (n_all <= P here, and P >= 256 is a power of two)
+    while (Pq < n_hit) Pq <<= 1;   // (n_hit <= P here, and P >= 256 is a power of two)
     for (uint32_t i = tid; i < Pq; i += 256) keys[i] = 0u;
     __syncthreads();
     // 8 counters per lane and load (rows start on 128-byte lines: NIQKI_ROW_STRIDE)
@@ -1803,22 +2035,26 @@ __global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uin
 
 hipError_t launch_hitlist_scan(const uint32_t *n, const HitsArgs &a, uint32_t hl_cap, uint32_t *over, hipStream_t stream) {
   if (a.nq == 0) return hipSuccess;   // (over[0] = 0: the gather launch that made n has done it, CandOut::hl_over)
-  hipLaunchKernelGGL(hitlist_scan_kernel, dim3((a.nq + 4095u) / 4096u), dim3(1024), 0, stream, n, a.nq, hl_cap, a.hit_off, over);
+  hipLaunchKernelGGL(hitlist_scan_kernel, dim3((a.nq + 4095u) / 4096u), dim3(1024), 0, stream, n, a.nq, hl_cap, a.top_k, a.hit_off,
+                     over);
   return hipGetLastError();
 }
 
-hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over, hipStream_t stream) {
+hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over,
+                               hipStream_t stream) {
   if (a.nq == 0) return hipSuccess;
   // (the network: 2048 keys = 8 KB of LDS, eight workgroups per CU; a query with more hits takes the wave path)
   uint32_t P = 256;
   while (P < a.n_gids && P < 2048u) P <<= 1;
-  hipLaunchKernelGGL(hitlist_emit_kernel, dim3((a.nq + 3) / 4), dim3(256), (size_t)P * 4, stream, a, hl, hl_cap, over, P);
+  const uint32_t lds = a.top_k && P < kSelBins ? kSelBins : P;
+  hipLaunchKernelGGL(hitlist_emit_kernel, dim3((a.nq + 3) / 4), dim3(256), (size_t)lds * 4, stream, a, n, hl, hl_cap, over, P);
   return hipGetLastError();
 }
 
 hipError_t launch_hits_count(const HitsArgs &a, hipStream_t stream) {
   if (a.nq == 0 || a.n_blk == 0) return hipSuccess;
-  if (a.n_blk >= 8) hipLaunchKernelGGL(hits_count_kernel<true>, dim3(a.nq), dim3(1024), 0, stream, a);
+  if (a.top_k) hipLaunchKernelGGL(hits_select_kernel, dim3(a.nq), dim3(256), 0, stream, a);
+  else if (a.n_blk >= 8) hipLaunchKernelGGL(hits_count_kernel<true>, dim3(a.nq), dim3(1024), 0, stream, a);
   else hipLaunchKernelGGL(hits_count_kernel<false>, dim3((a.nq + 15) / 16), dim3(1024), 0, stream, a);
   hipLaunchKernelGGL(hits_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
   return hipGetLastError();

@@ -97,10 +97,11 @@ void Index::make_shards(const niqki_params &p0, int device, int n_gpus, const ui
 }
 
 Index::Index(uint32_t ilF, uint32_t iK, uint32_t iW, uint32_t iH, const std::string &out_filename,
-             double min_fract, int device, int n_gpus, int resident_mib) {
+             double min_fract, int device, int n_gpus, int resident_mib, uint32_t itop_k) {
   niqki_params p{};
   p.K = iK; p.S = ilF; p.W = iW; p.H = iH;
   p.resident_mib = resident_mib > 0 ? (uint32_t)resident_mib : 0u;
+  p.top_k = top_k = itop_k;
   p.min_score = niqki_min_score(min_fract, ilF);
   make_shards(p, device, n_gpus, nullptr);
   if (n_gpus > 1) {
@@ -112,7 +113,7 @@ Index::Index(uint32_t ilF, uint32_t iK, uint32_t iW, uint32_t iH, const std::str
 }
 
 Index::Index(const std::string &dump_file, bool pretty, const std::string &out_filename, int device, int n_gpus,
-             int resident_mib) {
+             int resident_mib, uint32_t itop_k) {
   pretty_printing = pretty;
   // The dump is streamed: header, then the buckets in groups of whole slots (the payload of a 100k-genome index is
   // 13.6 GB), then the names.  A dump this program wrote is a file of size-tagged gzip members (gzio.h): they are
@@ -151,6 +152,7 @@ Index::Index(const std::string &dump_file, bool pretty, const std::string &out_f
   p = 24;
   niqki_params prm{};
   prm.resident_mib = resident_mib > 0 ? (uint32_t)resident_mib : 0u;
+  prm.top_k = top_k = itop_k;   // (the dump does not hold it: niqki_import_begin takes it from the params)
   make_shards(prm, device, n_gpus, hdr);   // every shard keeps its own slots of the stream
   niqki_params q{};
   niqki_get_params(h_, &q);
@@ -334,7 +336,9 @@ void Index::flush_insert(Batch &b) {
 void Index::group_query_staged(uint32_t per, const std::vector<uint32_t> &n_entry, Hits &h) {
   const size_t G = sh_.size();
   const uint64_t N = niqki_genome_count(h_);
-  uint64_t cap = std::max<uint64_t>(uint64_t(1) << 20, (uint64_t)per * 64);
+  // top-k: at most per x k hits per rank, never NIQKI_E_CAPACITY
+  uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)per * std::min<uint64_t>(top_k, N), 1)
+                       : std::max<uint64_t>(uint64_t(1) << 20, (uint64_t)per * 64);
   std::vector<std::vector<uint64_t>> off(G, std::vector<uint64_t>(per + 1));
   std::vector<std::vector<uint32_t>> hc(G), hg(G);
   for (;;) {
@@ -369,7 +373,9 @@ void Index::group_query_staged(uint32_t per, const std::vector<uint32_t> &n_entr
 // hits of the staged entries
 void Index::query_staged(size_t n, Hits &h) {
   const uint64_t N = niqki_genome_count(h_);
-  uint64_t cap = std::max<uint64_t>(uint64_t(1) << 20, n * 64);
+  // top-k: at most n x k hits, never NIQKI_E_CAPACITY
+  uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1)
+                       : std::max<uint64_t>(uint64_t(1) << 20, n * 64);
   h.off.resize(n + 1);
   for (;;) {
     h.hc.resize(cap);

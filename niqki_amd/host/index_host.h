@@ -25,16 +25,17 @@ class Index {
   // batch are dealt to the GPUs in order, every GPU frames and sketches its share
   // resident_mib > 0 (the program's --resident-mib): a paged index -- the sketch store in page-locked host
   // memory, the inverted index built for one page of slots at a time within that budget
+  // top_k > 0 (the program's --top): a query reports the first top_k entries of its list (niqki_params.top_k)
   Index(uint32_t lF, uint32_t K, uint32_t W, uint32_t H, const std::string &out_filename, double min_fract,
-        int device = -1, int n_gpus = 1, int resident_mib = 0);
+        int device = -1, int n_gpus = 1, int resident_mib = 0, uint32_t top_k = 0);
   // Index(dump file, pretty, filename): src/niqki_index.cpp:63-102
   Index(const std::string &dump_file, bool pretty_printing, const std::string &out_filename, int device = -1,
-        int n_gpus = 1, int resident_mib = 0);
+        int n_gpus = 1, int resident_mib = 0, uint32_t top_k = 0);
   ~Index();
   Index(const Index &) = delete;
   Index &operator=(const Index &) = delete;
 
-  uint32_t K = 0, W = 0, H = 0, lF = 0, F = 0, min_score = 0;
+  uint32_t K = 0, W = 0, H = 0, lF = 0, F = 0, min_score = 0, top_k = 0;
   bool pretty_printing = true;
   std::vector<std::string> filenames;
   std::unique_ptr<ParallelTextWriter> outfile;

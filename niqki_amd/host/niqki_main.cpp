@@ -5,6 +5,7 @@
 //   --device <n>   HIP device ordinal (default: current device)
 //   --gpus <n>     cut the index by sketch-slot range over n GPUs (devices --device .. +n-1)
 //   --resident-mib <n>  paged index: sketch store in host memory, n MiB of device memory for one page of slots
+//   --top <n>      report at most n best hits per query (-Q / -q; niqki_params.top_k), 0 = all
 #include <libgen.h>
 #include <limits.h>
 #include <unistd.h>
@@ -31,7 +32,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -60,6 +61,7 @@ const Desc kDesc[] = {
     {DEVICE, "", "device", NUMERIC, "  --device <int>                HIP device ordinal."},
     {GPUS, "", "gpus", NUMERIC, "  --gpus <int>                  Number of GPUs the index is sharded over (1)."},
     {RESIDENT, "", "resident-mib", NUMERIC, "  --resident-mib <int>          Device memory budget of a paged index in MiB (0: everything resident)."},
+    {TOP, "", "top", NUMERIC, "  --top <int>                   Report at most <int> best hits per query (0: all)."},
 };
 
 struct Parsed {
@@ -254,6 +256,17 @@ int main(int argc, char *argv[]) {
   const double min_jaccard = o.has(MIN) ? atof(o.last(MIN).c_str()) : 0;
   const int device = int_opt(o, DEVICE, -1), n_gpus = int_opt(o, GPUS, 1), resident_mib = int_opt(o, RESIDENT, 0);
   const string out_file = o.has(OUTPUT) ? o.last(OUTPUT) : "niqkiOutput.gz";
+  // --top: the first k lines of each query's list (count descending, the larger gid first among equal counts)
+  uint32_t top_k = 0;
+  if (o.has(TOP)) {
+    const long long v = strtoll(o.last(TOP).c_str(), nullptr, 10);
+    if (v < 0 || v > (long long)UINT32_MAX) {
+      fprintf(stderr, "Option 'top' requires a number in 0..%u\n", UINT32_MAX);
+      cout << "Bad usage!!!" << endl;
+      return EXIT_FAILURE;
+    }
+    top_k = (uint32_t)v;
+  }
 
   const char *rule = "+-----------------------------------+-------------------------------+";
   cout << "+-------------------------------------------------------------------+" << endl
@@ -261,8 +274,8 @@ int main(int argc, char *argv[]) {
        << rule << endl;
   std::unique_ptr<nqhost::Index> ix;
   try {
-    if (o.has(LOAD)) ix.reset(new nqhost::Index(o.last(LOAD), true, out_file, device, n_gpus, resident_mib));
-    else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib));
+    if (o.has(LOAD)) ix.reset(new nqhost::Index(o.last(LOAD), true, out_file, device, n_gpus, resident_mib, top_k));
+    else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib, top_k));
     if (const unsigned expect = (unsigned)int_opt(o, GENOME_SIZE, 0)) ix->select_best_H(expect);   // src/niqki.cpp:303-305
 
     RunClock clk;
