@@ -444,7 +444,7 @@ int niqki_synchronize(niqki_index *ix) {
 int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
   if (!ix || !key) return NIQKI_E_INVALID;
   if (!std::strcmp(key, "gather_variant")) {
-    // launch shapes 0 (choose) .. 5; the measurement-only variants exist in ABLATION builds alone
+    // launch shapes 0 (choose) .. 5
     if (!nq::gather_variant_valid((int)value)) return fail(ix, NIQKI_E_INVALID, "unknown gather_variant");
     ix->gather_variant = (int)value;
     return NIQKI_OK;

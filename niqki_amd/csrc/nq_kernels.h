@@ -25,7 +25,6 @@ struct SketchArgs {
   uint32_t redo_only;         // != 0: this launch works only on the sketches whose flag has this value
   uint32_t redo_mark;         // != 0 (one-wavefront kernel): a sketch that exceeds the entry list gets this flag and is left
                               // to a later launch -- nothing of it is stored
-  uint32_t window;            // set by launch_sketch: the short-read kernel's passes read their targets a window ahead
 };
 // avg_len: average input bytes per sketch (picks the launch shape)
 hipError_t launch_sketch(const SketchArgs &a, uint32_t n_entry, uint64_t avg_len,

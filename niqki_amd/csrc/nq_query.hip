@@ -53,12 +53,12 @@ constexpr uint32_t kQueue = 256;  // items per wave-private LDS work queue
 // u16 ids of one chunk, UNROLL chunks per round trip, two rounds in flight (the
 // loads of round r+1 are issued before the LDS atomics of round r; unconditional
 // loads, lanes past a chunk's end read what follows it and are masked).
-// The form of indexes that are not padded (and of the measurement modes); padded ones take PairWalk below.
+// The form of indexes that are not padded; padded ones take PairWalk below.
 // n (wave uniform, PARTIAL only): how many of the 64 lanes hold a chunk -- the last batch of a tile's walk; a short
 // read's whole walk is such a batch of ~10 chunks per wave, and walking all 64 places cost it half of its instructions.
-template <int UNROLL, int MODE, bool PARTIAL = false>
+template <int UNROLL, bool PARTIAL = false>
 __device__ __forceinline__ void walk64(const uint16_t *gl, uint32_t a, uint32_t pos, uint32_t len,
-                                       uint32_t lane, uint32_t *cnt, uint32_t &sink, uint32_t n = 64) {
+                                       uint32_t lane, uint32_t *cnt, uint32_t n = 64) {
   uint32_t ga[UNROLL], gb[UNROLL];
   auto fetch = [&](uint32_t j0, uint32_t (&g)[UNROLL]) {
 #pragma unroll
@@ -71,8 +71,7 @@ __device__ __forceinline__ void walk64(const uint16_t *gl, uint32_t a, uint32_t 
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const uint32_t l = __builtin_amdgcn_readlane(len, j0 + u);
-      if (MODE == 1) { if (lane < l) sink ^= g[u]; }
-      else bump_if(cnt, g[u], lane < l, lane);
+      bump_if(cnt, g[u], lane < l, lane);
     }
   };
   fetch(0, ga);
@@ -153,121 +152,6 @@ struct PairWalk {
       __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   }
-#ifdef NQ_ABLATION
-  // COST MODEL of a one-tile walk (measurement only, wrong counters): per id what byte counters for
-  // 100 000 genomes in one tile would cost on top of the same lines -- a half-select by the id's position in its line
-  // (ids stay 16 bits: a bucket as [ids below the split | ids above]), the byte's increment 1 << 8 (id & 3) as a
-  // RETURNING ds_add, and the test whether the byte just wrapped (its old value 0xFF: the carry has to be logged).
-  uint32_t sa[L], sb[L];   // the chunks' split positions (stand-in: their lengths, fetched with the positions)
-  __device__ __forceinline__ void fetch_model(uint32_t (&g)[L], uint32_t (&sp)[L], const Item *items, uint32_t j0) {
-    const Item *mine = items + half;
-    uint32_t pos[L];
-#pragma unroll
-    for (int k = 0; k < L; ++k) { const Item it = mine[j0 + 2 * k]; pos[k] = it.pos; sp[k] = it.len; }
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-      uint64_t addr;
-      asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(addr) : "v"(pos[k]), "s"(128u), "v"((uint64_t)lane_base) : "vcc");
-      g[k] = *(const __attribute__((address_space(1))) uint32_t *)addr;
-    }
-  }
-  // PARTS 4 / 5 / 6 take the SHIPPED walk apart instead: 4 = its loads and vector work without the LDS atomics (the ids
-  // are folded into a register), 5 = one of its two atomics per dword, 6 = the chunks' positions by v_readlane from one
-  // queue read per batch instead of a ds_read_b32 per load.
-  __device__ __forceinline__ bool apply_part(uint32_t (&g)[L], int part) {
-    uint32_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-      uint32_t even, addr, odd, inc, hi;
-      asm("v_and_b32 %0, 0xfffe, %1" : "=v"(even) : "v"(g[k]));
-      asm("v_add_u32 %0, %1, %1" : "=v"(addr) : "v"(even));
-      asm("v_and_b32 %0, 1, %1" : "=v"(odd) : "v"(g[k]));
-      asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(inc) : "v"(odd), "s"(0xFFFFu));
-      if (part == 4) acc ^= addr + inc;
-      else __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      asm("v_lshrrev_b32 %0, 16, %1" : "=v"(hi) : "v"(g[k]));
-      asm("v_and_b32 %0, 0xfffe, %1" : "=v"(even) : "v"(hi));
-      asm("v_add_u32 %0, %1, %1" : "=v"(addr) : "v"(even));
-      asm("v_and_b32 %0, 1, %1" : "=v"(odd) : "v"(hi));
-      asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(inc) : "v"(odd), "s"(0xFFFFu));
-      if (part == 4 || part == 5) acc ^= addr + inc;
-      else __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return acc == 0x12345u;
-  }
-  __device__ __forceinline__ void fetch_readlane(uint32_t (&g)[L], uint32_t posreg, uint32_t j0) {
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-      const uint32_t pa = __builtin_amdgcn_readlane(posreg, j0 + 2 * k), pb = __builtin_amdgcn_readlane(posreg, j0 + 2 * k + 1);
-      const uint32_t pos = half ? pb : pa;
-      uint64_t addr;
-      asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(addr) : "v"(pos), "s"(128u), "v"((uint64_t)lane_base) : "vcc");
-      g[k] = *(const __attribute__((address_space(1))) uint32_t *)addr;
-    }
-  }
-  template <int PART>
-  __device__ __forceinline__ bool batch_part(const Item *items, uint32_t lane) {
-    constexpr int R = 64 / UNROLL;
-    bool x = false;
-    if (PART == 6) {
-      const uint32_t posreg = items[lane].pos;
-      fetch_readlane(ga, posreg, 0);
-#pragma unroll
-      for (int r = 0; r < R; r += 2) {
-        fetch_readlane(gb, posreg, (r + 1) * UNROLL);
-        apply(ga);
-        if (r + 2 < R) fetch_readlane(ga, posreg, (r + 2) * UNROLL);
-        apply(gb);
-      }
-      return false;
-    }
-    fetch(ga, items, 0);
-#pragma unroll
-    for (int r = 0; r < R; r += 2) {
-      fetch(gb, items, (r + 1) * UNROLL);
-      x |= apply_part(ga, PART);
-      if (r + 2 < R) fetch(ga, items, (r + 2) * UNROLL);
-      x |= apply_part(gb, PART);
-    }
-    return x;
-  }
-  template <int PARTS>   // 3: all of it; 1: returning add + wrap test only; 2: half-select only (plain ds_add on the byte)
-  __device__ __forceinline__ bool apply_model(uint32_t (&g)[L], uint32_t (&sp)[L], uint32_t p0) {
-    bool carry = false;
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const uint32_t id = h ? g[k] >> 16 : g[k];                          // (the low id needs no mask: the and below drops the rest)
-        const uint32_t off = (PARTS & 2) ? ((p0 + (uint32_t)h >= sp[k]) ? 0x8000u : 0u) : 0u;   // which half of the genomes (model: an offset that stays inside the counters)
-        const uint32_t addr = (id & 0xFFFCu) | off;
-        const uint32_t sh = (id << 3) & 31u;
-        if (PARTS & 1) {
-          const uint32_t old = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          carry |= ((old >> sh) & 0xFFu) == 0xFFu;
-        } else {
-          __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-    }
-    return carry;
-  }
-  template <int PARTS>
-  __device__ __forceinline__ bool batch_model(const Item *items, uint32_t p0) {
-    constexpr int R = 64 / UNROLL;
-    bool carry = false;
-    fetch_model(ga, sa, items, 0);
-#pragma unroll
-    for (int r = 0; r < R; r += 2) {
-      fetch_model(gb, sb, items, (r + 1) * UNROLL);
-      carry |= apply_model<PARTS>(ga, sa, p0);
-      if (r + 2 < R) fetch_model(ga, sa, items, (r + 2) * UNROLL);
-      carry |= apply_model<PARTS>(gb, sb, p0);
-    }
-    return carry;
-  }
-#endif
   // 64 chunks: items[0 .. 64) of the wave's queue; all their lines in flight before the first id is counted
   // (keeping a round in flight across batches, over the cutting of the next buckets, gained nothing: measured)
   __device__ __forceinline__ void batch(const Item *items) {
@@ -292,18 +176,15 @@ struct PairWalk {
 // fingerprints two.  Buckets are cut into chunks of <= 64 ids that go through a
 // wave-private LDS queue, so the walk always runs on full batches of 64 chunks
 // whatever the bucket lengths are.
-// MODE is a measurement aid (results are wrong for MODE != 0): 1 = no LDS
-// atomics, 6 = lookups only, 7 = counters not written back, 8 = no walk (zero + write-back only).  MODE != 0 is instantiated only in -DNQ_ABLATION builds;
-// the shipped library cannot be switched into it.
 //   PRE      : entries come from the slot-major look-up pre-pass (lookup_kernel below): one
 //              packed word per (query, tile, slot) = bucket start relative to the slot's first
 //              unit << 16 | length, read coalesced; no table access in this kernel at all.
 //   PAD      : padded index (whole-line chunks): batches go through PairWalk (two lines per load), and the four
 //              waves of a SIMD take turns at the top issue priority; otherwise walk64 with explicit lengths.
 //   ahead    : (PRE) this wave's first two look-ups of the tile, issued a tile earlier by the caller / this function.
-template <int BLOCK, int UNROLL, int NT, bool STASH_OUT, bool STASH_IN, int MODE, bool PRE = false, bool PAD = false>
+template <int BLOCK, int UNROLL, int NT, bool STASH_OUT, bool STASH_IN, bool PRE = false, bool PAD = false>
 __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk, uint32_t q, uint32_t t,
-                                          uint32_t *cnt, Item *queue, Entry *stash, uint32_t &sink,
+                                          uint32_t *cnt, Item *queue, Entry *stash,
                                           uint32_t it_lo, uint32_t n_it, const uint32_t *pre = nullptr,
                                           Entry *ahead = nullptr) {
   // slots [64 * it_lo, min(64 * n_it, f_local)): one pass of the kernel
@@ -317,7 +198,7 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
   const uint32_t *my_units = v.slot_units + (uint64_t)t * (v.f_local + 1);
   Item *wq = queue + wave * kQueue;
   uint32_t q_head = 0, q_count = 0;  // wave-uniform
-  constexpr bool PAIR = PAD && (MODE == 0 || (MODE >= 9 && MODE <= 14)) && (UNROLL == 16 || UNROLL == 32);
+  constexpr bool PAIR = PAD && (UNROLL == 16 || UNROLL == 32);
   uint32_t prio_turn = wave >> 2;   // the four waves of a SIMD take turns at the issue arbiter's top priority (PAIR)
   PairWalk<PAIR ? UNROLL : 32> pw;
   pw.init(gl, lane);
@@ -365,14 +246,6 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
         else if (prio_turn == 1) __builtin_amdgcn_s_setprio(1);
         else if (prio_turn == 2) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(3);
-#ifdef NQ_ABLATION
-        if constexpr (MODE == 12 || MODE == 13 || MODE == 14) {
-          if (__any(pw.template batch_part<MODE == 12 ? 4 : MODE == 13 ? 5 : 6>(wq + q_head, lane))) sink += 1u;
-        } else if constexpr (MODE == 9 || MODE == 10 || MODE == 11) {
-          // (a wrapped byte would be logged: one append to a per-query list in global memory, by the lanes that saw one)
-          if (__any(pw.template batch_model<MODE == 9 ? 3 : MODE == 10 ? 1 : 2>(wq + q_head, 2u * (lane & 31u)))) sink += 1u;
-        } else
-#endif
         pw.batch(wq + q_head);             // (q_head is a multiple of 64: a batch never wraps; a wave's LDS traffic is in order)
         q_head = (q_head + 64) & (kQueue - 1);
         q_count -= 64;
@@ -381,7 +254,7 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
       const Item x = wq[(q_head + lane) & (kQueue - 1)];
       q_head = (q_head + 64) & (kQueue - 1);
       q_count -= 64;
-      walk64<UNROLL, MODE>(gl, a, x.pos, x.len, lane, cnt, sink);
+      walk64<UNROLL>(gl, a, x.pos, x.len, lane, cnt);
     }
   };
 
@@ -445,10 +318,7 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
       }
 #pragma unroll
       for (int k = 0; k < kDeep; ++k)
-        if (live[k]) {   // (wave-uniform)
-          if (MODE == 6) { sink += en[k].start ^ en[k].len; continue; }
-          cut_and_walk(en[k].start, en[k].len);
-        }
+        if (live[k]) cut_and_walk(en[k].start, en[k].len);   // (wave-uniform)
     }
     if (q_count) {  // the last partial batch; "no chunk" = the tile's spare line of padding ids
       if constexpr (PAIR) {
@@ -457,7 +327,7 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
       } else {
         Item x = wq[(q_head + lane) & (kQueue - 1)];
         if (lane >= q_count) x = Item{PAD ? my_units[v.f_local] : 0u, 0u};
-        walk64<(UNROLL > 8 ? 8 : UNROLL), MODE, true>(gl, a, x.pos, x.len, lane, cnt, sink, q_count);
+        walk64<(UNROLL > 8 ? 8 : UNROLL), true>(gl, a, x.pos, x.len, lane, cnt, q_count);
       }
     }
     return;
@@ -506,7 +376,6 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
           my_stash[(uint64_t)(k - 1) * v.f_local + s] = Entry{cur.e[k].start, cur_ok ? cur.e[k].len : 0u};
       }
     }
-    if (MODE == 6) { sink += pos ^ rem; cur = nxt; cur_ok = nxt_ok; nxt = nxt2; nxt_ok = nxt2_ok; continue; }
     cut_and_walk(pos, rem);
     cur = nxt;
     cur_ok = nxt_ok;
@@ -520,7 +389,7 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
     } else {
       Item x = wq[(q_head + lane) & (kQueue - 1)];
       if (lane >= q_count) x = Item{PAD ? my_units[v.f_local] : 0u, 0u};
-      walk64<(UNROLL > 8 ? 8 : UNROLL), MODE, true>(gl, a, x.pos, x.len, lane, cnt, sink, q_count);
+      walk64<(UNROLL > 8 ? 8 : UNROLL), true>(gl, a, x.pos, x.len, lane, cnt, q_count);
     }
   }
 }
@@ -892,7 +761,7 @@ extern "C" int nq_debug_gather_clock(unsigned long long *buf) { return (int)hipM
 // Its barriers order LDS traffic only (lds_barrier): threads never read each other's global writes here,
 // and the look-ups already on their way for the next tile must not be waited for.
 // NT = -1: every tile's entries come from the look-up pre-pass (`stash` then holds its packed words)
-template <int BLOCK, int UNROLL, int NT, int MODE = 0, bool PAD = false>
+template <int BLOCK, int UNROLL, int NT, bool PAD = false>
 __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_t *sketches,
                                                        uint16_t *counts, uint16_t *counts2, uint64_t stride, Entry *stash,
                                                        const uint32_t *order, uint32_t nq, CandOut co) {
@@ -921,7 +790,6 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
   // instantiation has no static LDS in front of its dynamic block and otherwise launches the form without PAD)
   const int32_t *sk = NT < 0 ? nullptr : sketches + (uint64_t)q * v.q_stride + v.q_off;
   Item *queue = (Item *)(cnt + (v.tile + 1) / 2 + (PAD ? kPadWords : 0u));  // behind the counters: kQueue items per wave
-  uint32_t sink = 0;
   const bool want_cand = co.cand != nullptr;
   const bool want_surv = co.surv != nullptr;
   const uint32_t emit_thr = want_surv ? co.surv_thr : co.thr;   // surv_thr <= thr
@@ -1011,23 +879,20 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
     }
     zeroed = false;
     NQ_GCLK(1 + 4 * (t & 1));
-    if constexpr (MODE == 8) {
-    } else if constexpr (NT < 0) {
-      walk_tile<BLOCK, UNROLL, 1, false, false, MODE, true, PAD>(v, sk, q, t, cnt, queue, nullptr, sink, it_lo, n_it, (const uint32_t *)stash, ahead);
+    if constexpr (NT < 0) {
+      walk_tile<BLOCK, UNROLL, 1, false, false, true, PAD>(v, sk, q, t, cnt, queue, nullptr, it_lo, n_it, (const uint32_t *)stash, ahead);
     } else if constexpr (NT >= 2) {
-      if (t == 0) walk_tile<BLOCK, UNROLL, NT, true, false, MODE, false, PAD>(v, sk, q, t, cnt, queue, stash, sink, it_lo, n_it);
-      else walk_tile<BLOCK, UNROLL, NT, false, true, MODE, false, PAD>(v, sk, q, t, cnt, queue, stash, sink, it_lo, n_it);
+      if (t == 0) walk_tile<BLOCK, UNROLL, NT, true, false, false, PAD>(v, sk, q, t, cnt, queue, stash, it_lo, n_it);
+      else walk_tile<BLOCK, UNROLL, NT, false, true, false, PAD>(v, sk, q, t, cnt, queue, stash, it_lo, n_it);
     } else {
-      walk_tile<BLOCK, UNROLL, 1, false, false, MODE, false, PAD>(v, sk, q, t, cnt, queue, stash, sink, it_lo, n_it);
+      walk_tile<BLOCK, UNROLL, 1, false, false, false, PAD>(v, sk, q, t, cnt, queue, stash, it_lo, n_it);
     }
-    if (MODE != 0) cnt[tid % n_words] ^= sink;
     if (want_cand && tid == 0) { lds_n[0] = n_surv; lds_n[1] = n_cand; }
     if (co.hl && tid == 0) lds_n[0] = 0;
     NQ_GCLK_WAVE(16 + 16 * (t & 1));
     NQ_GCLK(2 + 4 * (t & 1));
     lds_barrier();
     NQ_GCLK(3 + 4 * (t & 1));
-    if (MODE == 7) continue;
     if (plane == nullptr) {
       // no counter row (survivor output only): the tile's counters are scanned where they are
       // ... and left at zero for the next tile (whose counters are no more than this one's)
@@ -1206,9 +1071,6 @@ hipError_t launch_order(const IndexView &v, const int32_t *sketches, uint32_t nq
 }
 
 bool gather_variant_valid(int variant) {
-#ifdef NQ_ABLATION
-  if (variant == 11 || variant == 12 || variant == 16 || variant == 17 || variant == 18 || (variant >= 19 && variant <= 24)) return true;
-#endif
   return variant >= 0 && variant <= 5;
 }
 
@@ -1242,8 +1104,8 @@ hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t n
   // (any LDS base, any index layout) is launched instead.
   static const bool pad_at_zero = [] {
     hipFuncAttributes fa{};
-    return hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 32, -1, 0, true>) == hipSuccess && fa.sharedSizeBytes == 0 &&
-           hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 16, 2, 0, true>) == hipSuccess && fa.sharedSizeBytes == 0;
+    return hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 32, -1, true>) == hipSuccess && fa.sharedSizeBytes == 0 &&
+           hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 16, 2, true>) == hipSuccess && fa.sharedSizeBytes == 0;
   }();
   const bool padded = v.padded && pad_at_zero;
 #define NQ_BY_TILES(B, U, ...)                                                                   \
@@ -1255,30 +1117,17 @@ hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t n
     else NQ_LAUNCH_GATHER(B, U, 1, ##__VA_ARGS__);                                               \
   } while (0)
   switch (variant) {
-    case 1: if (padded) NQ_BY_TILES(1024, 8, 0, true); else NQ_BY_TILES(1024, 8); break;
-    case 2: if (padded) NQ_BY_TILES(1024, 32, 0, true); else NQ_BY_TILES(1024, 32); break;
+    case 1: if (padded) NQ_BY_TILES(1024, 8, true); else NQ_BY_TILES(1024, 8); break;
+    case 2: if (padded) NQ_BY_TILES(1024, 32, true); else NQ_BY_TILES(1024, 32); break;
     case 3: NQ_BY_TILES(512, 16); break;
     case 4: NQ_BY_TILES(256, 16); break;
     case 5: NQ_BY_TILES(128, 16); break;
-#ifdef NQ_ABLATION  // measurement builds only (make ABLATION=1): these variants return wrong counters
-    case 11: NQ_BY_TILES(1024, 16, 1); break;
-    case 12: NQ_BY_TILES(1024, 32, 1, true); break;
-    case 16: NQ_BY_TILES(1024, 16, 6); break;
-    case 17: NQ_BY_TILES(1024, 16, 7, true); break;
-    case 18: NQ_BY_TILES(1024, 16, 8, true); break;
-    case 19: NQ_BY_TILES(1024, 32, 9, true); break;   // the one-tile walk's per-id cost on the same lines (PairWalk::apply_model)
-    case 20: NQ_BY_TILES(1024, 32, 10, true); break;  // ... its returning byte add + wrap test alone
-    case 21: NQ_BY_TILES(1024, 32, 11, true); break;  // ... its half-select alone (plain ds_add on the byte)
-    case 22: NQ_BY_TILES(1024, 32, 12, true); break;  // the shipped walk without its LDS atomics
-    case 23: NQ_BY_TILES(1024, 32, 13, true); break;  // ... with one of the two atomics per dword
-    case 24: NQ_BY_TILES(1024, 32, 14, true); break;  // ... with the chunks' positions by v_readlane (no ds_read per load); counters exact
-#endif
     default:
       // small tiles (short-read indexes): counters of <= 24 KB leave room for several
       // workgroups per CU, and 4 waves per query then beat 16 (tools/bench_reads.py)
       if (v.tile <= 12288) NQ_BY_TILES(256, 16);
-      else if (padded && pre) NQ_BY_TILES(1024, 32, 0, true);   // without look-ups of its own the walk gains from 32 lines per round trip (8.42 against 8.6 ms)
-      else if (padded) NQ_BY_TILES(1024, 16, 0, true);   // padded index: mask-free bucket walk
+      else if (padded && pre) NQ_BY_TILES(1024, 32, true);   // without look-ups of its own the walk gains from 32 lines per round trip (8.42 against 8.6 ms)
+      else if (padded) NQ_BY_TILES(1024, 16, true);   // padded index: mask-free bucket walk
       else NQ_BY_TILES(1024, 16);
       break;
   }

@@ -971,9 +971,9 @@ __device__ __forceinline__ bool densify_tail(uint32_t *sk, uint32_t *scratch, ui
 // wave costs one ballot.  The window read may be stale for the later passes of its window in one direction only: a
 // cell it saw empty may have been filled by an earlier pass of the window (cells never go back to empty); the
 // proposal that follows is then a ds_min on an occupied cell, which changes nothing, and its read-back is not the
-// proposer's own word.  Exactly the passes of the plain loop below; 1.05 x its speed on 150- and 300-base reads
-// (profiles/r06_densify_forms.txt, form a: the passes are paid in LDS instructions, and this form issues fewer only
-// where no lane proposes).
+// proposer's own word.  Exactly the passes of the plain loop it replaced (every entry proposing in every pass);
+// 1.05 x its speed on 150- and 300-base reads (profiles/r06_densify_forms.txt, form a: the passes are paid in LDS
+// instructions, and this form issues fewer only where no lane proposes).
 template <int R, int U>
 __device__ __forceinline__ void densify_wave_entries_window(uint32_t *sk, const uint32_t *elist, uint32_t n_ent,
                                                             uint32_t F, uint32_t empty, uint32_t *scratch, bool tail) {
@@ -1057,56 +1057,6 @@ __device__ __forceinline__ void densify_wave_entries_window(uint32_t *sk, const 
       if (densify_tail<R>(sk, scratch, F, T, B, mk, V)) return;
       tail = false;
     }
-  }
-}
-
-// The plain form (NIQKI_DENSIFY_WINDOW=0: the A/B figure in profiles/): every entry proposes in every pass.
-template <int R>
-__device__ __forceinline__ void densify_wave_entries(uint32_t *sk, const uint32_t *elist, uint32_t n_ent,
-                                                     uint32_t F, uint32_t empty) {
-  const uint32_t lane = threadIdx.x, Fm = F - 1u;
-  uint32_t T[R], B[R], mk[R], V[R];
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    const uint32_t e = (uint32_t)k * 64u + lane;
-    const bool valid = e < n_ent;
-    const uint32_t v = valid ? elist[2 * e + 1] : 0u;
-    V[k] = v;
-    mk[k] = valid ? (0x80000000u | elist[2 * e]) : kEmpty32;  // a min with "empty" changes nothing
-    T[k] = (uint32_t)unrev64(v);
-    B[k] = (uint32_t)rev64(v);
-  }
-  uint32_t idle = 0;
-  for (;;) {
-#pragma unroll
-    for (int k = 0; k < R; ++k)
-      if (mk[k] != kEmpty32) atomicMin(&sk[T[k] & Fm], mk[k]);   // (lanes without an entry stay out of the LDS)
-    wave_lds_order();
-    // all proposals of the wave are issued before any read-back: a read sees the surviving proposal
-    // of its cell (which names exactly one entry), or, behind another entry's winner write of this
-    // pass, that winner's value -- not its own proposal either way.  One LDS round trip per pass:
-    // only the read-back is waited for; the winner writes and the next pass's proposals follow in order.
-    uint32_t back[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) back[k] = sk[T[k] & Fm];   // (unconditional: masking these reads costs 30 %)
-    wave_lds_order();
-    uint32_t tot = 0;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const uint32_t t = T[k] & Fm;
-      const bool won = back[k] == mk[k] && mk[k] != kEmpty32;
-      if (won) {
-        sk[t] = V[k];
-        const uint32_t m = 0x80000000u | t;
-        mk[k] = m < mk[k] ? m : mk[k];
-      }
-      tot += (uint32_t)__popcll(__ballot(won));
-      T[k] += B[k];
-    }
-    wave_lds_order();
-    empty -= tot;
-    idle = tot ? 0u : idle + 1u;
-    if (empty == 0 || idle >= F) break;
   }
 }
 
@@ -1234,22 +1184,15 @@ __global__ __launch_bounds__(64) void sketch_reads_kernel(SketchArgs a) {
         densify_wave_cells(sk, d, empty0);
       } else {
         const uint32_t rounds = (n_ent + 63u) >> 6;   // wave uniform
-        if (a.window) {
-          // (the entries are in registers by then: their list's space holds the tail's two lists)
-          uint32_t *scratch = elist;
-          static_assert(192 * 8 >= 2 * 64 * 4, "the tail's lists live in the entry list's space");
-          const bool tail = a.window >= 2 && quads;
-          if (rounds <= 1) densify_wave_entries_window<1, 8>(sk, elist, n_ent, F, empty0, scratch, tail);
-          else if (rounds <= 2) densify_wave_entries_window<2, 8>(sk, elist, n_ent, F, empty0, scratch, tail);
-          else if (rounds <= 3) densify_wave_entries_window<3, 4>(sk, elist, n_ent, F, empty0, scratch, tail);
-          else if (rounds <= 4) densify_wave_entries_window<4, 4>(sk, elist, n_ent, F, empty0, scratch, tail);
-          else densify_wave_entries_window<6, 4>(sk, elist, n_ent, F, empty0, scratch, tail);
-        }
-        else if (rounds <= 1) densify_wave_entries<1>(sk, elist, n_ent, F, empty0);
-        else if (rounds <= 2) densify_wave_entries<2>(sk, elist, n_ent, F, empty0);
-        else if (rounds <= 3) densify_wave_entries<3>(sk, elist, n_ent, F, empty0);
-        else if (rounds <= 4) densify_wave_entries<4>(sk, elist, n_ent, F, empty0);
-        else densify_wave_entries<6>(sk, elist, n_ent, F, empty0);
+        // (the entries are in registers by then: their list's space holds the tail's two lists; the closed-form
+        // tail runs where the cells are moved as quads)
+        uint32_t *scratch = elist;
+        static_assert(192 * 8 >= 2 * 64 * 4, "the tail's lists live in the entry list's space");
+        if (rounds <= 1) densify_wave_entries_window<1, 8>(sk, elist, n_ent, F, empty0, scratch, quads);
+        else if (rounds <= 2) densify_wave_entries_window<2, 8>(sk, elist, n_ent, F, empty0, scratch, quads);
+        else if (rounds <= 3) densify_wave_entries_window<3, 4>(sk, elist, n_ent, F, empty0, scratch, quads);
+        else if (rounds <= 4) densify_wave_entries_window<4, 4>(sk, elist, n_ent, F, empty0, scratch, quads);
+        else densify_wave_entries_window<6, 4>(sk, elist, n_ent, F, empty0, scratch, quads);
         static_assert(kReadEntries == 6, "dispatch above covers 1..6 rounds");
       }
     }
@@ -1426,9 +1369,6 @@ hipError_t launch_sketch(const SketchArgs &a_in, uint32_t n_entry, uint64_t avg_
     a.read_entries = sketch_reads_entries(avg_len);
     const size_t wl = sketch_reads_lds_bytes(a.d, a.read_entries);
     if (sketch_reads_shape(a.d, avg_len, a.splits, a.halves)) {
-      const char *dw = std::getenv("NIQKI_DENSIFY_WINDOW");   // 0: every entry proposes in every pass (measurement)
-      const char *dt = std::getenv("NIQKI_DENSIFY_TAIL");     // 0: passes to the end, no closed-form tail (measurement)
-      a.window = (dw && std::atoi(dw) == 0) ? 0u : (dt && std::atoi(dt) == 0) ? 1u : 2u;
       hipError_t e = hipFuncSetAttribute((const void *)sketch_reads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
       if (e != hipSuccess) return e;
       hipLaunchKernelGGL(sketch_reads_kernel, dim3(n_entry), dim3(64), wl, stream, a);
@@ -1568,7 +1508,7 @@ hipError_t launch_copy_probe(const void *src, void *dst, uint64_t bytes, hipStre
 // workgroup with the 150-base kernel's LDS footprint (the F = 4096 cells + entry list + code tile: 8 workgroups per
 // CU), two register entries per lane (a 150-base read has ~120 occupied cells), per pass two ds_min_u32 proposals
 // to pseudo-random cells, their read-backs behind them in issue order, a ballot + popcount and the advance of the
-// targets -- densify_wave_entries<2> without winner writes.  The rate of these passes is the ceiling the passes of
+// targets -- the plain pass (every entry proposing) without winner writes.  The rate of these passes is the ceiling the passes of
 // sketch_reads_kernel are measured against (LDS round-trip latency at 8 waves per CU).
 __global__ __launch_bounds__(64) void lds_pass_probe_kernel(uint32_t iters, uint32_t *sink) {
   extern __shared__ __align__(16) uint32_t smem[];

@@ -111,7 +111,7 @@ def test_config3_all_columns_and_hit_lists_vs_oracle(native, po, big):
     e.set_option("lookup_prepass", -1)
     # the launch form bench.py times -- 4096 queries in one call: table rows streamed through LDS
     # (lookup_rows_kernel, four groups of 1024 queries), locality probe + order over all 4096,
-    # gather_kernel<1024, 32, -1, 0, true>: rows CHECK of that call (every 61st launch position, all four
+    # gather_kernel<1024, 32, -1, true>: rows CHECK of that call (every 61st launch position, all four
     # groups) are the oracle's columns, the hit lists likewise
     import torch
     big_sk = BIG["qsk"]
