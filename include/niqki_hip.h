@@ -181,10 +181,11 @@ int niqki_synchronize(niqki_index *ix);
  * "sketch_lane_cus" (0 = default: all; n: the lane of niqki_sketch_ahead is made anew on the TOP n compute units of the
  * device's numbering (hipExtStreamCreateWithCUMask) -- for a caller that fences the two lanes, with its own stream
  * limited to the other units; on one MI355X the split is no faster than the hardware's own dispatch),
- * "hit_lists" (1 = default: on an index of ONE counter tile of at most 12 288 genomes -- the short-read shape of
- * src/niqki_index.cpp:412-430 -- niqki_query* / niqki_staged_query take a query's thresholded hits out of the gather
- * kernel while its counters are in LDS, already ordered, instead of writing a 2N-byte counter row per query and reading
- * it again; 0 = always through counter rows), "hit_list_cap" (1..2048, default 256: hits per query such a list holds; a
+ * "hit_lists" (1 = default: on a resident single-segment index with counts below 2^16 -- one counter tile of at most
+ * 12 288 genomes, the short-read shape of src/niqki_index.cpp:412-430, or a larger index of any number of tiles whose
+ * counters leave room for the list in a workgroup's LDS -- niqki_query* / niqki_staged_query take a query's thresholded
+ * hits out of the gather kernel while its counters are in LDS, already ordered, instead of writing a 2N-byte counter
+ * row per query and reading it again; 0 = always through counter rows), "hit_list_cap" (1..2048, default 256: hits per query such a list holds; a
  * query with more -- min_score 0: every genome -- leaves through its counter row and is ordered from there),
  * "inflate_window" (-1 = default: a launch of the device inflate, NIQKI_FILE_GZIP below, keeps each file's whole 32 KB
  * window in LDS -- four files per CU at a time -- unless it holds more files than that runs at once; then only the

@@ -256,17 +256,30 @@ int hits_dev(niqki_index *ix, const uint16_t *counts, uint32_t nq, uint64_t stri
   return NIQKI_OK;
 }
 
-// the built index takes the hit-list form of query_hits_dev (one small tile, one segment, resident, one plane)
+// the list capacity of the hit-list form: hit_list_cap rounded up to whole 16-byte pieces
+static uint32_t hit_list_cap(const niqki_index *ix) {
+  return std::min<uint32_t>((std::max<uint32_t>(ix->hit_list_cap, 1) + 3u) & ~3u, nq::kHitListMaxCap);
+}
+
+// the built index takes the hit-list form of query_hits_dev (one segment, resident, one plane, counts < 2^16, the
+// gather kernel's counters + queues + list within a workgroup's LDS).  An index of at most kHitListMaxTile genomes is
+// one tile unless option tile_genomes splits it; such a split index keeps counter rows, as it did before the form took
+// several tiles.  There is no speed or correctness reason for that: it keeps the behaviour the top-k tile tests pin
+// (tests/test_gpu_topk.py, form "tiles": counter rows on 3 000 genomes in tiles of 512).
+// At min_score 0 every genome is a hit and every query of an index larger than kHitListMaxTile (beyond the cap) falls
+// back to its row with N hits: there counter rows are faster (100 000 genomes: 7.8 ms against 23.0 in the emit's wave
+// radix passes, tools/bench_hitlists_overflow.py), and such an index keeps them.
 static bool hit_lists_apply(const niqki_index *ix) {
   const uint32_t N = ix->built_n;
-  return ix->hit_lists && N && !ix->resident_bytes && !two_planes(ix) && ix->n_tiles == 1 && ix->delta_n == 0 &&
-         ix->tile <= nq::kHitListMaxTile && ix->g_base == 0 && N <= 65536u;
+  return ix->hit_lists && N && !ix->resident_bytes && !two_planes(ix) && ix->delta_n == 0 && ix->g_base == 0 &&
+         (ix->d.min_score > 0 || N <= nq::kHitListMaxTile) &&
+         (ix->n_tiles == 1 || N > nq::kHitListMaxTile) && nq::hit_list_lds(ix->tile, hit_list_cap(ix)) <= nq::kGatherMaxLds;
 }
 
 // Index::query_sketch (src/niqki_index.cpp:633-687) for nq device-resident whole sketches into device buffers: counters,
-// threshold, order.  c1 / c2: counter planes of nq rows (c2 only on a two-plane handle).  On a single-tile, single-
-// segment index with a small tile -- the short-read shape -- the hits leave the gather kernel as ordered lists and no
-// counter row is written or read again, except for a query with more than hit_list_cap hits.
+// threshold, order.  c1 / c2: counter planes of nq rows (c2 only on a two-plane handle).  On a single-segment, single-
+// plane index (hit_lists_apply) the hits leave the gather kernel as ordered lists and no counter row is written or read
+// again, except for a query with more than hit_list_cap hits.
 int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16_t *c1, uint16_t *c2, uint64_t stride,
                    unsigned long long *hit_off, uint32_t *hc, uint32_t *hg, uint64_t capacity, bool check_capacity,
                    uint64_t *total_out) {
@@ -279,13 +292,13 @@ int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16
     if ((rc = counts_dev(ix, sketches, ix->d.F, first_slot(ix), nq, c1, stride, c2))) return rc;
     return hits_dev(ix, c1, nq, stride, 0, N, hit_off, hc, hg, capacity, check_capacity, total_out, c2);
   }
-  const uint32_t cap = std::min<uint32_t>((std::max<uint32_t>(ix->hit_list_cap, 1) + 3u) & ~3u, nq::kHitListMaxCap);
+  const uint32_t cap = hit_list_cap(ix);
   const uint32_t k = ix->p.top_k < N ? ix->p.top_k : 0u;   // (top-k: a query's segment is the first min(n, k) of its list)
   const uint64_t room = k ? std::min<uint64_t>(capacity, (uint64_t)nq * k) : capacity;
-  if ((rc = ensure(ix, ix->ws_hl, (size_t)nq * cap * 4))) return rc;
+  if ((rc = ensure(ix, ix->ws_hl, (size_t)nq * cap * 8))) return rc;
   if ((rc = ensure(ix, ix->ws_blk, ((size_t)nq * 2 + 1) * 4))) return rc;   // the lists' sizes, then the overflowing queries
   nq::CandOut co;
-  co.hl = (uint32_t *)ix->ws_hl.p;
+  co.hl = (unsigned long long *)ix->ws_hl.p;
   co.hl_n = (uint32_t *)ix->ws_blk.p;
   co.hl_over = (uint32_t *)ix->ws_blk.p + nq;
   if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;   // (lists of > 2048 hits)
@@ -318,7 +331,7 @@ int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16
     if (total_out) *total_out = total;
     if (total > capacity) return NIQKI_E_CAPACITY;
   }
-  NQ_HIP(ix, nq::launch_hitlist_emit(a, (const uint32_t *)ix->ws_blk.p, (const uint32_t *)ix->ws_hl.p, cap, over, ix->stream));
+  NQ_HIP(ix, nq::launch_hitlist_emit(a, (const uint32_t *)ix->ws_blk.p, (const unsigned long long *)ix->ws_hl.p, cap, over, ix->stream));
   return NIQKI_OK;
 }
 
@@ -332,11 +345,11 @@ int query_to_host(niqki_index *ix, const int32_t *sketches, bool sk_dev, uint32_
   uint64_t base = 0;
   bool overflow = false;
   hit_off[0] = 0;
-  // queries per round of launches: option "query_batch" bounds the counter rows (2N bytes per query); an index that
-  // takes the hit-list form writes rows only for the rare overflowing query and is small (<= 12 288 genomes), so a
-  // whole staged batch of short reads goes through in one round (64 rounds of 1024 cost the lines-mode host path
-  // twice its kernels' time)
-  const uint32_t qb = hit_lists_apply(ix) ? std::max<uint32_t>(ix->query_batch, 65536u) : ix->query_batch;
+  // queries per round of launches: option "query_batch" bounds the counter rows (2N bytes per query); a small index
+  // (<= 12 288 genomes) that takes the hit-list form writes rows only for the rare overflowing query, so a whole staged
+  // batch of short reads goes through in one round (64 rounds of 1024 cost the lines-mode host path twice its kernels'
+  // time)
+  const uint32_t qb = hit_lists_apply(ix) && N <= nq::kHitListMaxTile ? std::max<uint32_t>(ix->query_batch, 65536u) : ix->query_batch;
   const size_t planes = two_planes(ix) ? 2 : 1;
   std::vector<unsigned long long> off(std::min(qb, nq) + 1);
   for (uint32_t q0 = 0; q0 < nq; q0 += qb) {

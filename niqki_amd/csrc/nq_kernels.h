@@ -159,22 +159,28 @@ struct CandOut {
   int2 *surv = nullptr;
   int32_t *surv_n = nullptr;
   uint32_t surv_thr = 0, surv_cap = 0;
-  // Hit lists (single-tile, single-segment indexes with small tiles: the short-read shape): the thresholded hits of
-  // a query -- Index::query_sketch's result, src/niqki_index.cpp:662-666,:685 -- leave the kernel while its
-  // counters are still in LDS, already ordered by descending (count, gid): hl[q*hl_cap + i] = count << 16 | gid
-  // (a count <= 2^15, a genome id < 2^16 on such an index: the packed words order like the pairs) and hl_n[q] = how
-  // many there are.  Only a query with more than hl_cap hits writes its 2N-byte counter row (to `counts`, which must
-  // be given) and leaves hl_n[q] > hl_cap: launch_hitlist_emit thresholds and orders that row.
+  // Hit lists (single-segment, single-plane indexes, any number of tiles): the thresholded hits of a query --
+  // Index::query_sketch's result, src/niqki_index.cpp:662-666,:685 -- are picked while each tile's counters are still
+  // in LDS and leave the kernel after the last tile, ordered by descending (count, gid): hl[q*hl_cap + i] =
+  // count << 32 | gid (the keys order like the pairs) and hl_n[q] = how many there are.  Only a query with more than
+  // hl_cap hits writes its 2N-byte counter row (to `counts`, which must be given) and leaves hl_n[q] > hl_cap:
+  // launch_hitlist_emit thresholds and orders that row.
   // Not together with cand / surv.  hl_cap: a multiple of 4.
-  uint32_t *hl = nullptr;
+  unsigned long long *hl = nullptr;
   uint32_t *hl_n = nullptr;
   uint32_t *hl_over = nullptr;   // nq + 1 words: [0] is zeroed by the launch (launch_hitlist_scan lists the overflowing queries there)
   uint32_t hl_cap = 0, hl_min = 0;
 };
-// the largest tile the hit-list form takes (the 256-thread launch shape: counters + queues + list within a CU's LDS
-// several times over)
+// the 256-thread launch shape's largest tile (counters + queues + list within a CU's LDS several times over): an index
+// of at most this many genomes takes the hit-list form as one tile
 constexpr uint32_t kHitListMaxTile = 12288;
 constexpr uint32_t kHitListMaxCap = 2048;
+// LDS of a gather launch with hit lists at its largest workgroup (1024 threads: the counters of a padded tile, 16 wave
+// queues of 256 8-byte items, the list of cap 8-byte keys); the form takes tiles where that fits a workgroup's 160 KB
+constexpr size_t hit_list_lds(uint32_t tile, uint32_t cap) {
+  return ((size_t)(tile + 1) / 2 + kPadWords) * 4 + (size_t)16 * 256 * 8 + (size_t)cap * 8;
+}
+constexpr size_t kGatherMaxLds = 163840;
 hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t nq,
                          uint16_t *counts, uint16_t *counts2, uint64_t stride, Entry *stash, const uint32_t *order,
                          int variant, bool pre, hipStream_t stream, const CandOut &co = CandOut());
@@ -235,7 +241,7 @@ hipError_t launch_hits_count(const HitsArgs &a, hipStream_t stream);
 // over: nq + 1 words of scratch (the queries whose lists overflowed, made by the scan, taken by the emit launch)
 hipError_t launch_hitlist_scan(const uint32_t *n, const HitsArgs &a, uint32_t hl_cap, uint32_t *over, hipStream_t stream);
 // n: the lists' sizes (hl_n of the gather launch); with a.top_k a query's segment holds the first min(n, k) entries
-hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over,
+hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const unsigned long long *hl, uint32_t hl_cap, const uint32_t *over,
                                hipStream_t stream);
 hipError_t launch_hits_emit(const HitsArgs &a, hipStream_t stream);
 

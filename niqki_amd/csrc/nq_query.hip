@@ -48,6 +48,7 @@ struct Item {
   uint32_t pos, len;
 };
 constexpr uint32_t kQueue = 256;  // items per wave-private LDS work queue
+static_assert(hit_list_lds(0, 0) == kPadWords * 4 + 16 * kQueue * sizeof(Item), "hit_list_lds (nq_kernels.h) counts these queues");
 
 // Walks 64 chunks held one per lane (pos, len <= 64): all lanes read consecutive
 // u16 ids of one chunk, UNROLL chunks per round trip, two rounds in flight (the
@@ -865,6 +866,7 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
     }
   }
   bool zeroed = false;   // the scan of the tile before left this tile's counters at zero
+  uint32_t hl_total = 0;  // hit lists: the query's hits in the tiles before this one (the same in every thread)
   for (uint32_t t = 0; t < v.n_tiles; ++t) {
     const uint32_t n_t = tile_count(v, t);
     const uint32_t n_words = (n_t + 1) / 2;
@@ -873,8 +875,8 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
       uint4 *c4 = (uint4 *)cnt;   // (the dynamic LDS block is 16-byte aligned)
       for (uint32_t i = tid; i < n_words / 4; i += BLOCK) c4[i] = make_uint4(0, 0, 0, 0);
       for (uint32_t i = (n_words & ~3u) + tid; i < n_words; i += BLOCK) cnt[i] = 0;
-      if (co.hl)
-        for (uint32_t i = tid; i < co.hl_cap; i += BLOCK) ((uint32_t *)(queue + (BLOCK / 64) * kQueue))[i] = 0u;
+      if (co.hl && t == 0)   // (the list gathers the hits of every tile)
+        for (uint32_t i = tid; i < co.hl_cap; i += BLOCK) ((unsigned long long *)(queue + (BLOCK / 64) * kQueue))[i] = 0ull;
       lds_barrier();
     }
     zeroed = false;
@@ -888,7 +890,7 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
       walk_tile<BLOCK, UNROLL, 1, false, false, false, PAD>(v, sk, q, t, cnt, queue, stash, it_lo, n_it);
     }
     if (want_cand && tid == 0) { lds_n[0] = n_surv; lds_n[1] = n_cand; }
-    if (co.hl && tid == 0) lds_n[0] = 0;
+    if (co.hl && tid == 0) lds_n[0] = hl_total;
     NQ_GCLK_WAVE(16 + 16 * (t & 1));
     NQ_GCLK(2 + 4 * (t & 1));
     lds_barrier();
@@ -930,13 +932,16 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
       continue;
     }
     if (co.hl) {
-      // Hit lists (launch_gather: one tile, one plane, nothing to add to): the query's hits are picked while its
-      // counters are in LDS -- count >= min_score, src/niqki_index.cpp:662-666 -- and ordered here, by rank: the keys
-      // count << 32 | gid are distinct, so an entry's place under greater<pair<count, gid>> (:685) is the number of
-      // entries with a larger key.  A short read against a genome index has a few dozen hits: no 2N-byte counter row
-      // is written for it, none read again.  A query with more than hl_cap hits (min_score 0: every genome) leaves
-      // through its counter row as before; launch_hitlist_emit orders it.
-      uint32_t *list = (uint32_t *)(queue + (BLOCK / 64) * kQueue);   // hl_cap packed entries: count << 16 | gid
+      // Hit lists (launch_gather: one plane, one segment, nothing to add to): the query's hits are picked while a tile's
+      // counters are in LDS -- count >= min_score, src/niqki_index.cpp:662-666 -- into one LDS list for all tiles, and
+      // ordered after the last tile, by rank: the keys count << 32 | gid are distinct, so an entry's place under
+      // greater<pair<count, gid>> (:685) is the number of entries with a larger key.  The key holds the global gid (the
+      // genomes of striped tiles interleave).  A query with a few dozen hits writes no 2N-byte counter row and reads
+      // none again.  A query with more than hl_cap hits (min_score 0: every genome) leaves through its counter row as
+      // before, and launch_hitlist_emit orders it.  Its total may pass hl_cap only at a later tile: that tile first
+      // writes the row's other tiles -- zeros, then the hits of the tiles before, which the list holds in full -- and it
+      // and every tile after it write their counters there as the counter-row form does (below).
+      unsigned long long *list = (unsigned long long *)(queue + (BLOCK / 64) * kQueue);   // hl_cap keys
       const uint32_t cap = co.hl_cap, ms = co.hl_min;
       // (hits are few: an LDS atomic each; ballot ranking was slower.  The counters are read eight at a time -- the
       // workgroup's clock showed 2.7 of a read's 14.6 us in this scan when it took them word by word -- and a quad
@@ -945,11 +950,11 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
         const uint32_t lo = c & 0xFFFFu, hi = c >> 16;
         if (lo >= ms) {
           const uint32_t at = atomicAdd(&lds_n[0], 1u);
-          if (at < cap) list[at] = (lo << 16) | (v.g_base + 2 * i);
+          if (at < cap) list[at] = (unsigned long long)lo << 32 | (v.g_base + tile_gid(v, t, 2 * i));
         }
         if (2 * i + 1 < n_t && hi >= ms) {
           const uint32_t at = atomicAdd(&lds_n[0], 1u);
-          if (at < cap) list[at] = (hi << 16) | (v.g_base + 2 * i + 1);
+          if (at < cap) list[at] = (unsigned long long)hi << 32 | (v.g_base + tile_gid(v, t, 2 * i + 1));
         }
       };
       const uint32_t n_quads = n_words / 4;
@@ -962,35 +967,45 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
       }
       for (uint32_t i = 4 * n_quads + tid; i < n_words; i += BLOCK) pick(cnt[i], i);
       lds_barrier();
-      NQ_GCLK(4);
-      const uint32_t total = lds_n[0];
-      if (total <= cap) {
-        // (entries are read four at a time; the list was zeroed with the counters, and key 0 -- the places behind
-        // the last entry -- is larger than no key: a real key 0 is count 0 of genome 0, the smallest there is)
-        const uint32_t t4 = (total + 3u) & ~3u;
-        uint32_t *out = co.hl + (uint64_t)q * cap;
-        for (uint32_t i = tid; i < total; i += BLOCK) {
-          const uint32_t key = list[i];
-          uint32_t rank = 0;
-          for (uint32_t j = 0; j < t4; j += 4) {   // (all lanes read the same four entries: a broadcast)
-            const uint4 o = *(const uint4 *)(list + j);
-            rank += (o.x > key) + (o.y > key) + (o.z > key) + (o.w > key);
-          }
-          out[rank] = key;
-        }
-      } else {
+      const uint32_t total = lds_n[0];   // (hl_total: the same in every thread)
+      if (total > cap && hl_total <= cap && t > 0) {
         uint16_t *row = plane + (uint64_t)q * stride + v.g_base;
         if (((uintptr_t)row & 3u) == 0) {
-          uint32_t *out = (uint32_t *)row;
-          for (uint32_t i = tid; i < n_t / 2; i += BLOCK) out[i] = cnt[i];
-          if ((n_t & 1u) && tid == 0) row[n_t - 1] = (uint16_t)(cnt[n_t / 2] & 0xFFFFu);
+          for (uint32_t i = tid; i < v.n_genomes / 2; i += BLOCK) ((uint32_t *)row)[i] = 0u;
+          if ((v.n_genomes & 1u) && tid == 0) row[v.n_genomes - 1] = 0;
         } else {
-          for (uint32_t i = tid; i < n_t; i += BLOCK) row[i] = (uint16_t)(cnt[i >> 1] >> ((i & 1u) * 16u));
+          for (uint32_t i = tid; i < v.n_genomes; i += BLOCK) row[i] = 0;
+        }
+        __syncthreads();   // (a barrier that waits for the zeros: the counts below are stored over them)
+        for (uint32_t i = tid; i < hl_total; i += BLOCK) {
+          const unsigned long long e = list[i];
+          row[(uint32_t)e - v.g_base] = (uint16_t)(e >> 32);
         }
       }
-      if (tid == 0) co.hl_n[q] = total;
-      NQ_GCLK(5);
-      continue;   // (one tile: nothing of this workgroup follows that touches LDS)
+      if (t + 1 == v.n_tiles) {
+        if (total <= cap) {
+          // (entries are read two at a time; the list was zeroed before the first tile, and key 0 -- the places
+          // behind the last entry -- is larger than no key: a real key 0 is count 0 of genome 0, the smallest there is)
+          const uint32_t t2 = (total + 1u) & ~1u;
+          unsigned long long *out = co.hl + (uint64_t)q * cap;
+          for (uint32_t i = tid; i < total; i += BLOCK) {
+            const unsigned long long key = list[i];
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < t2; j += 2) {   // (all lanes read the same two entries: a broadcast)
+              const ulonglong2 o = *(const ulonglong2 *)(list + j);
+              rank += (o.x > key) + (o.y > key);
+            }
+            out[rank] = key;
+          }
+        }
+        if (tid == 0) co.hl_n[q] = total;
+      }
+      hl_total = total;
+      if (total <= cap) {
+        lds_barrier();   // (everyone has read lds_n before the next walk takes its words back)
+        NQ_GCLK(4 + 4 * (t & 1));
+        continue;
+      }
     }
     uint16_t *row = plane + (uint64_t)q * stride + v.g_base;
     if (v.stripe > 1 && v.n_tiles > 1 && ((uintptr_t)row & 3u) == 0) {
@@ -1082,10 +1097,10 @@ hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t n
   if (co.cand && (v.accumulate || v.f_local > kPassSlots || !co.n)) return hipErrorInvalidValue;
   if (co.surv && (!co.cand || !co.surv_n || co.surv_thr > co.thr || !co.surv_cap)) return hipErrorInvalidValue;
   if (!counts && !co.surv) return hipErrorInvalidValue;
-  if (co.hl && (co.cand || !co.hl_n || !counts || !co.hl_cap || (co.hl_cap & 3u) || co.hl_cap > kHitListMaxCap || v.g_base + v.n_genomes > 65536u || v.n_tiles != 1 || v.accumulate ||
-                v.f_local > kPassSlots || v.tile > kHitListMaxTile))
+  if (co.hl && (co.cand || !co.hl_n || !counts || !co.hl_cap || (co.hl_cap & 3u) || co.hl_cap > kHitListMaxCap || v.accumulate ||
+                v.f_local > kPassSlots || hit_list_lds(v.tile, co.hl_cap) > kGatherMaxLds))
     return hipErrorInvalidValue;
-#define NQ_GATHER_LDS(B) ((size_t)((v.tile + 1) / 2 + (v.padded ? kPadWords : 0u)) * 4 + (size_t)(B / 64) * kQueue * sizeof(Item) + (size_t)co.hl_cap * (co.hl ? 4 : 0))
+#define NQ_GATHER_LDS(B) ((size_t)((v.tile + 1) / 2 + (v.padded ? kPadWords : 0u)) * 4 + (size_t)(B / 64) * kQueue * sizeof(Item) + (size_t)co.hl_cap * (co.hl ? 8 : 0))
   // with a locality order the grid is padded to whole groups on every XCD
   const uint32_t per_round = kXcds * kOrderGroup;
   dim3 grid(order ? (nq + per_round - 1) / per_round * per_round : nq);
@@ -1716,9 +1731,11 @@ __global__ __launch_bounds__(1024) void hitlist_scan_kernel(const uint32_t *n, u
 // threads of a workgroup, the first n_out unpacked to hc / hg.  Element i = r * 256 + tid lives in register k[r]:
 // a stage whose partner i ^ j lies in the same thread (j >= 256) or the same wave (j < 64) needs no LDS and no
 // barrier; only the strides 64 and 128 go through LDS (9 of the 66 stages of 2048 keys).
-template <int ITEMS>
-__device__ __forceinline__ void bitonic_desc_256(uint32_t *keys, uint32_t tid, uint32_t n_out, uint32_t *hc, uint32_t *hg) {
-  uint32_t k[ITEMS];
+// K = uint32_t: count << 16 | gid (gids < 2^16); K = unsigned long long: count << 32 | gid (any gid).
+template <typename K, int ITEMS>
+__device__ __forceinline__ void bitonic_desc_256(K *keys, uint32_t tid, uint32_t n_out, uint32_t *hc, uint32_t *hg) {
+  constexpr uint32_t GB = sizeof(K) * 4;   // bits of the gid
+  K k[ITEMS];
 #pragma unroll
   for (int r = 0; r < ITEMS; ++r) k[r] = keys[r * 256 + tid];
   constexpr uint32_t P = 256u * ITEMS;
@@ -1732,8 +1749,8 @@ __device__ __forceinline__ void bitonic_desc_256(uint32_t *keys, uint32_t tid, u
           const int r2 = r ^ (int)(j >> 8);
           if (r2 > r) {
             const bool desc = (((uint32_t)r * 256u) & kk) == 0;   // (kk > j >= 256: bit kk of i is a bit of r)
-            const uint32_t x = k[r], y = k[r2];
-            const uint32_t hi = x > y ? x : y, lo = x > y ? y : x;
+            const K x = k[r], y = k[r2];
+            const K hi = x > y ? x : y, lo = x > y ? y : x;
             k[r] = desc ? hi : lo;
             k[r2] = desc ? lo : hi;
           }
@@ -1750,9 +1767,9 @@ __device__ __forceinline__ void bitonic_desc_256(uint32_t *keys, uint32_t tid, u
         for (int r = 0; r < ITEMS; ++r) {
           const uint32_t i = (uint32_t)r * 256u + tid;
           const bool desc = (i & kk) == 0;
-          const uint32_t x = k[r];
-          const uint32_t y = j >= 64 ? keys[r * 256 + (tid ^ j)] : (uint32_t)__shfl_xor((int)x, (int)j, 64);
-          const uint32_t hi = x > y ? x : y, lo = x > y ? y : x;
+          const K x = k[r];
+          const K y = j >= 64 ? keys[r * 256 + (tid ^ j)] : (K)__shfl_xor(x, (int)j, 64);
+          const K hi = x > y ? x : y, lo = x > y ? y : x;
           k[r] = (desc == lower) ? hi : lo;
         }
       }
@@ -1761,19 +1778,138 @@ __device__ __forceinline__ void bitonic_desc_256(uint32_t *keys, uint32_t tid, u
 #pragma unroll
   for (int r = 0; r < ITEMS; ++r) {
     const uint32_t i = (uint32_t)r * 256u + tid;
-    if (i < n_out) { hc[i] = k[r] >> 16; hg[i] = k[r] & 0xFFFFu; }
+    if (i < n_out) { hc[i] = (uint32_t)(k[r] >> GB); hg[i] = (uint32_t)(k[r] & ((K(1) << GB) - 1u)); }
   }
 }
 
-// hitlist_emit_kernel, two parts.  First, one wave per query (4 per workgroup): a query whose list fits -- the usual
+// The hits of a counter row of the hit-list form's emit launch (count >= min_score, src/niqki_index.cpp:662-666) as
+// keys count << G | gid -- distinct keys whose descending order is greater<pair<count, gid>> (:685) -- in LDS, ordered
+// there by a bitonic network of Pq keys (>= the row's hits) and the first n_out unpacked to [seg0, seg0 + n_out).
+template <typename K>
+__device__ void network_sort(const uint16_t *row, const HitsArgs &a, K *keys, uint32_t &s_n, uint32_t Pq, uint32_t n_out,
+                             unsigned long long seg0, uint32_t tid) {
+  constexpr uint32_t GB = sizeof(K) * 4;
+  if (tid == 0) s_n = 0;
+  for (uint32_t i = tid; i < Pq; i += 256) keys[i] = 0;
+  __syncthreads();
+  // 8 counters per lane and load (rows start on 128-byte lines: NIQKI_ROW_STRIDE)
+  const bool vec = (((uintptr_t)row) & 15u) == 0;
+  for (uint32_t i0 = tid * 8; i0 < a.n_gids; i0 += 256 * 8) {
+    uint32_t c[8];
+    if (vec && i0 + 8 <= a.n_gids) {
+      const uint4 w = *(const uint4 *)(row + i0);
+      c[0] = w.x & 0xFFFFu; c[1] = w.x >> 16; c[2] = w.y & 0xFFFFu; c[3] = w.y >> 16;
+      c[4] = w.z & 0xFFFFu; c[5] = w.z >> 16; c[6] = w.w & 0xFFFFu; c[7] = w.w >> 16;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) c[j] = i0 + j < a.n_gids ? (uint32_t)row[i0 + j] : 0u;
+    }
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m |= (uint32_t)(i0 + j < a.n_gids && c[j] >= a.min_score) << j;
+    if (m) {
+      uint32_t at = atomicAdd(&s_n, (uint32_t)__builtin_popcount(m));
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (m >> j & 1u) keys[at++] = ((K)c[j] << GB) | (K)(a.gid_begin + i0 + j);
+    }
+  }
+  __syncthreads();
+  // bitonic sort, descending (the zero keys behind the real ones end up last: a real key 0 -- count 0 of genome 0 at
+  // min_score 0 -- is the smallest key and belongs there too), in registers: see bitonic_desc_256
+  if (Pq <= 256) bitonic_desc_256<K, 1>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
+  else if (Pq == 512) bitonic_desc_256<K, 2>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
+  else if (Pq == 1024) bitonic_desc_256<K, 4>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
+  else bitonic_desc_256<K, 8>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
+  __syncthreads();
+}
+
+// A counter row thresholded into [seg0, ..) in descending gid by a 256-thread workgroup: c > T, and of the genomes with
+// c == T the first r met from the top gid down (r = kSkipAllTies: all).  2048 counters per step: thread t takes the 8
+// counters [top - 8 (t + 1), top - 8 t) -- thread 0 the largest gids -- and an exclusive scan of ties << 16 | hits over
+// the threads places them; the next step's 16 bytes are loaded before this step's scan.  wtot: 4 words of LDS.
+__device__ void compact_desc(const uint16_t *row, uint32_t n_gids, uint32_t T, uint32_t r, unsigned long long seg0,
+                             const HitsArgs &a, uint32_t *wtot, uint32_t tid) {
+  const uint32_t lane = tid & 63u, wave = tid >> 6;
+  const bool vec = (((uintptr_t)row) & 15u) == 0;
+  auto load = [&](long long lo) {   // counters [lo, lo + 8) as packed pairs, 0 outside the row
+    if (vec && lo >= 0 && lo + 8 <= (long long)n_gids) return *(const uint4 *)(row + lo);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long long i = lo + j;
+      if (i >= 0 && i < (long long)n_gids) w[j >> 1] |= (uint32_t)row[i] << ((j & 1) * 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  };
+  const long long top0 = ((long long)n_gids + 7) & ~7ll;
+  unsigned long long run = 0;   // entries written
+  uint32_t ties_run = 0;        // genomes of count T met
+  uint4 next = load(top0 - 8ll * (tid + 1));
+  for (long long top = top0; top > 0; top -= 2048) {
+    const long long lo = top - 8ll * (tid + 1);
+    const uint4 w = next;
+    if (top > 2048) next = load(top - 2048 - 8ll * (tid + 1));
+    const uint32_t cw[4] = {w.x, w.y, w.z, w.w};
+    uint32_t nh = 0, nt = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long long i = lo + j;
+      const uint32_t c = (cw[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
+      const bool in = i >= 0 && i < (long long)n_gids;
+      nh += (uint32_t)(in && c > T);
+      nt += (uint32_t)(in && c == T);
+    }
+    const uint32_t x = nt << 16 | nh;   // (<= 2048 of each per step)
+    uint32_t incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(incl, o, 64);
+      if (lane >= (uint32_t)o) incl += y;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t before = incl - x, total = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < 4; ++v) {
+      const uint32_t t = wtot[v];
+      if (v < wave) before += t;
+      total += t;
+    }
+    __syncthreads();   // (wtot is written again by the next step)
+    // ties before this thread's: G; the kept ones among them and among those of earlier steps
+    uint32_t G = ties_run + (before >> 16);
+    const uint32_t kept_run = ties_run < r ? ties_run : r;
+    unsigned long long pos = seg0 + run + (before & 0xFFFFu) + ((G < r ? G : r) - kept_run);
+#pragma unroll
+    for (int j = 7; j >= 0; --j) {
+      const long long i = lo + j;
+      const uint32_t c = (cw[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
+      if (i < 0 || i >= (long long)n_gids || c < T) continue;
+      bool keep = c > T;
+      if (c == T) keep = G++ < r;
+      if (keep) {
+        if (pos < a.capacity) { a.hit_counts[pos] = c; a.hit_gids[pos] = a.gid_begin + (uint32_t)i; }
+        ++pos;
+      }
+    }
+    const uint32_t tt = ties_run + (total >> 16);
+    run += (total & 0xFFFFu) + ((tt < r ? tt : r) - kept_run);
+    ties_run = tt;
+  }
+}
+
+// hitlist_emit_kernel, two parts.  First, one wave per query (4 per workgroup, the first nq / 4 workgroups): a query whose list fits -- the usual
 // case -- is a copy of its ordered entries to [hit_off[q], hit_off[q+1]).  Then the queries whose lists overflowed, one
-// workgroup each (grid-stride over the list the scan made): the hits are thresholded from the query's counter row
-// (src/niqki_index.cpp:662-666) into LDS as count << 16 | gid -- distinct keys whose descending order is
-// greater<pair<count, gid>> (:685) -- and ordered there by a bitonic network.  keys: P words of LDS (P >= 256).
-__global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uint32_t *hn, const uint32_t *hl, uint32_t hl_cap,
+// workgroup each (grid-stride over the list the scan made): up to P hits are thresholded from the query's counter row
+// into LDS keys and ordered there by a bitonic network (network_sort); more are thresholded into the segment in
+// descending gid by the workgroup and ordered by a wave's radix passes (compact_desc).  keys: P words of LDS (P >= 256),
+// 2 P beyond 16-bit gids.
+__global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uint32_t *hn, const unsigned long long *hl, uint32_t hl_cap,
                                                             const uint32_t *over, uint32_t P) {
   extern __shared__ __align__(16) uint32_t keys[];   // (top-k: at least kSelBins words, the select's histogram)
   __shared__ uint32_t s_n;
+  __shared__ uint32_t s_wtot[4];
   __shared__ SelShared sh;
   const uint32_t tid = threadIdx.x;
   {
@@ -1782,13 +1918,13 @@ __global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uin
       // the segment: the list, or with top-k its first k entries
       const unsigned long long seg0 = a.hit_off[q], n_all = a.hit_off[q + 1] - seg0;
       if (n_all && hn[q] <= hl_cap) {
-        const uint32_t *src = hl + (uint64_t)q * hl_cap;
+        const unsigned long long *src = hl + (uint64_t)q * hl_cap;
         for (uint32_t i = lane; i < (uint32_t)n_all; i += 64) {
           const unsigned long long pos = seg0 + i;
           if (pos < a.capacity) {
-            const uint32_t e = src[i];
-            a.hit_counts[pos] = e >> 16;
-            a.hit_gids[pos] = e & 0xFFFFu;
+            const unsigned long long e = src[i];
+            a.hit_counts[pos] = (uint32_t)(e >> 32);
+            a.hit_gids[pos] = (uint32_t)e;
           }
         }
       }
@@ -1801,84 +1937,37 @@ __global__ __launch_bounds__(256) void hitlist_emit_kernel(HitsArgs a, const uin
     const unsigned long long seg0 = a.hit_off[q], n_all = a.hit_off[q + 1] - seg0, n_hit = hn[q];
     const uint16_t *row = a.counts + (uint64_t)q * a.stride + a.gid_begin;
     if (n_hit > P) {
-      // more hits than the network holds (a threshold that lets a sixth of the index through): one wave thresholds the
-      // row in descending gid and orders it with the stable radix passes of hits_sort_kernel, through tmp_*.  With
-      // top-k the wave keeps c > T and the first r genomes of count T it meets (the largest gids): the select's boundary
+      // more hits than the network holds (a threshold that lets a sixth of the index through): the workgroup thresholds
+      // the row in descending gid into the segment and one wave orders it with the stable radix passes of
+      // hits_sort_kernel, through tmp_*.  With top-k the row keeps c > T and the first r genomes of count T in
+      // descending gid (the largest gids): the select's boundary
       uint32_t T = a.min_score, r = kSkipAllTies;
       if (a.top_k && n_hit > a.top_k) sel_boundary<false>(row, nullptr, a.n_gids, a.min_score, a.top_k, keys, sh, nullptr, nullptr, nullptr, T, r);
+      compact_desc(row, a.n_gids, T, r, seg0, a, s_wtot, tid);
+      __syncthreads();   // (the segment is written: global stores of the workgroup before the wave's loads)
       if (tid < 64) {
-        uint32_t *cur = keys;   // 256 words
-        const uint32_t lane = tid;
-        const uint64_t lt_mask = (1ULL << lane) - 1ULL;
-        unsigned long long run = 0;
-        uint32_t ties = 0;   // genomes of count T met so far
-        for (uint32_t top = (a.n_gids + 63u) & ~63u; top > 0; top -= 64) {
-          const uint32_t i = top - 1 - lane;
-          const uint32_t c = i < a.n_gids ? (uint32_t)row[i] : 0u;
-          const bool tie = i < a.n_gids && c == T;
-          const uint64_t tb = __ballot(tie);
-          const bool hit = i < a.n_gids && (c > T || (tie && ties + __popcll(tb & lt_mask) < r));
-          ties += __popcll(tb);
-          const uint64_t bal = __ballot(hit);
-          if (hit) {
-            const unsigned long long pos = seg0 + run + __popcll(bal & lt_mask);
-            if (pos < a.capacity) { a.hit_counts[pos] = c; a.hit_gids[pos] = a.gid_begin + i; }
-          }
-          run += __popcll(bal);
-        }
         unsigned long long seg1 = seg0 + n_all;
         if (seg1 > a.capacity) seg1 = a.capacity;
         if (seg0 < seg1) {
           const unsigned long long n = seg1 - seg0;
           uint32_t *tc = a.tmp_counts + seg0, *tg = a.tmp_gids + seg0;
           uint32_t *hc = a.hit_counts + seg0, *hg = a.hit_gids + seg0;
+          radix_pass_desc(hc, hg, tc, tg, n, 0, keys, tid);
           __threadfence_block();
-          radix_pass_desc(hc, hg, tc, tg, n, 0, cur, lane);
-          __threadfence_block();
-          radix_pass_desc(tc, tg, hc, hg, n, 8, cur, lane);
+          radix_pass_desc(tc, tg, hc, hg, n, 8, keys, tid);
         }
       }
       __syncthreads();
       continue;
     }
-    if (tid == 0) s_n = 0;
     // the network's size for this query
     uint32_t Pq = 256;
     while (Pq < n_hit) Pq <<= 1;   // (n_hit <= P here, and P >= 256 is a power of two)
-    for (uint32_t i = tid; i < Pq; i += 256) keys[i] = 0u;
-    __syncthreads();
-    // 8 counters per lane and load (rows start on 128-byte lines: NIQKI_ROW_STRIDE)
-    const bool vec = (((uintptr_t)row) & 15u) == 0;
-    for (uint32_t i0 = tid * 8; i0 < a.n_gids; i0 += 256 * 8) {
-      uint32_t c[8];
-      if (vec && i0 + 8 <= a.n_gids) {
-        const uint4 w = *(const uint4 *)(row + i0);
-        c[0] = w.x & 0xFFFFu; c[1] = w.x >> 16; c[2] = w.y & 0xFFFFu; c[3] = w.y >> 16;
-        c[4] = w.z & 0xFFFFu; c[5] = w.z >> 16; c[6] = w.w & 0xFFFFu; c[7] = w.w >> 16;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) c[j] = i0 + j < a.n_gids ? (uint32_t)row[i0 + j] : 0u;
-      }
-      uint32_t m = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m |= (uint32_t)(i0 + j < a.n_gids && c[j] >= a.min_score) << j;
-      if (m) {
-        uint32_t at = atomicAdd(&s_n, (uint32_t)__builtin_popcount(m));
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (m >> j & 1u) keys[at++] = (c[j] << 16) | (a.gid_begin + i0 + j);
-      }
-    }
-    __syncthreads();
-    // bitonic sort, descending (the zero keys behind the n_all real ones end up last: a real key 0 -- count 0 of
-    // genome 0 at min_score 0 -- is the smallest key and belongs there too), in registers: see bitonic_desc_256
     const unsigned long long room = seg0 < a.capacity ? a.capacity - seg0 : 0ull;
     const uint32_t n_out = (uint32_t)(n_all < room ? n_all : room);
-    if (Pq <= 256) bitonic_desc_256<1>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
-    else if (Pq == 512) bitonic_desc_256<2>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
-    else if (Pq == 1024) bitonic_desc_256<4>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
-    else bitonic_desc_256<8>(keys, tid, n_out, a.hit_counts + seg0, a.hit_gids + seg0);
-    __syncthreads();
+    // (gids of 16 bits: 4-byte keys; a larger index: 8-byte keys, the LDS block holds 2 P words then)
+    if (a.gid_begin + a.n_gids <= 65536u) network_sort<uint32_t>(row, a, keys, s_n, Pq, n_out, seg0, tid);
+    else network_sort<unsigned long long>(row, a, (unsigned long long *)keys, s_n, Pq, n_out, seg0, tid);
   }
 }
 
@@ -1889,14 +1978,17 @@ hipError_t launch_hitlist_scan(const uint32_t *n, const HitsArgs &a, uint32_t hl
   return hipGetLastError();
 }
 
-hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const uint32_t *hl, uint32_t hl_cap, const uint32_t *over,
+hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const unsigned long long *hl, uint32_t hl_cap, const uint32_t *over,
                                hipStream_t stream) {
   if (a.nq == 0) return hipSuccess;
-  // (the network: 2048 keys = 8 KB of LDS, eight workgroups per CU; a query with more hits takes the wave path)
+  // (the network: 2048 keys = 8 or 16 KB of LDS, several workgroups per CU; a query with more hits takes compact_desc)
   uint32_t P = 256;
   while (P < a.n_gids && P < 2048u) P <<= 1;
-  const uint32_t lds = a.top_k && P < kSelBins ? kSelBins : P;
-  hipLaunchKernelGGL(hitlist_emit_kernel, dim3((a.nq + 3) / 4), dim3(256), (size_t)lds * 4, stream, a, n, hl, hl_cap, over, P);
+  const uint32_t words = a.gid_begin + a.n_gids > 65536u ? 2 * P : P;   // (8-byte keys beyond 16-bit gids)
+  const uint32_t lds = a.top_k && words < kSelBins ? kSelBins : words;
+  // (nq workgroups: the first nq / 4 copy the lists; every overflowing query then has a workgroup of its own -- a wave's
+  // radix passes over a long segment are the slow part, and the counter-row path runs one wave per query at once too)
+  hipLaunchKernelGGL(hitlist_emit_kernel, dim3(a.nq), dim3(256), (size_t)lds * 4, stream, a, n, hl, hl_cap, over, P);
   return hipGetLastError();
 }
 
