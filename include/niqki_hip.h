@@ -426,6 +426,38 @@ void niqki_host_free(void *p);
 int niqki_matrix_range(niqki_index *ix, uint32_t begin, uint32_t end,
                        uint16_t *counts, uint64_t stride, int mem);
 
+/* ---- self-join: the index asked about itself ------------------------------------------------
+ * Whole-range single-GPU handles only (resident or paged, any tile count, hit lists or counter rows, S <= 16, with or
+ * without a delta segment).  A slot-range shard (niqki_params.slot_begin / slot_end) sees partial counts: both calls
+ * return NIQKI_E_STATE on it.  Groups have no self-join (out of scope: build a single-GPU index for it).
+ *
+ * Sparse form of Index::query_range (src/niqki_index.cpp:570-610): the hits of the STORED sketches of genomes
+ * [begin, end).  Defined as: exactly what niqki_query returns for the output of
+ * niqki_get_sketches(ix, begin, end - begin, ...) -- same threshold (the handle's min_score), same order and tie
+ * rule, top_k honoured, the genome itself included where its own count passes the threshold -- without the
+ * sketches leaving the device.  Capacity protocol and mem as niqki_query (NIQKI_MEM_DEVICE: one launch round for the
+ * whole range, no capacity check; NIQKI_MEM_HOST: batches of option "query_batch", NIQKI_E_CAPACITY with the true
+ * total in hit_off[end - begin]).  begin > end or end > genome count: NIQKI_E_INVALID. */
+int niqki_neighbors_range(niqki_index *ix, uint32_t begin, uint32_t end, uint64_t *hit_off,
+                          uint32_t *hit_counts, uint32_t *hit_gids, uint64_t capacity, int mem);
+
+/* Single-linkage clusters of the indexed genomes: a and b are linked when their co-occurrence count (the cell
+ * niqki_matrix_range gives, before any u16 wrap) is >= threshold; a cluster is a connected component of that
+ * graph.  labels[g] = the SMALLEST genome id of g's cluster, for every g in [0, n_genomes).  *n_clusters (may be
+ * NULL, host memory whatever mem is) = number of g with labels[g] == g.  The result is a function of the index and the
+ * threshold only: it does not depend on batch sizes, options, top_k (ignored here) or the order in which the device
+ * links pairs.  threshold 0 links everything: all labels 0, nothing is launched.  The handle's min_score and top_k are
+ * unchanged when the call returns, also when it fails.
+ * The pair list never leaves the device: per batch of option "query_batch" stored sketches the hits at the threshold
+ * stay in device buffers of a fixed budget (option "cluster_ws_mib", default 1024; a batch whose hits exceed it is
+ * split in halves, down to one query, whose hits always fit; stat "cluster_splits" counts the splits of the last
+ * call) and a link kernel unites the components on a device-resident parent array.
+ * While profiling is on (niqki_profile_enable, niqki_hip_bench.h) the call also times its phases with events, one
+ * synchronisation per batch; niqki_get_stat then gives, for the last call: "cluster_us_read" (stored sketches back
+ * into query form), "cluster_us_hits" (gather + threshold + order), "cluster_us_link", "cluster_us_flatten"
+ * (microseconds) and "cluster_pairs" (hits the link kernel went through; tools/bench_selfjoin.py). */
+int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *n_clusters, int mem);
+
 /* dump_index_disk payload (src/niqki_index.cpp:42-55), before gzip and
  * without the trailing names: 6 x u32 header {lF,K,H,W,min_score,N} then per
  * bucket u32 size + size x u32 gid, buckets in fp + slot*2^W order, gids

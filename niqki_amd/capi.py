@@ -115,6 +115,8 @@ ABI = [
     ("niqki_host_alloc", _vp, [C.c_size_t]),
     ("niqki_host_free", None, [_vp]),
     ("niqki_matrix_range", _int, [_vp, _u32, _u32, _vp, _u64, _int]),
+    ("niqki_neighbors_range", _int, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_cluster", _int, [_vp, _u32, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
     ("niqki_export_dump_header", _int, [_vp, _vp]),
@@ -524,6 +526,22 @@ class Engine:
         out = np.zeros((end - begin, stride), dtype=np.uint16)
         self._ck(self.L.niqki_matrix_range(self.h, begin, end, _p(out), stride, MEM_HOST))
         return out[:, :n]
+
+    def neighbors_range(self, begin, end, capacity=None):
+        """The hits of the STORED sketches of genomes [begin, end): what query(get_sketches(begin, end - begin))
+        returns, without the sketches leaving the device.  Same return shape as query."""
+        nq = max(end - begin, 0)
+        cap = capacity if capacity is not None else max(1024, nq * 64)
+        return self._hits(lambda off, hc, hg, c: self.L.niqki_neighbors_range(
+            self.h, begin, end, _p(off), _p(hc), _p(hg), c, MEM_HOST), nq, cap)
+
+    def cluster(self, threshold):
+        """Single-linkage clusters at co-occurrence count >= threshold: (labels, n_clusters), labels[g] = the
+        smallest genome id of g's cluster."""
+        labels = np.empty(self.n_genomes, dtype=np.uint32)
+        n = _u32(0)
+        self._ck(self.L.niqki_cluster(self.h, int(threshold), _p(labels), C.byref(n), MEM_HOST))
+        return labels, int(n.value)
 
     def get_sketches(self, begin, n):
         out = np.empty((n, self.F), dtype=np.int32)

@@ -379,7 +379,7 @@ void niqki_destroy(niqki_index *ix) {
   for (Buf *b : {&ix->ws_seq, &ix->ws_recoff, &ix->ws_entry, &ix->ws_sk, &ix->ws_counts, &ix->ws_blk,
                  &ix->ws_hitoff, &ix->ws_hc, &ix->ws_hg, &ix->ws_tc, &ix->ws_tg, &ix->ws_misc, &ix->ws_stash,
                  &ix->ws_raw, &ix->ws_wire[0], &ix->ws_wire[1], &ix->ws_redo[0], &ix->ws_redo[1], &ix->ws_fmeta, &ix->ws_summ, &ix->ws_chunk, &ix->ws_fkept, &ix->ws_fnrec,
-                 &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab})
+                 &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -468,6 +468,11 @@ int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
     ix->hit_list_cap = (uint32_t)value;
     return NIQKI_OK;
   }
+  if (!std::strcmp(key, "cluster_ws_mib")) {
+    if (value < 1 || value > (1 << 20)) return fail(ix, NIQKI_E_INVALID, "cluster_ws_mib must be in 1..1048576");
+    ix->cluster_ws_mib = (uint32_t)value;
+    return NIQKI_OK;
+  }
   if (!std::strcmp(key, "query_batch")) { if (value < 1) return NIQKI_E_INVALID; ix->query_batch = (uint32_t)value; return NIQKI_OK; }
   if (!std::strcmp(key, "tile_genomes")) {
     if (value < 0 || value > 65536 || (value & 63)) return fail(ix, NIQKI_E_INVALID, "tile_genomes must be a multiple of 64, <= 65536");
@@ -553,6 +558,13 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "class_mask")) { *value = (ix->built && ix->hmask_ok) ? 1 : 0; return NIQKI_OK; }
   if (!std::strcmp(key, "last_gather_form")) { *value = ix->last_form; return NIQKI_OK; }
   if (!std::strcmp(key, "last_hits_form")) { *value = ix->last_hits_form; return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_splits")) { *value = ix->cluster_splits; return NIQKI_OK; }
+  // the last niqki_cluster call while profiling was on (niqki_profile_enable): microseconds per phase, hits linked
+  if (!std::strcmp(key, "cluster_us_read")) { *value = (uint64_t)(ix->cluster_ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_hits")) { *value = (uint64_t)(ix->cluster_ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_link")) { *value = (uint64_t)(ix->cluster_ms[2] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_flatten")) { *value = (uint64_t)(ix->cluster_ms[3] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_pairs")) { *value = ix->cluster_pairs; return NIQKI_OK; }
   if (!std::strcmp(key, "inflate_files_in_flight") || !std::strcmp(key, "inflate_files_in_flight_8k")) {
     // how many files a launch of the device inflate runs at once (workgroups the device keeps resident), by kernel form
     (void)hipSetDevice(ix->device);

@@ -104,9 +104,13 @@ struct niqki_index {
   int hit_lists = 1;             // option: queries of a single small tile leave the gather kernel as ordered hit lists (no counter rows)
   uint32_t hit_list_cap = 256;   // option: hits per query such a list holds; a query with more goes through its counter row
   uint32_t last_hits_form = 0;   // stat "last_hits_form": 1 = the last query call took the hit-list form
+  uint32_t cluster_ws_mib = 1024;   // option "cluster_ws_mib": device hit buffers of a niqki_cluster batch (nq_cluster.hip)
+  uint64_t cluster_splits = 0;      // stat "cluster_splits": batches the last niqki_cluster call had to halve
+  double cluster_ms[4] = {0, 0, 0, 0};   // the last niqki_cluster call, while profiling is on: store read, gather + hits, link, flatten
+  uint64_t cluster_pairs = 0;       // ... and the hits its link kernel went through
 
   nqi::Buf ws_seq, ws_recoff, ws_entry, ws_sk, ws_counts, ws_blk, ws_hitoff, ws_hc, ws_hg, ws_tc, ws_tg,
-      ws_misc, ws_stash, ws_hl;
+      ws_misc, ws_stash, ws_hl, ws_parent;
   // staged batch (niqki_stage_raw): framing results live in ws_seq / ws_recoff / ws_entry
   nqi::Buf ws_raw, ws_fmeta, ws_summ, ws_chunk, ws_fkept, ws_fnrec, ws_hdrpos, ws_ehdr, ws_stsk, ws_order, ws_pre, ws_useg, ws_ijob, ws_xtab;
   uint64_t inflate_stats[4] = {0, 0, 0, 0};   // niqki_gunzip_stats
@@ -190,6 +194,8 @@ int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16
                    uint64_t *total_out);
 int query_to_host(niqki_index *ix, const int32_t *sketches, bool sk_dev, uint32_t nq, uint64_t *hit_off, uint32_t *hit_counts,
                   uint32_t *hit_gids, uint64_t capacity);
+// the handle counts whole sketches (no slot-range shard): what the self-join calls need (nq_cluster.hip)
+bool whole_range(const niqki_index *ix);
 // hit counters of nq device-resident sketches (rows q_stride apart, this shard's slots at q_off)
 // counts2: the second counter plane of a whole-range S = 16 handle (nq_kernels.h, kPassSlots), else nullptr
 // co: also the candidate lists of the rows (nq_kernels.h CandOut; presets them itself), not on paged or S = 16 handles

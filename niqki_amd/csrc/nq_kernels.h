@@ -245,6 +245,16 @@ hipError_t launch_hitlist_emit(const HitsArgs &a, const uint32_t *n, const unsig
                                hipStream_t stream);
 hipError_t launch_hits_emit(const HitsArgs &a, hipStream_t stream);
 
+// ---- single-linkage clusters (nq_cluster.hip) ------------------------------------
+// parent[g] = g for g < n
+hipError_t launch_cluster_init(uint32_t *parent, uint32_t n, hipStream_t stream);
+// Unites, for every query t < nq and every hit g = hit_gids[i], hit_off[t] <= i < hit_off[t + 1], with g < t0 + t, the
+// components of t0 + t and g on parent[]: the larger root goes under the smaller one.  One wavefront per query.
+hipError_t launch_cluster_link(uint32_t *parent, uint32_t n, const unsigned long long *hit_off, const uint32_t *hit_gids,
+                               uint32_t t0, uint32_t nq, hipStream_t stream);
+// labels[g] = root of g; *n_roots (zeroed here) = number of roots.  labels may not alias parent.
+hipError_t launch_cluster_flatten(const uint32_t *parent, uint32_t n, uint32_t *labels, uint32_t *n_roots, hipStream_t stream);
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

@@ -970,6 +970,69 @@ void Index::query_matrix() {
   }
 }
 
+// ---- self-join --------------------------------------------------------------------
+
+namespace {
+using neighbors_fn = int (*)(niqki_index *, uint32_t, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint64_t, int);
+using cluster_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, int);
+neighbors_fn engine_neighbors() { return (neighbors_fn)dlsym(RTLD_DEFAULT, "niqki_neighbors_range"); }
+cluster_fn engine_cluster() { return (cluster_fn)dlsym(RTLD_DEFAULT, "niqki_cluster"); }
+}  // namespace
+
+bool Index::has_self_join() { return engine_neighbors() != nullptr && engine_cluster() != nullptr; }
+
+void Index::query_neighbors() {
+  const neighbors_fn call = engine_neighbors();
+  if (!call || grp_) throw std::runtime_error("this engine has no self-join");
+  const uint32_t N = (uint32_t)filenames.size(), rows = 1024;
+  Hits h;
+  for (uint32_t t0 = 0; t0 < N; t0 += rows) {
+    const uint32_t t1 = std::min(N, t0 + rows), n = t1 - t0;
+    h.names.assign(filenames.begin() + t0, filenames.begin() + t1);
+    // (capacity as query_staged: top-k never exceeds n x k)
+    uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1)
+                         : std::max<uint64_t>(uint64_t(1) << 20, (uint64_t)n * 64);
+    h.off.resize(n + 1);
+    for (;;) {
+      h.hc.resize(cap);
+      h.hg.resize(cap);
+      const int rc = call(h_, t0, t1, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST);
+      if (rc == NIQKI_E_CAPACITY && cap < (uint64_t)n * N) { cap = std::max(h.off[n], cap * 2); continue; }
+      check(rc, "niqki_neighbors_range");
+      break;
+    }
+    write_hits(h);
+  }
+}
+
+void Index::cluster_to_file(const std::string &filestr) {
+  const cluster_fn call = engine_cluster();
+  if (!call || grp_) throw std::runtime_error("this engine has no self-join");
+  const uint32_t N = (uint32_t)filenames.size();
+  niqki_params p{};
+  check(niqki_get_params(h_, &p), "niqki_get_params");
+  std::vector<uint32_t> labels(N), start(N + 1, 0), order(N);
+  uint32_t n_clusters = 0;
+  check(call(h_, p.min_score, labels.data(), &n_clusters, NIQKI_MEM_HOST), "niqki_cluster");
+  // members by representative (a label is its cluster's smallest id, so label order is index order), in index order
+  for (uint32_t g = 0; g < N; ++g) start[labels[g] + 1] += 1;
+  for (uint32_t g = 0; g < N; ++g) start[g + 1] += start[g];
+  std::vector<uint32_t> at(start.begin(), start.end() - 1);
+  for (uint32_t g = 0; g < N; ++g) order[at[labels[g]]++] = g;
+  ParallelTextWriter out(filestr, host_threads());
+  std::string text;
+  for (uint32_t i = 0; i < N; ++i) {
+    const uint32_t g = order[i];
+    text += filenames[labels[g]];
+    text += '\t';
+    text += filenames[g];
+    text += '\n';
+    if (text.size() >= (size_t(4) << 20)) { out.write(text); text.clear(); }
+  }
+  out.write(text);
+  out.close();
+}
+
 // ---- dump ------------------------------------------------------------------------
 
 void Index::dump_index_disk(const std::string &filestr) {

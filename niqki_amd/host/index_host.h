@@ -57,6 +57,15 @@ class Index {
   void query_matrix();                                          // :614-628
   void dump_index_disk(const std::string &filestr);            // :42-59
 
+  // The self-join (long options --neighbors / --cluster; single-GPU index).  The two engine calls are looked up at run
+  // time, so that the program still links against an engine that answers the C ABI without them.
+  static bool has_self_join();
+  // the indexed genomes as queries, in index order, written like a -Q batch (niqki_neighbors_range)
+  void query_neighbors();
+  // single-linkage clusters at min_score (niqki_cluster) as lines representative<TAB>member: clusters in the order of
+  // their representative's index position, members in index order; a gzip file like every output of the program
+  void cluster_to_file(const std::string &filestr);
+
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
 

@@ -6,6 +6,8 @@
 //   --gpus <n>     cut the index by sketch-slot range over n GPUs (devices --device .. +n-1)
 //   --resident-mib <n>  paged index: sketch store in host memory, n MiB of device memory for one page of slots
 //   --top <n>      report at most n best hits per query (-Q / -q; niqki_params.top_k), 0 = all
+//   --neighbors    the indexed genomes themselves as queries, in index order, written like -Q (niqki_neighbors_range)
+//   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
 #include <libgen.h>
 #include <limits.h>
 #include <unistd.h>
@@ -32,7 +34,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -62,6 +64,8 @@ const Desc kDesc[] = {
     {GPUS, "", "gpus", NUMERIC, "  --gpus <int>                  Number of GPUs the index is sharded over (1)."},
     {RESIDENT, "", "resident-mib", NUMERIC, "  --resident-mib <int>          Device memory budget of a paged index in MiB (0: everything resident)."},
     {TOP, "", "top", NUMERIC, "  --top <int>                   Report at most <int> best hits per query (0: all)."},
+    {NEIGHBORS, "", "neighbors", NONE, "  --neighbors                   Query the index with its own genomes, in index order (output as -Q)."},
+    {CLUSTER, "", "cluster", NONEMPTY, "  --cluster <filename>          Single-linkage clusters at the -J threshold: lines representative<TAB>member."},
 };
 
 struct Parsed {
@@ -268,6 +272,18 @@ int main(int argc, char *argv[]) {
     top_k = (uint32_t)v;
   }
 
+  // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts
+  if (o.has(NEIGHBORS) || o.has(CLUSTER)) {
+    if (n_gpus > 1) {
+      cerr << "niqki: the self-join (--neighbors, --cluster) needs a single-GPU index (--gpus 1)" << endl;
+      return EXIT_FAILURE;
+    }
+    if (!nqhost::Index::has_self_join()) {
+      cerr << "niqki: this engine has no self-join" << endl;
+      return EXIT_FAILURE;
+    }
+  }
+
   const char *rule = "+-----------------------------------+-------------------------------+";
   cout << "+-------------------------------------------------------------------+" << endl
        << "|                            Informations                           |" << endl
@@ -283,7 +299,14 @@ int main(int argc, char *argv[]) {
     if (o.has(DOWNLAD)) cout << "--indexdownload needs network access and is not part of this build" << endl;
     if (o.has(DUMP)) ix->dump_index_disk(o.last(DUMP));
     clk.index_done();
+    if (o.has(CLUSTER)) {   // a phase of its own between indexing and the queries
+      ix->cluster_to_file(o.last(CLUSTER));
+      const RunClock::tp now = system_clock::now();
+      RunClock::row("| Cluster lasted (s)                |", clk.index_end, now);
+      clk.index_end = now;
+    }
     run_matrix(*ix, o, clk);
+    if (o.has(NEIGHBORS)) ix->query_neighbors();
     for (const Phase &ph : kQueryPhases) run_phase(*ix, o, ph);
     ix->outfile->close();
     const RunClock::tp done = system_clock::now();
