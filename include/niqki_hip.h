@@ -458,6 +458,33 @@ int niqki_neighbors_range(niqki_index *ix, uint32_t begin, uint32_t end, uint64_
  * (microseconds) and "cluster_pairs" (hits the link kernel went through; tools/bench_selfjoin.py). */
 int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *n_clusters, int mem);
 
+/* Dereplication: greedy representatives of the indexed genomes, in INDEX ORDER.  count(a, b) is the co-occurrence count
+ * of the stored sketches (the cell niqki_matrix_range gives, before any u16 wrap); a and b are linked when
+ * count(a, b) >= threshold.
+ *   1. genome t is a representative iff no representative g < t is linked to t;
+ *   2. labels[t] = t for a representative; for any other genome the linked representative r (of any index position,
+ *      also r > t) with the largest count(t, r), among equal counts the smallest r.  One exists by rule 1.
+ * So no two representatives are linked, every other genome is linked to its label, and every label is a
+ * representative (single linkage, niqki_cluster, promises none of that: its clusters chain).  labels[g] for every g
+ * in [0, n_genomes); label_counts (may be NULL) [g] = count(g, labels[g]), 0 for a representative;
+ * *n_representatives (may be NULL, host memory whatever mem is) = number of g with labels[g] == g.  mem as in
+ * niqki_cluster: NIQKI_MEM_DEVICE takes labels / label_counts as device arrays and copies nothing.
+ * The result is a function of the index and the threshold only: it does not depend on batch sizes, options, top_k
+ * (ignored here) or the order in which the device decides.  threshold 0 links everything: genome 0 is the only
+ * representative (only genome 0's list is made, for label_counts).  No genomes: 0 representatives.  The handle's
+ * min_score and top_k are unchanged when the call returns, also when it fails.  Handles as niqki_cluster
+ * (NIQKI_E_STATE on a slot-range shard).
+ * The pair list never leaves the device: the batches, the hit buffers, their budget (option "cluster_ws_mib") and the
+ * halving rule are niqki_cluster's (stat "derep_splits": the splits of the last call).  Per batch, in index order,
+ * decide rounds settle who is a representative -- a genome waits while a linked genome below it is undecided, so a
+ * batch may need several rounds (a path in index order: as many as it has genomes); stat "derep_rounds" = the most
+ * rounds one batch of the last call needed -- then every new representative offers itself to the genomes of its list
+ * with one 64-bit atomic maximum each.  Device state: 13 bytes a genome.
+ * While profiling is on the call times its phases with events, one synchronisation per batch: "derep_us_read",
+ * "derep_us_hits", "derep_us_decide", "derep_us_assign" (microseconds) and "derep_pairs" (hits the batches held). */
+int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts,
+                      uint32_t *n_representatives, int mem);
+
 /* dump_index_disk payload (src/niqki_index.cpp:42-55), before gzip and
  * without the trailing names: 6 x u32 header {lF,K,H,W,min_score,N} then per
  * bucket u32 size + size x u32 gid, buckets in fp + slot*2^W order, gids

@@ -117,6 +117,7 @@ ABI = [
     ("niqki_matrix_range", _int, [_vp, _u32, _u32, _vp, _u64, _int]),
     ("niqki_neighbors_range", _int, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, _int]),
     ("niqki_cluster", _int, [_vp, _u32, _vp, C.POINTER(_u32), _int]),
+    ("niqki_dereplicate", _int, [_vp, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
     ("niqki_export_dump_header", _int, [_vp, _vp]),
@@ -542,6 +543,17 @@ class Engine:
         n = _u32(0)
         self._ck(self.L.niqki_cluster(self.h, int(threshold), _p(labels), C.byref(n), MEM_HOST))
         return labels, int(n.value)
+
+    def dereplicate(self, threshold, counts=False):
+        """Greedy representatives in index order at co-occurrence count >= threshold: genome t is a representative
+        iff no representative below it is linked to it; labels[g] = g, or the linked representative with the largest
+        count (ties: the smallest).  (labels, n_representatives), or with counts=True
+        (labels, label_counts, n_representatives), label_counts[g] = count(g, labels[g]), 0 for a representative."""
+        labels = np.empty(self.n_genomes, dtype=np.uint32)
+        lc = np.empty(self.n_genomes, dtype=np.uint32) if counts else None
+        n = _u32(0)
+        self._ck(self.L.niqki_dereplicate(self.h, int(threshold), _p(labels), _p(lc) if counts else None, C.byref(n), MEM_HOST))
+        return (labels, lc, int(n.value)) if counts else (labels, int(n.value))
 
     def get_sketches(self, begin, n):
         out = np.empty((n, self.F), dtype=np.int32)

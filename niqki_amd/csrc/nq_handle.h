@@ -108,6 +108,9 @@ struct niqki_index {
   uint64_t cluster_splits = 0;      // stat "cluster_splits": batches the last niqki_cluster call had to halve
   double cluster_ms[4] = {0, 0, 0, 0};   // the last niqki_cluster call, while profiling is on: store read, gather + hits, link, flatten
   uint64_t cluster_pairs = 0;       // ... and the hits its link kernel went through
+  uint64_t derep_rounds = 0, derep_splits = 0;   // stats of the last niqki_dereplicate call: most decide rounds of a batch, halved batches
+  double derep_ms[4] = {0, 0, 0, 0};   // ... while profiling is on: store read, gather + hits, decide, assign
+  uint64_t derep_pairs = 0;         // ... and the hits its kernels went through
 
   nqi::Buf ws_seq, ws_recoff, ws_entry, ws_sk, ws_counts, ws_blk, ws_hitoff, ws_hc, ws_hg, ws_tc, ws_tg,
       ws_misc, ws_stash, ws_hl, ws_parent;

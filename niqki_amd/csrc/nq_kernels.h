@@ -255,6 +255,20 @@ hipError_t launch_cluster_link(uint32_t *parent, uint32_t n, const unsigned long
 // labels[g] = root of g; *n_roots (zeroed here) = number of roots.  labels may not alias parent.
 hipError_t launch_cluster_flatten(const uint32_t *parent, uint32_t n, uint32_t *labels, uint32_t *n_roots, hipStream_t stream);
 
+// ---- greedy representatives (nq_cluster.hip) -------------------------------------
+// state[g]: 0 undecided, 1 representative, 2 covered.  Decides the queries t0 + q, q < nq, of a batch whose hit lists
+// are (hit_off, hit_gids) and whose earlier genomes are all decided: two launches over the batch, then one workgroup
+// that runs the remaining rounds.  info: 4 words, zeroed once per call; info[0] = the most rounds a batch needed.
+hipError_t launch_derep_decide(uint8_t *state, uint32_t n, const unsigned long long *hit_off, const uint32_t *hit_gids, uint32_t t0,
+                               uint32_t nq, uint32_t *info, hipStream_t stream);
+// every representative of the batch: best[g] = max(best[g], count << 32 | ~t) over its hits g != t
+hipError_t launch_derep_assign(const uint8_t *state, unsigned long long *best, uint32_t n, const unsigned long long *hit_off,
+                               const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream);
+// labels[g] = g or the representative in best[g]; label_counts (may be null) = 0 or the count in best[g];
+// *n_reps (zeroed here) = number of representatives
+hipError_t launch_derep_finish(const uint8_t *state, const unsigned long long *best, uint32_t n, uint32_t *labels, uint32_t *label_counts,
+                               uint32_t *n_reps, hipStream_t stream);
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

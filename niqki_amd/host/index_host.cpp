@@ -975,11 +975,14 @@ void Index::query_matrix() {
 namespace {
 using neighbors_fn = int (*)(niqki_index *, uint32_t, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint64_t, int);
 using cluster_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, int);
+using derep_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, int);
 neighbors_fn engine_neighbors() { return (neighbors_fn)dlsym(RTLD_DEFAULT, "niqki_neighbors_range"); }
 cluster_fn engine_cluster() { return (cluster_fn)dlsym(RTLD_DEFAULT, "niqki_cluster"); }
+derep_fn engine_derep() { return (derep_fn)dlsym(RTLD_DEFAULT, "niqki_dereplicate"); }
 }  // namespace
 
 bool Index::has_self_join() { return engine_neighbors() != nullptr && engine_cluster() != nullptr; }
+bool Index::has_dereplication() { return engine_derep() != nullptr; }
 
 void Index::query_neighbors() {
   const neighbors_fn call = engine_neighbors();
@@ -1005,20 +1008,16 @@ void Index::query_neighbors() {
   }
 }
 
-void Index::cluster_to_file(const std::string &filestr) {
-  const cluster_fn call = engine_cluster();
-  if (!call || grp_) throw std::runtime_error("this engine has no self-join");
-  const uint32_t N = (uint32_t)filenames.size();
-  niqki_params p{};
-  check(niqki_get_params(h_, &p), "niqki_get_params");
-  std::vector<uint32_t> labels(N), start(N + 1, 0), order(N);
-  uint32_t n_clusters = 0;
-  check(call(h_, p.min_score, labels.data(), &n_clusters, NIQKI_MEM_HOST), "niqki_cluster");
-  // members by representative (a label is its cluster's smallest id, so label order is index order), in index order
+// lines label<TAB>member: the groups in the index order of their label (a member of its own group), inside a group the
+// label's own line first, then the other members in index order
+void Index::write_groups(const std::string &filestr, const std::vector<uint32_t> &labels) {
+  const uint32_t N = (uint32_t)labels.size();
+  std::vector<uint32_t> start(N + 1, 0), order(N);
   for (uint32_t g = 0; g < N; ++g) start[labels[g] + 1] += 1;
   for (uint32_t g = 0; g < N; ++g) start[g + 1] += start[g];
   std::vector<uint32_t> at(start.begin(), start.end() - 1);
-  for (uint32_t g = 0; g < N; ++g) order[at[labels[g]]++] = g;
+  for (uint32_t g = 0; g < N; ++g) if (labels[g] == g) order[at[g]++] = g;
+  for (uint32_t g = 0; g < N; ++g) if (labels[g] != g) order[at[labels[g]]++] = g;
   ParallelTextWriter out(filestr, host_threads());
   std::string text;
   for (uint32_t i = 0; i < N; ++i) {
@@ -1031,6 +1030,31 @@ void Index::cluster_to_file(const std::string &filestr) {
   }
   out.write(text);
   out.close();
+}
+
+void Index::cluster_to_file(const std::string &filestr) {
+  const cluster_fn call = engine_cluster();
+  if (!call || grp_) throw std::runtime_error("this engine has no self-join");
+  const uint32_t N = (uint32_t)filenames.size();
+  niqki_params p{};
+  check(niqki_get_params(h_, &p), "niqki_get_params");
+  std::vector<uint32_t> labels(N);
+  uint32_t n_clusters = 0;
+  check(call(h_, p.min_score, labels.data(), &n_clusters, NIQKI_MEM_HOST), "niqki_cluster");
+  // (a label is its cluster's smallest id: label order is index order and the label leads its cluster anyway)
+  write_groups(filestr, labels);
+}
+
+void Index::dereplicate_to_file(const std::string &filestr) {
+  const derep_fn call = engine_derep();
+  if (!call || grp_) throw std::runtime_error("this engine has no dereplication");
+  const uint32_t N = (uint32_t)filenames.size();
+  niqki_params p{};
+  check(niqki_get_params(h_, &p), "niqki_get_params");
+  std::vector<uint32_t> labels(N);
+  check(call(h_, p.min_score, labels.data(), nullptr, nullptr, NIQKI_MEM_HOST), "niqki_dereplicate");
+  // a representative may stand for genomes that precede it in the index: its own line still leads its group
+  write_groups(filestr, labels);
 }
 
 // ---- dump ------------------------------------------------------------------------

@@ -65,11 +65,17 @@ class Index {
   // single-linkage clusters at min_score (niqki_cluster) as lines representative<TAB>member: clusters in the order of
   // their representative's index position, members in index order; a gzip file like every output of the program
   void cluster_to_file(const std::string &filestr);
+  // Dereplication (long option --derep; single-GPU index; niqki_dereplicate, looked up at run time like the two above):
+  // greedy representatives at min_score in index order, as lines representative<TAB>member: groups in the order of
+  // their representative's index position, the representative's own line first, then its members in index order
+  static bool has_dereplication();
+  void dereplicate_to_file(const std::string &filestr);
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
 
  private:
+  void write_groups(const std::string &filestr, const std::vector<uint32_t> &labels);
   struct Batch;
   void stage_batch(Batch &b, bool prefetch);
   void flush_insert(Batch &b);

@@ -8,6 +8,8 @@
 //   --top <n>      report at most n best hits per query (-Q / -q; niqki_params.top_k), 0 = all
 //   --neighbors    the indexed genomes themselves as queries, in index order, written like -Q (niqki_neighbors_range)
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
+//   --derep <f>    greedy representatives at the -J threshold, in index order, into f: representative<TAB>member
+//                  (niqki_dereplicate); the lines whose two names are equal are the dereplicated list
 #include <libgen.h>
 #include <limits.h>
 #include <unistd.h>
@@ -34,7 +36,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -66,6 +68,7 @@ const Desc kDesc[] = {
     {TOP, "", "top", NUMERIC, "  --top <int>                   Report at most <int> best hits per query (0: all)."},
     {NEIGHBORS, "", "neighbors", NONE, "  --neighbors                   Query the index with its own genomes, in index order (output as -Q)."},
     {CLUSTER, "", "cluster", NONEMPTY, "  --cluster <filename>          Single-linkage clusters at the -J threshold: lines representative<TAB>member."},
+    {DEREP, "", "derep", NONEMPTY, "  --derep <filename>            Dereplication at the -J threshold: greedy representatives in index order, lines representative<TAB>member."},
 };
 
 struct Parsed {
@@ -273,13 +276,17 @@ int main(int argc, char *argv[]) {
   }
 
   // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts
-  if (o.has(NEIGHBORS) || o.has(CLUSTER)) {
+  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP)) {
     if (n_gpus > 1) {
-      cerr << "niqki: the self-join (--neighbors, --cluster) needs a single-GPU index (--gpus 1)" << endl;
+      cerr << "niqki: the self-join (--neighbors, --cluster, --derep) needs a single-GPU index (--gpus 1)" << endl;
       return EXIT_FAILURE;
     }
-    if (!nqhost::Index::has_self_join()) {
+    if ((o.has(NEIGHBORS) || o.has(CLUSTER)) && !nqhost::Index::has_self_join()) {
       cerr << "niqki: this engine has no self-join" << endl;
+      return EXIT_FAILURE;
+    }
+    if (o.has(DEREP) && !nqhost::Index::has_dereplication()) {
+      cerr << "niqki: this engine has no dereplication" << endl;
       return EXIT_FAILURE;
     }
   }
@@ -303,6 +310,12 @@ int main(int argc, char *argv[]) {
       ix->cluster_to_file(o.last(CLUSTER));
       const RunClock::tp now = system_clock::now();
       RunClock::row("| Cluster lasted (s)                |", clk.index_end, now);
+      clk.index_end = now;
+    }
+    if (o.has(DEREP)) {   // ... and so is the dereplication, after the clusters where both are asked for
+      ix->dereplicate_to_file(o.last(DEREP));
+      const RunClock::tp now = system_clock::now();
+      RunClock::row("| Dereplication lasted (s)          |", clk.index_end, now);
       clk.index_end = now;
     }
     run_matrix(*ix, o, clk);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The self-join (niqki_cluster) at the index shape of bench.py: 100 000 genomes, S = 15, W = 12, -J 0.1.  The index
+"""The self-join (niqki_cluster, niqki_dereplicate) at the index shape of bench.py: 100 000 genomes, S = 15, W = 12, -J 0.1.  The index
 is made of synthetic sketches (families of related genomes, made and inserted on the device, as tools/bench_topk.py
 does).  Every case runs in a child process of its own under its own time limit, one after the other; the first that
 fails ends the run.  One JSON line per case:
@@ -11,8 +11,14 @@ fails ends the run.  One JSON line per case:
               time x genomes / slice -- an extrapolation, not a measurement
   one         the link kernel's contention case: --extreme identical genomes, ONE component, every hit redundant
   singletons  unrelated genomes at a threshold nothing reaches: every list holds the genome itself only
+  derep, derep_one, derep_singletons
+              niqki_dereplicate on the indexes of cluster / one / singletons, and niqki_cluster on the SAME handle in
+              the same process as the yardstick: the read and hits phases are the same work, the decide + assign
+              phases stand beside the link + flatten phases
+  derep_path  the decide rounds' worst case: --path genomes, each linked to its two index neighbours only, inside
+              one batch; microseconds per round
 
-    python tools/bench_selfjoin.py [--genomes 100000] [--slice 4096] [--extreme 20000] [--out FILE]
+    python tools/bench_selfjoin.py [--genomes 100000] [--slice 4096] [--extreme 20000] [--path 1024] [--out FILE]
 """
 import argparse
 import json
@@ -77,6 +83,67 @@ def case_cluster(args, kind):
     return res
 
 
+def make_path_index(args):
+    """--path genomes in index order, each the one before with 20 % of its cells drawn again: consecutive ones share
+    0.8, two apart 0.64; the threshold lies between"""
+    import torch
+    import niqki_amd
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev)
+    g.manual_seed(args.seed)
+    n = args.path
+    rows = [torch.randint(0, 1 << W, (F,), dtype=torch.int32, device=dev, generator=g)]
+    for _ in range(n - 1):
+        s = rows[-1].clone()
+        m = torch.rand((F,), device=dev, generator=g) < 0.2
+        s[m] = torch.randint(0, 1 << W, (int(m.sum().item()),), dtype=torch.int32, device=dev, generator=g)
+        rows.append(s)
+    e = niqki_amd.Engine(K=K, S=S, W=W, H=H, min_score_value=int(0.72 * F))
+    e.set_stream(torch.cuda.current_stream().cuda_stream)
+    e.set_option("query_batch", max(n, 1))
+    e.insert_dev(torch.stack(rows).contiguous(), n)
+    e.build()
+    torch.cuda.synchronize()
+    return e, n
+
+
+def case_derep(args, kind):
+    import torch
+    if kind == "path":
+        e, N = make_path_index(args)
+        thr = e.min_score
+    else:
+        e, N = make_index(args, kind)
+        thr = e.min_score if kind != "singletons" else F // 2
+    e.dereplicate(thr)                                 # warm-up: workspace allocations
+    t = time.time()
+    labels, n = e.dereplicate(thr)
+    wall = time.time() - t
+    e.cluster(thr)
+    t = time.time()
+    _, n_cl = e.cluster(thr)
+    wall_cl = time.time() - t
+    e.profile(True)
+    e.dereplicate(thr)
+    us = {k: e.stat("derep_us_" + k) for k in ("read", "hits", "decide", "assign")}
+    pairs, rounds, splits = e.stat("derep_pairs"), e.stat("derep_rounds"), e.stat("derep_splits")
+    e.cluster(thr)
+    e.profile(False)
+    cl = {k: e.stat("cluster_us_" + k) for k in ("read", "hits", "link", "flatten")}
+    res = {"case": "derep" if kind == "families" else "derep_" + kind, "genomes": N, "threshold": int(thr),
+           "representatives": n, "clusters": n_cl, "wall_s": round(wall, 3), "cluster_wall_s": round(wall_cl, 3),
+           "phases_ms": {k: round(v / 1e3, 3) for k, v in us.items()},
+           "cluster_phases_ms": {k: round(v / 1e3, 3) for k, v in cl.items()}, "hits": pairs, "rounds": rounds,
+           "splits": splits,
+           "decide_plus_assign_over_gather_plus_hits": round((us["decide"] + us["assign"]) / max(us["hits"], 1), 4),
+           "link_plus_flatten_over_gather_plus_hits": round((cl["link"] + cl["flatten"]) / max(cl["hits"], 1), 4)}
+    if kind == "path":
+        res["decide_us_per_round"] = round(us["decide"] / max(rounds, 1), 2)
+    e.close()
+    torch.cuda.synchronize()
+    return res
+
+
 def case_host(args):
     import numpy as np
     e, N = make_index(args, "families")
@@ -111,20 +178,27 @@ def main():
     ap.add_argument("--genomes", type=int, default=100000)
     ap.add_argument("--slice", type=int, default=4096)
     ap.add_argument("--extreme", type=int, default=20000)
+    ap.add_argument("--path", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per case")
+    ap.add_argument("--only", default=None, help="comma-separated cases instead of all of them")
     ap.add_argument("--out", default=None)
     ap.add_argument("--case", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.case:
-        res = case_host(args) if args.case == "host" else case_cluster(args, args.case)
+        if args.case.startswith("derep"):
+            res = case_derep(args, args.case[6:] or "families")
+        else:
+            res = case_host(args) if args.case == "host" else case_cluster(args, args.case)
         print(json.dumps(res), flush=True)
         return 0
     lines = []
-    for case in ("families", "host", "one", "singletons"):
+    for case in ("families", "host", "one", "singletons", "derep", "derep_one", "derep_singletons", "derep_path"):
+        if args.only and case not in args.only.split(","):
+            continue
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case,
                "--genomes", str(args.genomes), "--slice", str(args.slice), "--extreme", str(args.extreme),
-               "--seed", str(args.seed)]
+               "--path", str(args.path), "--seed", str(args.seed)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:                          # nothing more on the GPU after a failure
             print("case %s failed with exit status %d\n%s" % (case, r.returncode, r.stderr[-2000:]), flush=True)
@@ -132,7 +206,7 @@ def main():
         lines.append(r.stdout.strip().split("\n")[-1])
         print(lines[-1], flush=True)
     if args.out:
-        with open(args.out, "w") as f:
+        with open(args.out, "a" if args.only else "w") as f:
             f.write("\n".join(lines) + "\n")
     return 0
 
