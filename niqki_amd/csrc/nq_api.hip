@@ -558,21 +558,21 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "class_mask")) { *value = (ix->built && ix->hmask_ok) ? 1 : 0; return NIQKI_OK; }
   if (!std::strcmp(key, "last_gather_form")) { *value = ix->last_form; return NIQKI_OK; }
   if (!std::strcmp(key, "last_hits_form")) { *value = ix->last_hits_form; return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_splits")) { *value = ix->cluster_splits; return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_splits")) { *value = ix->cluster_stats.splits; return NIQKI_OK; }
   // the last niqki_cluster call while profiling was on (niqki_profile_enable): microseconds per phase, hits linked
-  if (!std::strcmp(key, "cluster_us_read")) { *value = (uint64_t)(ix->cluster_ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_us_hits")) { *value = (uint64_t)(ix->cluster_ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_us_link")) { *value = (uint64_t)(ix->cluster_ms[2] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_us_flatten")) { *value = (uint64_t)(ix->cluster_ms[3] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_pairs")) { *value = ix->cluster_pairs; return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_read")) { *value = (uint64_t)(ix->cluster_stats.ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_hits")) { *value = (uint64_t)(ix->cluster_stats.ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_link")) { *value = (uint64_t)(ix->cluster_stats.ms[2] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_us_flatten")) { *value = (uint64_t)(ix->cluster_stats.ms[3] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cluster_pairs")) { *value = ix->cluster_stats.pairs; return NIQKI_OK; }
   // the last niqki_dereplicate call; the phases and the hits while profiling was on
-  if (!std::strcmp(key, "derep_rounds")) { *value = ix->derep_rounds; return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_splits")) { *value = ix->derep_splits; return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_read")) { *value = (uint64_t)(ix->derep_ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_hits")) { *value = (uint64_t)(ix->derep_ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_decide")) { *value = (uint64_t)(ix->derep_ms[2] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_assign")) { *value = (uint64_t)(ix->derep_ms[3] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_pairs")) { *value = ix->derep_pairs; return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_rounds")) { *value = ix->derep_stats.rounds; return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_splits")) { *value = ix->derep_stats.splits; return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_us_read")) { *value = (uint64_t)(ix->derep_stats.ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_us_hits")) { *value = (uint64_t)(ix->derep_stats.ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_us_decide")) { *value = (uint64_t)(ix->derep_stats.ms[2] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_us_assign")) { *value = (uint64_t)(ix->derep_stats.ms[3] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "derep_pairs")) { *value = ix->derep_stats.pairs; return NIQKI_OK; }
   if (!std::strcmp(key, "inflate_files_in_flight") || !std::strcmp(key, "inflate_files_in_flight_8k")) {
     // how many files a launch of the device inflate runs at once (workgroups the device keeps resident), by kernel form
     (void)hipSetDevice(ix->device);

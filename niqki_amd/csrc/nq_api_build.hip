@@ -294,6 +294,24 @@ int build_range(niqki_index *ix, uint32_t g_base, uint32_t N) {
   return NIQKI_OK;
 }
 
+// the stored sketches of genomes [t0, t0 + n) as query sketches (whole rows of F cells) in device memory.  A paged
+// index keeps its sketch store in page-locked host memory: the device reads the cells from there (zero-copy, 2 bytes
+// per cell).
+int stored_sketch_rows(niqki_index *ix, uint32_t t0, uint32_t n, int32_t *dst) {
+  if (!n) return NIQKI_OK;
+  if (!ix->resident_bytes) {
+    NQ_HIP(ix, nq::launch_store_read(ix->d, ix->store, ix->cap, t0, n, dst, ix->stream));
+    return NIQKI_OK;
+  }
+  nq::Derived d = ix->d;
+  d.slot_begin = ix->full_begin;
+  d.slot_end = ix->full_end;
+  void *dp = nullptr;
+  NQ_HIP(ix, hipHostGetDevicePointer(&dp, ix->host_store, 0));
+  NQ_HIP(ix, nq::launch_store_read(d, (const uint16_t *)dp, ix->host_cap, t0, n, dst, ix->stream));
+  return NIQKI_OK;
+}
+
 }  // namespace nqi
 
 using namespace nqi;

@@ -205,11 +205,41 @@ int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride,
   return NIQKI_OK;
 }
 
-// hits from device-resident counters into device buffers; hit_off device (nq+1)
-int hits_dev(niqki_index *ix, const uint16_t *counts, uint32_t nq, uint64_t stride, uint32_t gid_begin,
-             uint32_t n_gids, unsigned long long *hit_off, uint32_t *hc, uint32_t *hg, uint64_t capacity,
-             bool check_capacity, uint64_t *total_out, const uint16_t *counts2) {
-  nq::HitsArgs a;
+int counter_planes(niqki_index *ix, uint32_t n, uint64_t stride, Planes &pl, bool zeroed) {
+  const size_t plane = (size_t)n * stride * 2, bytes = std::max<size_t>(plane * (two_planes(ix) ? 2 : 1), 4);
+  int rc = ensure(ix, ix->ws_counts, bytes);
+  if (rc) return rc;
+  pl.c1 = (uint16_t *)ix->ws_counts.p;
+  pl.c2 = two_planes(ix) ? (uint16_t *)((char *)ix->ws_counts.p + plane) : nullptr;
+  if (zeroed) NQ_HIP(ix, hipMemsetAsync(ix->ws_counts.p, 0, bytes, ix->stream));
+  return NIQKI_OK;
+}
+
+int hit_out_ws(niqki_index *ix, uint32_t n, uint64_t capacity, HitOut &out) {
+  int rc;
+  if ((rc = ensure(ix, ix->ws_hitoff, (size_t)(n + 1) * 8))) return rc;
+  if ((rc = ensure(ix, ix->ws_hc, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
+  if ((rc = ensure(ix, ix->ws_hg, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
+  out = HitOut{(unsigned long long *)ix->ws_hitoff.p, (uint32_t *)ix->ws_hc.p, (uint32_t *)ix->ws_hg.p, capacity, true};
+  return NIQKI_OK;
+}
+
+int hits_to_host(niqki_index *ix, int rc, const HitOut &out, uint32_t n, void *hit_off, uint32_t *hit_counts, uint32_t *hit_gids) {
+  if (rc && rc != NIQKI_E_CAPACITY) return rc;
+  NQ_HIP(ix, hipMemcpyAsync(hit_off, out.off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ix->stream));
+  if (rc == NIQKI_OK && out.total) {
+    NQ_HIP(ix, hipMemcpyAsync(hit_counts, out.counts, (size_t)out.total * 4, hipMemcpyDeviceToHost, ix->stream));
+    NQ_HIP(ix, hipMemcpyAsync(hit_gids, out.gids, (size_t)out.total * 4, hipMemcpyDeviceToHost, ix->stream));
+  }
+  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  return rc;
+}
+
+// What the two forms of the hit step share: the rows, the output, the top-k clamp and the scratch the hits are ordered
+// in (ws_tc / ws_tg).  The block scratch (ws_blk) is each form's own.
+static int hits_args(niqki_index *ix, const uint16_t *counts, const uint16_t *counts2, uint32_t nq, uint64_t stride, uint32_t gid_begin,
+                     uint32_t n_gids, const HitOut &out, nq::HitsArgs &a) {
+  a = nq::HitsArgs{};
   a.counts = counts;
   a.counts2 = counts2;
   a.stride = stride;
@@ -218,40 +248,54 @@ int hits_dev(niqki_index *ix, const uint16_t *counts, uint32_t nq, uint64_t stri
   a.n_gids = n_gids;
   a.min_score = ix->d.min_score;
   a.n_blk = (n_gids + nq::kHitsBlk - 1) / nq::kHitsBlk;
-  a.hit_off = hit_off;
-  a.hit_counts = hc;
-  a.hit_gids = hg;
-  a.capacity = capacity;
-  if (nq == 0 || a.n_blk == 0) {
-    NQ_HIP(ix, hipMemsetAsync(hit_off, 0, (size_t)(nq + 1) * 8, ix->stream));
-    if (total_out) *total_out = 0;
-    return NIQKI_OK;
-  }
-  // top-k (k < n_gids: k >= n_gids cuts nothing): the select replaces the hit count, the output holds <= nq x k entries
+  a.hit_off = out.off;
+  a.hit_counts = out.counts;
+  a.hit_gids = out.gids;
+  a.capacity = out.capacity;
+  // top-k (k < n_gids: k >= n_gids cuts nothing): the output holds <= nq x k entries
   a.top_k = ix->p.top_k < n_gids ? ix->p.top_k : 0u;
-  const uint64_t room = a.top_k ? std::min<uint64_t>(capacity, (uint64_t)nq * a.top_k) : capacity;
-  const size_t nb = (size_t)nq * a.n_blk;
-  int rc = ensure(ix, ix->ws_blk, (a.top_k ? nb * (2 + nq::kSelBlkWords) + nq : nb) * 4);
-  if (rc) return rc;
+  const uint64_t room = a.top_k ? std::min<uint64_t>(out.capacity, (uint64_t)nq * a.top_k) : out.capacity;
+  int rc;
   if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
   if ((rc = ensure(ix, ix->ws_tg, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
+  a.tmp_counts = (uint32_t *)ix->ws_tc.p;
+  a.tmp_gids = (uint32_t *)ix->ws_tg.p;
+  return NIQKI_OK;
+}
+
+// between a form's count and emit launches, with out.check: the total back, NIQKI_E_CAPACITY where it does not fit
+static int check_capacity(niqki_index *ix, uint32_t nq, HitOut &out) {
+  if (!out.check) return NIQKI_OK;
+  unsigned long long total = 0;
+  NQ_HIP(ix, hipMemcpyAsync(&total, out.off + nq, 8, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  out.total = total;
+  return total > out.capacity ? NIQKI_E_CAPACITY : NIQKI_OK;
+}
+
+// hits from device-resident counters into device buffers; out.off device (nq+1)
+int hits_dev(niqki_index *ix, const uint16_t *counts, const uint16_t *counts2, uint32_t nq, uint64_t stride, uint32_t gid_begin,
+             uint32_t n_gids, HitOut &out) {
+  out.total = 0;
+  if (nq == 0 || n_gids == 0) {   // (before any scratch is sized)
+    NQ_HIP(ix, hipMemsetAsync(out.off, 0, (size_t)(nq + 1) * 8, ix->stream));
+    return NIQKI_OK;
+  }
+  nq::HitsArgs a;
+  int rc = hits_args(ix, counts, counts2, nq, stride, gid_begin, n_gids, out, a);
+  if (rc) return rc;
+  // with top-k the select replaces the hit count
+  const size_t nb = (size_t)nq * a.n_blk;
+  if ((rc = ensure(ix, ix->ws_blk, (a.top_k ? nb * (2 + nq::kSelBlkWords) + nq : nb) * 4))) return rc;
   a.blk_counts = (uint32_t *)ix->ws_blk.p;
   if (a.top_k) {
     a.blk_skip = a.blk_counts + nb;
     a.blk_tmp = a.blk_skip + nb;
     a.thr = a.blk_tmp + nb * nq::kSelBlkWords;
   }
-  a.tmp_counts = (uint32_t *)ix->ws_tc.p;
-  a.tmp_gids = (uint32_t *)ix->ws_tg.p;
   Span sp(ix, NIQKI_KC_HITS);
   NQ_HIP(ix, nq::launch_hits_count(a, ix->stream));
-  if (check_capacity) {
-    unsigned long long total = 0;
-    NQ_HIP(ix, hipMemcpyAsync(&total, hit_off + nq, 8, hipMemcpyDeviceToHost, ix->stream));
-    NQ_HIP(ix, hipStreamSynchronize(ix->stream));
-    if (total_out) *total_out = total;
-    if (total > capacity) return NIQKI_E_CAPACITY;
-  }
+  if ((rc = check_capacity(ix, nq, out))) return rc;
   NQ_HIP(ix, nq::launch_hits_emit(a, ix->stream));
   return NIQKI_OK;
 }
@@ -277,107 +321,96 @@ static bool hit_lists_apply(const niqki_index *ix) {
 }
 
 // Index::query_sketch (src/niqki_index.cpp:633-687) for nq device-resident whole sketches into device buffers: counters,
-// threshold, order.  c1 / c2: counter planes of nq rows (c2 only on a two-plane handle).  On a single-segment, single-
-// plane index (hit_lists_apply) the hits leave the gather kernel as ordered lists and no counter row is written or read
-// again, except for a query with more than hit_list_cap hits.
-int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16_t *c1, uint16_t *c2, uint64_t stride,
-                   unsigned long long *hit_off, uint32_t *hc, uint32_t *hg, uint64_t capacity, bool check_capacity,
-                   uint64_t *total_out) {
+// threshold, order.  pl: counter planes of nq rows (counter_planes).  On a single-segment, single-plane index
+// (hit_lists_apply) the hits leave the gather kernel as ordered lists and no counter row is written or read again,
+// except for a query with more than hit_list_cap hits.
+int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, const Planes &pl, uint64_t stride, HitOut &out) {
   int rc = build_if_needed(ix);
   if (rc) return rc;
   const uint32_t N = ix->built_n;
   const bool lists = nq && hit_lists_apply(ix);
   ix->last_hits_form = lists ? 1u : 0u;
   if (!lists) {
-    if ((rc = counts_dev(ix, sketches, ix->d.F, first_slot(ix), nq, c1, stride, c2))) return rc;
-    return hits_dev(ix, c1, nq, stride, 0, N, hit_off, hc, hg, capacity, check_capacity, total_out, c2);
+    if ((rc = counts_dev(ix, sketches, ix->d.F, first_slot(ix), nq, pl.c1, stride, pl.c2))) return rc;
+    return hits_dev(ix, pl.c1, pl.c2, nq, stride, 0, N, out);
   }
+  out.total = 0;
   const uint32_t cap = hit_list_cap(ix);
-  const uint32_t k = ix->p.top_k < N ? ix->p.top_k : 0u;   // (top-k: a query's segment is the first min(n, k) of its list)
-  const uint64_t room = k ? std::min<uint64_t>(capacity, (uint64_t)nq * k) : capacity;
+  nq::HitsArgs a;   // (top-k: a query's segment is the first min(n, k) of its list; ws_tc / ws_tg: lists of > 2048 hits)
+  if ((rc = hits_args(ix, pl.c1, nullptr, nq, stride, 0, N, out, a))) return rc;
   if ((rc = ensure(ix, ix->ws_hl, (size_t)nq * cap * 8))) return rc;
   if ((rc = ensure(ix, ix->ws_blk, ((size_t)nq * 2 + 1) * 4))) return rc;   // the lists' sizes, then the overflowing queries
   nq::CandOut co;
   co.hl = (unsigned long long *)ix->ws_hl.p;
   co.hl_n = (uint32_t *)ix->ws_blk.p;
-  co.hl_over = (uint32_t *)ix->ws_blk.p + nq;
-  if ((rc = ensure(ix, ix->ws_tc, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;   // (lists of > 2048 hits)
-  if ((rc = ensure(ix, ix->ws_tg, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
+  co.hl_over = co.hl_n + nq;
   co.hl_cap = cap;
   co.hl_min = ix->d.min_score;
-  if ((rc = counts_dev(ix, sketches, ix->d.F, first_slot(ix), nq, c1, stride, nullptr, &co))) return rc;
-  nq::HitsArgs a{};
-  a.counts = c1;
-  a.counts2 = nullptr;
-  a.stride = stride;
-  a.nq = nq;
-  a.gid_begin = 0;
-  a.n_gids = N;
-  a.min_score = ix->d.min_score;
-  a.hit_off = hit_off;
-  a.hit_counts = hc;
-  a.hit_gids = hg;
-  a.tmp_counts = (uint32_t *)ix->ws_tc.p;
-  a.tmp_gids = (uint32_t *)ix->ws_tg.p;
-  a.capacity = capacity;
-  a.top_k = k;
-  uint32_t *over = (uint32_t *)ix->ws_blk.p + nq;
+  if ((rc = counts_dev(ix, sketches, ix->d.F, first_slot(ix), nq, pl.c1, stride, nullptr, &co))) return rc;
   Span sp(ix, NIQKI_KC_HITS);
-  NQ_HIP(ix, nq::launch_hitlist_scan((const uint32_t *)ix->ws_blk.p, a, cap, over, ix->stream));
-  if (check_capacity) {
-    unsigned long long total = 0;
-    NQ_HIP(ix, hipMemcpyAsync(&total, hit_off + nq, 8, hipMemcpyDeviceToHost, ix->stream));
-    NQ_HIP(ix, hipStreamSynchronize(ix->stream));
-    if (total_out) *total_out = total;
-    if (total > capacity) return NIQKI_E_CAPACITY;
-  }
-  NQ_HIP(ix, nq::launch_hitlist_emit(a, (const uint32_t *)ix->ws_blk.p, (const unsigned long long *)ix->ws_hl.p, cap, over, ix->stream));
+  NQ_HIP(ix, nq::launch_hitlist_scan(co.hl_n, a, cap, co.hl_over, ix->stream));
+  if ((rc = check_capacity(ix, nq, out))) return rc;
+  NQ_HIP(ix, nq::launch_hitlist_emit(a, co.hl_n, co.hl, cap, co.hl_over, ix->stream));
   return NIQKI_OK;
 }
 
-// Hits of nq sketches (host memory, or device-resident when sk_dev) into HOST arrays:
-// batches of query_batch sketches, hits appended in query order.
-int query_to_host(niqki_index *ix, const int32_t *sketches, bool sk_dev, uint32_t nq, uint64_t *hit_off,
-                  uint32_t *hit_counts, uint32_t *hit_gids, uint64_t capacity) {
+SketchSource host_rows(niqki_index *ix, const int32_t *sketches) {
+  return [=](uint32_t q0, uint32_t n, const int32_t **d_sk) {
+    const size_t bytes = (size_t)n * ix->d.F * 4;
+    int rc = ensure(ix, ix->ws_sk, bytes);
+    if (rc) return rc;
+    NQ_HIP(ix, hipMemcpyAsync(ix->ws_sk.p, sketches + (size_t)q0 * ix->d.F, bytes, hipMemcpyHostToDevice, ix->stream));
+    *d_sk = (const int32_t *)ix->ws_sk.p;
+    return (int)NIQKI_OK;
+  };
+}
+
+SketchSource device_rows(niqki_index *ix, const int32_t *sketches) {
+  return [=](uint32_t q0, uint32_t, const int32_t **d_sk) {
+    *d_sk = sketches + (size_t)q0 * ix->d.F;
+    return (int)NIQKI_OK;
+  };
+}
+
+SketchSource stored_rows(niqki_index *ix, uint32_t begin) {
+  return [=](uint32_t q0, uint32_t n, const int32_t **d_sk) {
+    int rc = ensure(ix, ix->ws_misc, (size_t)n * ix->d.F * 4);
+    if (rc) return rc;
+    *d_sk = (const int32_t *)ix->ws_misc.p;
+    return stored_sketch_rows(ix, begin + q0, n, (int32_t *)ix->ws_misc.p);
+  };
+}
+
+// queries per round of launches: option "query_batch" bounds the counter rows (2N bytes per query); a small index
+// (<= 12 288 genomes) that takes the hit-list form writes rows only for the rare overflowing query, so a whole staged
+// batch of short reads goes through in one round (64 rounds of 1024 cost the lines-mode host path twice its kernels'
+// time)
+uint32_t query_rows_per_batch(const niqki_index *ix) {
+  return hit_lists_apply(ix) && ix->built_n <= nq::kHitListMaxTile ? std::max<uint32_t>(ix->query_batch, 65536u) : ix->query_batch;
+}
+
+// Every hit_off entry is a true total, whatever the capacity; nothing is written beyond it, and NIQKI_E_CAPACITY comes
+// at the end.
+int query_to_host(niqki_index *ix, const SketchSource &src, uint32_t nq, uint32_t qb, uint64_t *hit_off, uint32_t *hit_counts,
+                  uint32_t *hit_gids, uint64_t capacity) {
   int rc;
-  const uint32_t N = ix->built_n;
-  const uint64_t stride = NIQKI_ROW_STRIDE(N);
+  const uint64_t stride = NIQKI_ROW_STRIDE(ix->built_n);
   uint64_t base = 0;
   bool overflow = false;
   hit_off[0] = 0;
-  // queries per round of launches: option "query_batch" bounds the counter rows (2N bytes per query); a small index
-  // (<= 12 288 genomes) that takes the hit-list form writes rows only for the rare overflowing query, so a whole staged
-  // batch of short reads goes through in one round (64 rounds of 1024 cost the lines-mode host path twice its kernels'
-  // time)
-  const uint32_t qb = hit_lists_apply(ix) && N <= nq::kHitListMaxTile ? std::max<uint32_t>(ix->query_batch, 65536u) : ix->query_batch;
-  const size_t planes = two_planes(ix) ? 2 : 1;
   std::vector<unsigned long long> off(std::min(qb, nq) + 1);
   for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
     const uint32_t n = std::min(qb, nq - q0);
-    if (!sk_dev && (rc = ensure(ix, ix->ws_sk, (size_t)n * ix->d.F * 4))) return rc;
-    const size_t plane = std::max<size_t>((size_t)n * stride * 2, 2);
-    if ((rc = ensure(ix, ix->ws_counts, plane * planes))) return rc;
-    uint16_t *c1 = (uint16_t *)ix->ws_counts.p, *c2 = planes == 2 ? (uint16_t *)((char *)ix->ws_counts.p + plane) : nullptr;
-    if ((rc = ensure(ix, ix->ws_hitoff, (size_t)(n + 1) * 8))) return rc;
-    const uint64_t room = overflow || base > capacity ? 0 : capacity - base;
-    if ((rc = ensure(ix, ix->ws_hc, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
-    if ((rc = ensure(ix, ix->ws_hg, (size_t)std::max<uint64_t>(room, 1) * 4))) return rc;
-    const int32_t *d_sk = sketches + (size_t)q0 * ix->d.F;
-    if (!sk_dev) {
-      NQ_HIP(ix, hipMemcpyAsync(ix->ws_sk.p, d_sk, (size_t)n * ix->d.F * 4, hipMemcpyHostToDevice, ix->stream));
-      d_sk = (const int32_t *)ix->ws_sk.p;
-    }
-    uint64_t total = 0;
-    rc = query_hits_dev(ix, d_sk, n, c1, c2, stride, (unsigned long long *)ix->ws_hitoff.p, (uint32_t *)ix->ws_hc.p,
-                        (uint32_t *)ix->ws_hg.p, room, true, &total);
-    if (rc && rc != NIQKI_E_CAPACITY) return rc;
-    NQ_HIP(ix, hipMemcpyAsync(off.data(), ix->ws_hitoff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ix->stream));
-    if (rc == NIQKI_OK && total) {
-      NQ_HIP(ix, hipMemcpyAsync(hit_counts + base, ix->ws_hc.p, (size_t)total * 4, hipMemcpyDeviceToHost, ix->stream));
-      NQ_HIP(ix, hipMemcpyAsync(hit_gids + base, ix->ws_hg.p, (size_t)total * 4, hipMemcpyDeviceToHost, ix->stream));
-    }
-    NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+    const int32_t *d_sk = nullptr;
+    Planes pl;
+    HitOut out;
+    if ((rc = src(q0, n, &d_sk))) return rc;
+    if ((rc = counter_planes(ix, n, stride, pl))) return rc;
+    if ((rc = hit_out_ws(ix, n, overflow || base > capacity ? 0 : capacity - base, out))) return rc;
+    rc = query_hits_dev(ix, d_sk, n, pl, stride, out);
+    rc = hits_to_host(ix, rc, out, n, off.data(), hit_counts + base, hit_gids + base);
     if (rc == NIQKI_E_CAPACITY) overflow = true;
+    else if (rc) return rc;
     for (uint32_t i = 0; i < n; ++i) hit_off[q0 + i + 1] = base + off[i + 1];
     base += off[n];
   }
@@ -418,13 +451,10 @@ int niqki_query_counts32(niqki_index *ix, const int32_t *sketches, uint32_t nq, 
   if (rc) return rc;
   if (stride < ix->n_genomes || (stride & 1)) return fail(ix, NIQKI_E_INVALID, "stride must be even and >= genome count");
   const uint32_t qb = mem == NIQKI_MEM_DEVICE ? std::min<uint32_t>(nq, 4096) : ix->query_batch;
-  const size_t planes = two_planes(ix) ? 2 : 1;
   for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
     const uint32_t n = std::min(qb, nq - q0);
-    const size_t plane = (size_t)n * stride * 2;
-    if ((rc = ensure(ix, ix->ws_counts, std::max<size_t>(plane * planes, 4)))) return rc;
-    uint16_t *c1 = (uint16_t *)ix->ws_counts.p, *c2 = planes == 2 ? (uint16_t *)((char *)ix->ws_counts.p + plane) : nullptr;
-    NQ_HIP(ix, hipMemsetAsync(ix->ws_counts.p, 0, std::max<size_t>(plane * planes, 4), ix->stream));
+    Planes pl;
+    if ((rc = counter_planes(ix, n, stride, pl, true))) return rc;
     const int32_t *d_sk = sketches + (size_t)q0 * ix->d.F;
     uint32_t *d_out = counts + (size_t)q0 * stride;
     if (mem == NIQKI_MEM_HOST) {
@@ -434,8 +464,8 @@ int niqki_query_counts32(niqki_index *ix, const int32_t *sketches, uint32_t nq, 
       d_sk = (const int32_t *)ix->ws_sk.p;
       d_out = (uint32_t *)ix->ws_misc.p;
     }
-    if ((rc = counts_dev(ix, d_sk, ix->d.F, first_slot(ix), n, c1, stride, c2))) return rc;
-    NQ_HIP(ix, nq::launch_plane_sum32(c1, c2, d_out, (uint64_t)n * stride, ix->stream));
+    if ((rc = counts_dev(ix, d_sk, ix->d.F, first_slot(ix), n, pl.c1, stride, pl.c2))) return rc;
+    NQ_HIP(ix, nq::launch_plane_sum32(pl.c1, pl.c2, d_out, (uint64_t)n * stride, ix->stream));
     if (mem == NIQKI_MEM_HOST) {
       NQ_HIP(ix, hipMemcpyAsync(counts + (size_t)q0 * stride, d_out, (size_t)n * stride * 4, hipMemcpyDeviceToHost, ix->stream));
       NQ_HIP(ix, hipStreamSynchronize(ix->stream));
@@ -451,27 +481,14 @@ int niqki_hits_from_counts(niqki_index *ix, const uint16_t *counts, uint32_t nq,
   if ((uint64_t)gid_begin + n_gids > stride) return fail(ix, NIQKI_E_INVALID, "gid range exceeds stride");
   if (ix->d.S > 15) return fail(ix, NIQKI_E_INVALID, "S = 16: u16 counters cannot hold a count of 2^16; use niqki_query");
   NQ_HIP(ix, hipSetDevice(ix->device));
-  if (mem == NIQKI_MEM_DEVICE)
-    return hits_dev(ix, counts, nq, stride, gid_begin, n_gids, (unsigned long long *)hit_off, hit_counts,
-                    hit_gids, capacity, false, nullptr);
+  HitOut out{(unsigned long long *)hit_off, hit_counts, hit_gids, capacity};
+  if (mem == NIQKI_MEM_DEVICE) return hits_dev(ix, counts, nullptr, nq, stride, gid_begin, n_gids, out);
   int rc;
-  if ((rc = ensure(ix, ix->ws_counts, std::max<size_t>((size_t)nq * stride * 2, 2)))) return rc;
-  if ((rc = ensure(ix, ix->ws_hitoff, (size_t)(nq + 1) * 8))) return rc;
-  if ((rc = ensure(ix, ix->ws_hc, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
-  if ((rc = ensure(ix, ix->ws_hg, (size_t)std::max<uint64_t>(capacity, 1) * 4))) return rc;
+  if ((rc = ensure(ix, ix->ws_counts, std::max<size_t>((size_t)nq * stride * 2, 2)))) return rc;   // (one plane: S <= 15)
+  if ((rc = hit_out_ws(ix, nq, capacity, out))) return rc;
   if (nq) NQ_HIP(ix, hipMemcpyAsync(ix->ws_counts.p, counts, (size_t)nq * stride * 2, hipMemcpyHostToDevice, ix->stream));
-  uint64_t total = 0;
-  rc = hits_dev(ix, (const uint16_t *)ix->ws_counts.p, nq, stride, gid_begin, n_gids,
-                (unsigned long long *)ix->ws_hitoff.p, (uint32_t *)ix->ws_hc.p, (uint32_t *)ix->ws_hg.p,
-                capacity, true, &total);
-  if (rc && rc != NIQKI_E_CAPACITY) return rc;
-  NQ_HIP(ix, hipMemcpyAsync(hit_off, ix->ws_hitoff.p, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, ix->stream));
-  if (rc == NIQKI_OK && total) {
-    NQ_HIP(ix, hipMemcpyAsync(hit_counts, ix->ws_hc.p, (size_t)total * 4, hipMemcpyDeviceToHost, ix->stream));
-    NQ_HIP(ix, hipMemcpyAsync(hit_gids, ix->ws_hg.p, (size_t)total * 4, hipMemcpyDeviceToHost, ix->stream));
-  }
-  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
-  return rc;
+  rc = hits_dev(ix, (const uint16_t *)ix->ws_counts.p, nullptr, nq, stride, gid_begin, n_gids, out);
+  return hits_to_host(ix, rc, out, nq, hit_off, hit_counts, hit_gids);
 }
 
 int niqki_candidates_from_counts(niqki_index *ix, const uint16_t *counts, uint32_t nq, uint64_t stride,
@@ -507,12 +524,12 @@ int niqki_query(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint64_t 
   const uint32_t N = ix->built_n;
   const uint64_t stride = NIQKI_ROW_STRIDE(N);
   if (mem == NIQKI_MEM_DEVICE) {
-    const size_t plane = std::max<size_t>((size_t)nq * stride * 2, 2);
-    if ((rc = ensure(ix, ix->ws_counts, plane * (two_planes(ix) ? 2 : 1)))) return rc;
-    uint16_t *c1 = (uint16_t *)ix->ws_counts.p, *c2 = two_planes(ix) ? (uint16_t *)((char *)ix->ws_counts.p + plane) : nullptr;
-    return query_hits_dev(ix, sketches, nq, c1, c2, stride, (unsigned long long *)hit_off, hit_counts, hit_gids, capacity, false, nullptr);
+    Planes pl;
+    HitOut out{(unsigned long long *)hit_off, hit_counts, hit_gids, capacity};
+    if ((rc = counter_planes(ix, nq, stride, pl))) return rc;
+    return query_hits_dev(ix, sketches, nq, pl, stride, out);
   }
-  return query_to_host(ix, sketches, false, nq, hit_off, hit_counts, hit_gids, capacity);
+  return query_to_host(ix, host_rows(ix, sketches), nq, query_rows_per_batch(ix), hit_off, hit_counts, hit_gids, capacity);
 }
 
 int niqki_query_sequences(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, uint32_t n_rec,
@@ -598,7 +615,7 @@ int niqki_query_ahead(niqki_index *ix, uint32_t *n_entry, uint64_t *hit_off, uin
     rc = niqki_query(ix, (const int32_t *)a.sk.p, a.n_entry, hit_off, hit_counts, hit_gids, capacity, NIQKI_MEM_DEVICE);
   } else {
     if ((rc = build_if_needed(ix))) return rc;
-    rc = query_to_host(ix, (const int32_t *)a.sk.p, true, a.n_entry, hit_off, hit_counts, hit_gids, capacity);
+    rc = query_to_host(ix, device_rows(ix, (const int32_t *)a.sk.p), a.n_entry, query_rows_per_batch(ix), hit_off, hit_counts, hit_gids, capacity);
   }
   if (rc == NIQKI_E_CAPACITY) return rc;   // the batch stays the oldest one: the same call again with larger arrays
   if (!rc && sketches && a.n_entry)
@@ -616,23 +633,11 @@ int niqki_matrix_range(niqki_index *ix, uint32_t begin, uint32_t end, uint16_t *
                        int mem) {
   if (!ix || begin > end || end > ix->n_genomes || (!counts && end > begin)) return NIQKI_E_INVALID;
   NQ_HIP(ix, hipSetDevice(ix->device));
-  // A paged index keeps its sketch store in page-locked host memory: the stored sketches of a batch are read
-  // from there by the device (zero-copy, 2 bytes per cell), the counters then come from the paged walk.
+  // (a paged index: the counters come from the paged walk)
   int rc = ix->resident_bytes ? NIQKI_OK : build_if_needed(ix);
   if (rc) return rc;
   const uint32_t n_all = ix->resident_bytes ? ix->n_genomes : ix->built_n;
   if (stride < n_all || (stride & 1)) return fail(ix, NIQKI_E_INVALID, "stride must be even and >= genome count");
-  nq::Derived d_full = ix->d;
-  const uint16_t *store_dev = ix->store;
-  uint64_t store_cap = ix->cap;
-  if (ix->resident_bytes) {
-    d_full.slot_begin = ix->full_begin;
-    d_full.slot_end = ix->full_end;
-    void *dp = nullptr;
-    NQ_HIP(ix, hipHostGetDevicePointer(&dp, ix->host_store, 0));
-    store_dev = (const uint16_t *)dp;
-    store_cap = ix->host_cap;
-  }
   // The bucket co-occurrence count of (a, t) equals the hit count of genome a
   // for the stored sketch of t: both count the slots where the two sketches
   // hold the same valid fingerprint.  So the range is answered by the gather
@@ -641,7 +646,7 @@ int niqki_matrix_range(niqki_index *ix, uint32_t begin, uint32_t end, uint16_t *
   for (uint32_t t0 = begin; t0 < end; t0 += qb) {
     const uint32_t n = std::min(qb, end - t0);
     if ((rc = ensure(ix, ix->ws_misc, (size_t)n * ix->d.F * 4))) return rc;
-    NQ_HIP(ix, nq::launch_store_read(d_full, store_dev, store_cap, t0, n, (int32_t *)ix->ws_misc.p, ix->stream));
+    if ((rc = stored_sketch_rows(ix, t0, n, (int32_t *)ix->ws_misc.p))) return rc;
     uint16_t *dst = counts + (size_t)(t0 - begin) * stride;
     if (mem == NIQKI_MEM_DEVICE) {
       uint16_t *c2 = nullptr;
@@ -653,13 +658,11 @@ int niqki_matrix_range(niqki_index *ix, uint32_t begin, uint32_t end, uint16_t *
       // uint16 counters whatever S (src/niqki_index.cpp:572): at S = 16 a count of 2^16 reads 0, as in the reference
       if (c2) NQ_HIP(ix, nq::launch_plane_add16(dst, c2, (uint64_t)n * stride, ix->stream));
     } else {
-      const size_t plane = (size_t)n * stride * 2;
-      if ((rc = ensure(ix, ix->ws_counts, plane * (two_planes(ix) ? 2 : 1)))) return rc;
-      NQ_HIP(ix, hipMemsetAsync(ix->ws_counts.p, 0, plane * (two_planes(ix) ? 2 : 1), ix->stream));
-      uint16_t *c2 = two_planes(ix) ? (uint16_t *)((char *)ix->ws_counts.p + plane) : nullptr;
-      if ((rc = counts_dev(ix, (const int32_t *)ix->ws_misc.p, ix->d.F, first_slot(ix), n, (uint16_t *)ix->ws_counts.p, stride, c2))) return rc;
-      if (c2) NQ_HIP(ix, nq::launch_plane_add16((uint16_t *)ix->ws_counts.p, c2, (uint64_t)n * stride, ix->stream));
-      NQ_HIP(ix, hipMemcpyAsync(dst, ix->ws_counts.p, (size_t)n * stride * 2, hipMemcpyDeviceToHost, ix->stream));
+      Planes pl;
+      if ((rc = counter_planes(ix, n, stride, pl, true))) return rc;
+      if ((rc = counts_dev(ix, (const int32_t *)ix->ws_misc.p, ix->d.F, first_slot(ix), n, pl.c1, stride, pl.c2))) return rc;
+      if (pl.c2) NQ_HIP(ix, nq::launch_plane_add16(pl.c1, pl.c2, (uint64_t)n * stride, ix->stream));
+      NQ_HIP(ix, hipMemcpyAsync(dst, pl.c1, (size_t)n * stride * 2, hipMemcpyDeviceToHost, ix->stream));
       NQ_HIP(ix, hipStreamSynchronize(ix->stream));
     }
   }

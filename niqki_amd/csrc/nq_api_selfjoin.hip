@@ -1,0 +1,262 @@
+// nq_api_selfjoin.hip -- the self-join of an index behind the C ABI: niqki_neighbors_range (the hits of the stored
+// sketches, the sparse form of Index::query_range, src/niqki_index.cpp:570-610), niqki_cluster (single-linkage
+// clusters: the link and flatten kernels over the hit lists of the stored sketches) and niqki_dereplicate (greedy
+// representatives in index order: the decide, assign and finish kernels over the same hit lists).  The kernels are in
+// nq_cluster.hip, the hit lists come from the query path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c.
+#include "nq_handle.h"
+
+#include <algorithm>
+#include <string>
+
+namespace nqi {
+
+bool whole_range(const niqki_index *ix) {
+  const uint32_t b = first_slot(ix), e = ix->resident_bytes ? ix->full_end : ix->d.slot_end;
+  return b == 0 && e == ix->d.F;
+}
+
+namespace {
+
+// The query path with the call's threshold and no top-k; the handle's own values come back whatever happens.
+struct CallThreshold {
+  niqki_index *ix;
+  const uint32_t ms, pms, k;
+  CallThreshold(niqki_index *ix_, uint32_t threshold) : ix(ix_), ms(ix_->d.min_score), pms(ix_->p.min_score), k(ix_->p.top_k) {
+    ix->d.min_score = threshold;
+    ix->p.min_score = threshold;
+    ix->p.top_k = 0;
+  }
+  ~CallThreshold() {
+    ix->d.min_score = ms;
+    ix->p.min_score = pms;
+    ix->p.top_k = k;
+  }
+};
+
+// One self-join with a consumer of the hit buffers: niqki_cluster (the link kernel) or niqki_dereplicate (decide +
+// assign).  The batches go in index order and a halved batch finishes its first half before its second: the
+// dereplication relies on that (a batch's earlier genomes are all decided), clustering does not care.
+struct SelfJoin {
+  niqki_index *ix;
+  const char *who;
+  SelfJoinStats &stats;
+  // phases of a batch the stats time (stats.ms): store read, gather + hits, then the consumer's: 3 or 4 in all
+  const int phases;
+  // Enqueues the consumer's kernels on the hits (off, hit_counts, hit_gids) of genomes [t0, t0 + n) and ends each of
+  // its phases k = 2 .. phases - 1 with mark(k + 1).
+  std::function<int(const unsigned long long *, const uint32_t *, const uint32_t *, uint32_t, uint32_t)> consume;
+  uint64_t stride = 0, room = 0;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // phase k lies between ev[k] and ev[k + 1]
+
+  SelfJoin(niqki_index *ix_, const char *who_, SelfJoinStats &stats_, int phases_) : ix(ix_), who(who_), stats(stats_), phases(phases_) {}
+  ~SelfJoin() {
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  int create_events() {   // (there are none unless the handle is profiling)
+    if (ix->prof) for (int k = 0; k <= phases; ++k) NQ_HIP(ix, hipEventCreate(&ev[k]));
+    return NIQKI_OK;
+  }
+  int mark(int k) {
+    if (ix->prof) NQ_HIP(ix, hipEventRecord(ev[k], ix->stream));
+    return NIQKI_OK;
+  }
+};
+
+// genomes [t0, t0 + n): hits at the threshold into the fixed hit buffers, then the consumer's kernels; a batch whose
+// hits exceed the room is halved.  The total is known only after the gather and the count, so a split loses that work:
+// the following batches start from the size that fitted and stay there (the batch size never grows back within a call).
+int self_join_batch(SelfJoin &r, uint32_t t0, uint32_t n, uint32_t *fitted) {
+  niqki_index *ix = r.ix;
+  int rc;
+  Planes pl;
+  HitOut out;
+  if ((rc = ensure(ix, ix->ws_misc, (size_t)n * ix->d.F * 4))) return rc;
+  if ((rc = counter_planes(ix, n, r.stride, pl))) return rc;
+  if ((rc = hit_out_ws(ix, n, r.room, out))) return rc;
+  if ((rc = r.mark(0))) return rc;
+  if ((rc = stored_sketch_rows(ix, t0, n, (int32_t *)ix->ws_misc.p))) return rc;
+  if ((rc = r.mark(1))) return rc;
+  rc = query_hits_dev(ix, (const int32_t *)ix->ws_misc.p, n, pl, r.stride, out);
+  if (rc == NIQKI_E_CAPACITY) {
+    if (n == 1) return fail(ix, NIQKI_E_STATE, std::string(r.who) + ": one query's hits exceed the genome count");   // (room >= N)
+    r.stats.splits += 1;
+    const uint32_t h = n / 2;
+    uint32_t f1 = 0, f2 = 0;
+    if ((rc = self_join_batch(r, t0, h, &f1))) return rc;
+    if ((rc = self_join_batch(r, t0 + h, n - h, &f2))) return rc;
+    *fitted = std::max(1u, std::min(f1, f2));
+    return NIQKI_OK;
+  }
+  if (rc) return rc;
+  if ((rc = r.mark(2))) return rc;
+  if ((rc = r.consume(out.off, out.counts, out.gids, t0, n))) return rc;
+  if (ix->prof) {
+    NQ_HIP(ix, hipEventSynchronize(r.ev[r.phases]));
+    for (int k = 0; k < r.phases; ++k) {
+      float ms = 0;
+      NQ_HIP(ix, hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
+      r.stats.ms[k] += ms;
+    }
+    r.stats.pairs += out.total;
+  }
+  *fitted = n;
+  return NIQKI_OK;
+}
+
+// the hit buffers, the events, then the batches of genomes [0, n_run) in index order
+int self_join_batches(SelfJoin &r, uint32_t n_run) {
+  niqki_index *ix = r.ix;
+  const uint32_t N = ix->n_genomes;
+  r.stride = NIQKI_ROW_STRIDE(N);
+  // hit_counts + hit_gids and the two scratch arrays of the same size the hit kernels order them in: 16 bytes a hit;
+  // never below N, the hits of one query
+  r.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
+  int rc = r.create_events();
+  uint32_t qb = std::max<uint32_t>(ix->query_batch, 1);
+  for (uint32_t t0 = 0; t0 < n_run && !rc;) {
+    const uint32_t n = std::min(qb, n_run - t0);
+    uint32_t fitted = n;
+    rc = self_join_batch(r, t0, n, &fitted);
+    if (fitted < n) qb = fitted;   // a split batch: do not gather the following ones twice
+    t0 += n;
+  }
+  return rc;
+}
+
+int cluster_run(niqki_index *ix, uint32_t *labels, uint32_t *n_clusters, int mem) {
+  const uint32_t N = ix->n_genomes;
+  int rc = build_if_needed(ix);
+  if (rc) return rc;
+  // parent[N], labels[N] (device copy of a host result), the root count
+  if ((rc = ensure(ix, ix->ws_parent, ((size_t)N * 2 + 1) * 4))) return rc;
+  uint32_t *parent = (uint32_t *)ix->ws_parent.p;
+  uint32_t *d_labels = mem == NIQKI_MEM_DEVICE ? labels : parent + N, *d_roots = parent + 2 * (size_t)N;
+  SelfJoin r(ix, "niqki_cluster", ix->cluster_stats, 3);
+  r.consume = [&](const unsigned long long *off, const uint32_t *, const uint32_t *hg, uint32_t t0, uint32_t n) {
+    NQ_HIP(ix, nq::launch_cluster_link(parent, N, off, hg, t0, n, ix->stream));
+    return r.mark(3);
+  };
+  NQ_HIP(ix, nq::launch_cluster_init(parent, N, ix->stream));
+  if ((rc = self_join_batches(r, N))) return rc;
+  if ((rc = r.mark(0))) return rc;
+  NQ_HIP(ix, nq::launch_cluster_flatten(parent, N, d_labels, d_roots, ix->stream));
+  if ((rc = r.mark(1))) return rc;
+  uint32_t roots = 0;
+  if (mem != NIQKI_MEM_DEVICE) NQ_HIP(ix, hipMemcpyAsync(labels, d_labels, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipMemcpyAsync(&roots, d_roots, 4, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  if (ix->prof) {
+    float ms = 0;
+    NQ_HIP(ix, hipEventElapsedTime(&ms, r.ev[0], r.ev[1]));
+    ix->cluster_stats.ms[3] = ms;
+  }
+  if (n_clusters) *n_clusters = roots;
+  return NIQKI_OK;
+}
+
+// threshold 0 links every pair, so genome 0 is the only representative: only ITS list is made (at min_score 0 it holds
+// every genome with its count), the other genomes start as covered
+int derep_run(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_reps, int mem) {
+  const uint32_t N = ix->n_genomes;
+  int rc = build_if_needed(ix);
+  if (rc) return rc;
+  // best[N] (8 bytes), labels[N] and label_counts[N] (device copies of host results), info[4], state[N]
+  const bool dev = mem == NIQKI_MEM_DEVICE;
+  if ((rc = ensure(ix, ix->ws_parent, (size_t)N * 17 + 16))) return rc;
+  unsigned long long *best = (unsigned long long *)ix->ws_parent.p;
+  uint32_t *own_labels = (uint32_t *)(best + N), *own_counts = own_labels + N;
+  uint32_t *info = own_counts + N;   // [0] rounds, [1] [2] flags of a batch's first two rounds, [3] the representative count
+  uint8_t *state = (uint8_t *)(info + 4);
+  uint32_t *d_labels = dev ? labels : own_labels, *d_counts = !label_counts ? nullptr : dev ? label_counts : own_counts;
+  SelfJoin r(ix, "niqki_dereplicate", ix->derep_stats, 4);
+  r.consume = [&](const unsigned long long *off, const uint32_t *hc, const uint32_t *hg, uint32_t t0, uint32_t n) {
+    NQ_HIP(ix, nq::launch_derep_decide(state, N, off, hg, t0, n, info, ix->stream));
+    int rc_ = r.mark(3);
+    if (rc_) return rc_;
+    NQ_HIP(ix, nq::launch_derep_assign(state, best, N, off, hc, hg, t0, n, ix->stream));
+    return r.mark(4);
+  };
+  NQ_HIP(ix, hipMemsetAsync(best, 0, (size_t)N * 8, ix->stream));
+  NQ_HIP(ix, hipMemsetAsync(info, 0, 16, ix->stream));
+  NQ_HIP(ix, hipMemsetAsync(state, threshold ? nq::kUndecided : nq::kCovered, N, ix->stream));
+  if (!threshold) NQ_HIP(ix, hipMemsetAsync(state, nq::kUndecided, 1, ix->stream));
+  if ((rc = self_join_batches(r, threshold ? N : 1))) return rc;
+  uint32_t out[4] = {0, 0, 0, 0};
+  NQ_HIP(ix, nq::launch_derep_finish(state, best, N, d_labels, d_counts, info + 3, ix->stream));
+  if (!dev) NQ_HIP(ix, hipMemcpyAsync(labels, d_labels, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream));
+  if (!dev && label_counts) NQ_HIP(ix, hipMemcpyAsync(label_counts, d_counts, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipMemcpyAsync(out, info, 16, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  ix->derep_stats.rounds = out[0];
+  if (n_reps) *n_reps = out[3];
+  return NIQKI_OK;
+}
+
+}  // namespace
+
+}  // namespace nqi
+
+using namespace nqi;
+
+extern "C" {
+
+int niqki_neighbors_range(niqki_index *ix, uint32_t begin, uint32_t end, uint64_t *hit_off, uint32_t *hit_counts,
+                          uint32_t *hit_gids, uint64_t capacity, int mem) {
+  if (!ix || !hit_off) return NIQKI_E_INVALID;
+  if (begin > end || end > ix->n_genomes) return fail(ix, NIQKI_E_INVALID, "genome range out of bounds");
+  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_neighbors_range: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  int rc = build_if_needed(ix);
+  if (rc) return rc;
+  const uint32_t nq = end - begin;
+  if (mem == NIQKI_MEM_DEVICE) {
+    const uint64_t stride = NIQKI_ROW_STRIDE(ix->built_n);
+    Planes pl;
+    HitOut out{(unsigned long long *)hit_off, hit_counts, hit_gids, capacity};
+    if ((rc = ensure(ix, ix->ws_misc, std::max<size_t>((size_t)nq * ix->d.F * 4, 4)))) return rc;
+    if ((rc = counter_planes(ix, nq, stride, pl))) return rc;
+    if ((rc = stored_sketch_rows(ix, begin, nq, (int32_t *)ix->ws_misc.p))) return rc;
+    return query_hits_dev(ix, (const int32_t *)ix->ws_misc.p, nq, pl, stride, out);
+  }
+  // batches of query_batch stored sketches through the host path of niqki_query
+  return query_to_host(ix, stored_rows(ix, begin), nq, std::max<uint32_t>(ix->query_batch, 1), hit_off, hit_counts, hit_gids, capacity);
+}
+
+int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *n_clusters, int mem) {
+  if (!ix || (!labels && ix->n_genomes)) return NIQKI_E_INVALID;
+  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_cluster: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  const uint32_t N = ix->n_genomes;
+  ix->cluster_stats = SelfJoinStats();
+  if (N == 0) {
+    if (n_clusters) *n_clusters = 0;
+    return NIQKI_OK;
+  }
+  if (threshold == 0) {   // every pair is linked
+    if (mem == NIQKI_MEM_DEVICE) {
+      NQ_HIP(ix, hipMemsetAsync(labels, 0, (size_t)N * 4, ix->stream));
+    } else {
+      std::fill(labels, labels + N, 0u);
+    }
+    if (n_clusters) *n_clusters = 1;
+    return NIQKI_OK;
+  }
+  CallThreshold guard(ix, threshold);
+  return cluster_run(ix, labels, n_clusters, mem);
+}
+
+int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_representatives,
+                      int mem) {
+  if (!ix || (!labels && ix->n_genomes)) return NIQKI_E_INVALID;
+  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_dereplicate: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  ix->derep_stats = SelfJoinStats();
+  if (ix->n_genomes == 0) {
+    if (n_representatives) *n_representatives = 0;
+    return NIQKI_OK;
+  }
+  CallThreshold guard(ix, threshold);
+  return derep_run(ix, threshold, labels, label_counts, n_representatives, mem);
+}
+
+}  // extern "C"

@@ -428,8 +428,8 @@ int niqki_staged_query(niqki_index *ix, uint64_t *hit_off, uint32_t *hit_counts,
     return niqki_query(ix, (const int32_t *)ix->ws_stsk.p, ix->staged.n_entry, hit_off, hit_counts, hit_gids,
                        capacity, NIQKI_MEM_DEVICE);
   if ((rc = build_if_needed(ix))) return rc;
-  return query_to_host(ix, (const int32_t *)ix->ws_stsk.p, true, ix->staged.n_entry, hit_off, hit_counts,
-                       hit_gids, capacity);
+  return query_to_host(ix, device_rows(ix, (const int32_t *)ix->ws_stsk.p), ix->staged.n_entry, query_rows_per_batch(ix), hit_off,
+                       hit_counts, hit_gids, capacity);
 }
 
 int niqki_staged_records(niqki_index *ix, uint64_t *rec_off, uint8_t *seqs, uint32_t *entry_rec,

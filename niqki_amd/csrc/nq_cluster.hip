@@ -152,7 +152,6 @@ __global__ void cluster_flatten_kernel(const uint32_t *parent, uint32_t n, uint3
 // word is hot.  A covered genome has at least one linked representative below it, so its best[] is set when the last
 // batch is through.
 
-enum : uint8_t { kUndecided = 0, kRep = 1, kCovered = 2 };
 constexpr uint32_t kFinisherBlock = 1024;
 
 // kFresh: state[] through agent-scope atomics (the finisher); otherwise plain loads of what earlier launches wrote
@@ -301,326 +300,3 @@ hipError_t launch_derep_finish(const uint8_t *state, const unsigned long long *b
 }
 
 }  // namespace nq
-
-namespace nqi {
-
-bool whole_range(const niqki_index *ix) {
-  const uint32_t b = first_slot(ix), e = ix->resident_bytes ? ix->full_end : ix->d.slot_end;
-  return b == 0 && e == ix->d.F;
-}
-
-// the stored sketches of genomes [t0, t0 + n) as query sketches in device memory: from the store, or -- paged handle --
-// zero-copy from the page-locked host store, as niqki_matrix_range reads them
-static int read_stored(niqki_index *ix, uint32_t t0, uint32_t n, int32_t *dst) {
-  if (!n) return NIQKI_OK;
-  if (!ix->resident_bytes) {
-    NQ_HIP(ix, nq::launch_store_read(ix->d, ix->store, ix->cap, t0, n, dst, ix->stream));
-    return NIQKI_OK;
-  }
-  nq::Derived d = ix->d;
-  d.slot_begin = ix->full_begin;
-  d.slot_end = ix->full_end;
-  void *dp = nullptr;
-  NQ_HIP(ix, hipHostGetDevicePointer(&dp, ix->host_store, 0));
-  NQ_HIP(ix, nq::launch_store_read(d, (const uint16_t *)dp, ix->host_cap, t0, n, dst, ix->stream));
-  return NIQKI_OK;
-}
-
-// counter planes of n query rows in ws_counts (the rows the hit-list form falls back on, or the rows themselves)
-static int count_rows(niqki_index *ix, uint32_t n, uint64_t stride, uint16_t **c1, uint16_t **c2) {
-  const size_t plane = std::max<size_t>((size_t)n * stride * 2, 2);
-  int rc = ensure(ix, ix->ws_counts, plane * (two_planes(ix) ? 2 : 1));
-  if (rc) return rc;
-  *c1 = (uint16_t *)ix->ws_counts.p;
-  *c2 = two_planes(ix) ? (uint16_t *)((char *)ix->ws_counts.p + plane) : nullptr;
-  return NIQKI_OK;
-}
-
-namespace {
-
-// One self-join with a consumer of the hit buffers: niqki_cluster (the link kernel) or niqki_dereplicate (decide +
-// assign).  The batches go in index order and a halved batch finishes its first half before its second: the
-// dereplication relies on that (a batch's earlier genomes are all decided), clustering does not care.
-struct SelfJoin {
-  niqki_index *ix;
-  const char *who;
-  bool derep;
-  uint64_t stride, room;
-  uint32_t *parent = nullptr;               // niqki_cluster
-  uint8_t *state = nullptr;                 // niqki_dereplicate ...
-  unsigned long long *best = nullptr;
-  uint32_t *info = nullptr;
-  uint64_t *splits, *pairs;                 // the call's stats
-  double *ms;                               // read, gather + hits, then the consumer's phases
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-};
-
-// genomes [t0, t0 + n): hits at the threshold into the fixed hit buffers, then the consumer's kernels; a batch whose
-// hits exceed the room is halved.  The total is known only after the gather and the count, so a split loses that work:
-// the following batches start from the size that fitted and stay there (the batch size never grows back within a call).
-int self_join_batch(SelfJoin &r, uint32_t t0, uint32_t n, uint32_t *fitted) {
-  niqki_index *ix = r.ix;
-  int rc;
-  uint16_t *c1, *c2;
-  if ((rc = ensure(ix, ix->ws_misc, (size_t)n * ix->d.F * 4))) return rc;
-  if ((rc = count_rows(ix, n, r.stride, &c1, &c2))) return rc;
-  if ((rc = ensure(ix, ix->ws_hitoff, (size_t)(n + 1) * 8))) return rc;
-  if (ix->prof) NQ_HIP(ix, hipEventRecord(r.ev[0], ix->stream));
-  if ((rc = read_stored(ix, t0, n, (int32_t *)ix->ws_misc.p))) return rc;
-  if (ix->prof) NQ_HIP(ix, hipEventRecord(r.ev[1], ix->stream));
-  uint64_t total = 0;
-  rc = query_hits_dev(ix, (const int32_t *)ix->ws_misc.p, n, c1, c2, r.stride, (unsigned long long *)ix->ws_hitoff.p,
-                      (uint32_t *)ix->ws_hc.p, (uint32_t *)ix->ws_hg.p, r.room, true, &total);
-  if (rc == NIQKI_E_CAPACITY) {
-    if (n == 1) return fail(ix, NIQKI_E_STATE, std::string(r.who) + ": one query's hits exceed the genome count");   // (room >= N)
-    *r.splits += 1;
-    const uint32_t h = n / 2;
-    uint32_t f1 = 0, f2 = 0;
-    if ((rc = self_join_batch(r, t0, h, &f1))) return rc;
-    if ((rc = self_join_batch(r, t0 + h, n - h, &f2))) return rc;
-    *fitted = std::max(1u, std::min(f1, f2));
-    return NIQKI_OK;
-  }
-  if (rc) return rc;
-  if (ix->prof) NQ_HIP(ix, hipEventRecord(r.ev[2], ix->stream));
-  const unsigned long long *off = (const unsigned long long *)ix->ws_hitoff.p;
-  const uint32_t *hc = (const uint32_t *)ix->ws_hc.p, *hg = (const uint32_t *)ix->ws_hg.p;
-  int last = 3;
-  if (!r.derep) {
-    NQ_HIP(ix, nq::launch_cluster_link(r.parent, ix->n_genomes, off, hg, t0, n, ix->stream));
-  } else {
-    NQ_HIP(ix, nq::launch_derep_decide(r.state, ix->n_genomes, off, hg, t0, n, r.info, ix->stream));
-    if (ix->prof) NQ_HIP(ix, hipEventRecord(r.ev[3], ix->stream));
-    NQ_HIP(ix, nq::launch_derep_assign(r.state, r.best, ix->n_genomes, off, hc, hg, t0, n, ix->stream));
-    last = 4;
-  }
-  if (ix->prof) {
-    NQ_HIP(ix, hipEventRecord(r.ev[last], ix->stream));
-    NQ_HIP(ix, hipEventSynchronize(r.ev[last]));
-    for (int k = 0; k < last; ++k) {
-      float ms = 0;
-      NQ_HIP(ix, hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
-      r.ms[k] += ms;
-    }
-    *r.pairs += total;
-  }
-  *fitted = n;
-  return NIQKI_OK;
-}
-
-// the hit buffers, the events, then the batches of genomes [0, n_run) in index order
-int self_join_batches(SelfJoin &r, uint32_t n_run) {
-  niqki_index *ix = r.ix;
-  const uint32_t N = ix->n_genomes;
-  r.stride = NIQKI_ROW_STRIDE(N);
-  // hit_counts + hit_gids and the two scratch arrays of the same size the hit kernels order them in: 16 bytes a hit;
-  // never below N, the hits of one query
-  r.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
-  int rc;
-  if ((rc = ensure(ix, ix->ws_hc, (size_t)r.room * 4))) return rc;
-  if ((rc = ensure(ix, ix->ws_hg, (size_t)r.room * 4))) return rc;
-  uint32_t qb = std::max<uint32_t>(ix->query_batch, 1);
-  for (uint32_t t0 = 0; t0 < n_run && !rc;) {
-    const uint32_t n = std::min(qb, n_run - t0);
-    uint32_t fitted = n;
-    rc = self_join_batch(r, t0, n, &fitted);
-    if (fitted < n) qb = fitted;   // a split batch: do not gather the following ones twice
-    t0 += n;
-  }
-  return rc;
-}
-
-int cluster_run(niqki_index *ix, uint32_t *labels, uint32_t *n_clusters, int mem) {
-  const uint32_t N = ix->n_genomes;
-  int rc = build_if_needed(ix);
-  if (rc) return rc;
-  SelfJoin r;
-  r.ix = ix;
-  r.who = "niqki_cluster";
-  r.derep = false;
-  r.splits = &ix->cluster_splits;
-  r.pairs = &ix->cluster_pairs;
-  r.ms = ix->cluster_ms;
-  // parent[N], labels[N] (device copy of a host result), the root count
-  if ((rc = ensure(ix, ix->ws_parent, ((size_t)N * 2 + 1) * 4))) return rc;
-  r.parent = (uint32_t *)ix->ws_parent.p;
-  uint32_t *d_labels = mem == NIQKI_MEM_DEVICE ? labels : r.parent + N, *d_roots = r.parent + 2 * (size_t)N;
-  hipError_t e0 = hipSuccess;   // (no early return from here on: the events are destroyed below)
-  if (ix->prof) for (int k = 0; k < 4; ++k) if (e0 == hipSuccess) e0 = hipEventCreate(&r.ev[k]);
-  if (e0 == hipSuccess) e0 = nq::launch_cluster_init(r.parent, N, ix->stream);
-  if (e0 != hipSuccess) rc = fail(ix, NIQKI_E_HIP, std::string("niqki_cluster: ") + hipGetErrorString(e0));
-  if (!rc) rc = self_join_batches(r, N);
-  if (!rc) {
-    hipError_t e = hipSuccess;
-    if (ix->prof) e = hipEventRecord(r.ev[0], ix->stream);
-    if (e == hipSuccess) e = nq::launch_cluster_flatten(r.parent, N, d_labels, d_roots, ix->stream);
-    if (e == hipSuccess && ix->prof) e = hipEventRecord(r.ev[1], ix->stream);
-    uint32_t roots = 0;
-    if (e == hipSuccess && mem != NIQKI_MEM_DEVICE) e = hipMemcpyAsync(labels, d_labels, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&roots, d_roots, 4, hipMemcpyDeviceToHost, ix->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-    if (e == hipSuccess && ix->prof) {
-      float ms = 0;
-      e = hipEventElapsedTime(&ms, r.ev[0], r.ev[1]);
-      ix->cluster_ms[3] = ms;
-    }
-    if (e != hipSuccess) rc = fail(ix, NIQKI_E_HIP, std::string("niqki_cluster: ") + hipGetErrorString(e));
-    else if (n_clusters) *n_clusters = roots;
-  }
-  for (auto &e : r.ev) if (e) (void)hipEventDestroy(e);
-  return rc;
-}
-
-// threshold 0 links every pair, so genome 0 is the only representative: only ITS list is made (at min_score 0 it holds
-// every genome with its count), the other genomes start as covered
-int derep_run(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_reps, int mem) {
-  const uint32_t N = ix->n_genomes;
-  int rc = build_if_needed(ix);
-  if (rc) return rc;
-  SelfJoin r;
-  r.ix = ix;
-  r.who = "niqki_dereplicate";
-  r.derep = true;
-  r.splits = &ix->derep_splits;
-  r.pairs = &ix->derep_pairs;
-  r.ms = ix->derep_ms;
-  // best[N] (8 bytes), labels[N] and label_counts[N] (device copies of host results), info[4], state[N]
-  const bool dev = mem == NIQKI_MEM_DEVICE;
-  if ((rc = ensure(ix, ix->ws_parent, (size_t)N * 17 + 16))) return rc;
-  r.best = (unsigned long long *)ix->ws_parent.p;
-  uint32_t *own_labels = (uint32_t *)(r.best + N), *own_counts = own_labels + N;
-  r.info = own_counts + N;   // [0] rounds, [1] [2] flags of a batch's first two rounds, [3] the representative count
-  r.state = (uint8_t *)(r.info + 4);
-  uint32_t *d_labels = dev ? labels : own_labels, *d_counts = !label_counts ? nullptr : dev ? label_counts : own_counts;
-  hipError_t e = hipSuccess;   // (no early return from here on: the events are destroyed below)
-  if (ix->prof) for (auto &v : r.ev) if (e == hipSuccess) e = hipEventCreate(&v);
-  if (e == hipSuccess) e = hipMemsetAsync(r.best, 0, (size_t)N * 8, ix->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(r.info, 0, 16, ix->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(r.state, threshold ? nq::kUndecided : nq::kCovered, N, ix->stream);
-  if (e == hipSuccess && !threshold) e = hipMemsetAsync(r.state, nq::kUndecided, 1, ix->stream);
-  if (e != hipSuccess) rc = fail(ix, NIQKI_E_HIP, std::string("niqki_dereplicate: ") + hipGetErrorString(e));
-  if (!rc) rc = self_join_batches(r, threshold ? N : 1);
-  if (!rc) {
-    uint32_t out[4] = {0, 0, 0, 0};
-    e = nq::launch_derep_finish(r.state, r.best, N, d_labels, d_counts, r.info + 3, ix->stream);
-    if (e == hipSuccess && !dev) e = hipMemcpyAsync(labels, d_labels, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream);
-    if (e == hipSuccess && !dev && label_counts) e = hipMemcpyAsync(label_counts, d_counts, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, r.info, 16, hipMemcpyDeviceToHost, ix->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-    if (e != hipSuccess) rc = fail(ix, NIQKI_E_HIP, std::string("niqki_dereplicate: ") + hipGetErrorString(e));
-    else {
-      ix->derep_rounds = out[0];
-      if (n_reps) *n_reps = out[3];
-    }
-  }
-  for (auto &v : r.ev) if (v) (void)hipEventDestroy(v);
-  return rc;
-}
-
-}  // namespace
-
-}  // namespace nqi
-
-using namespace nqi;
-
-extern "C" {
-
-int niqki_neighbors_range(niqki_index *ix, uint32_t begin, uint32_t end, uint64_t *hit_off, uint32_t *hit_counts,
-                          uint32_t *hit_gids, uint64_t capacity, int mem) {
-  if (!ix || !hit_off) return NIQKI_E_INVALID;
-  if (begin > end || end > ix->n_genomes) return fail(ix, NIQKI_E_INVALID, "genome range out of bounds");
-  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_neighbors_range: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
-  NQ_HIP(ix, hipSetDevice(ix->device));
-  int rc = build_if_needed(ix);
-  if (rc) return rc;
-  const uint32_t nq = end - begin, N = ix->built_n;
-  const uint64_t stride = NIQKI_ROW_STRIDE(N);
-  if (mem == NIQKI_MEM_DEVICE) {
-    uint16_t *c1, *c2;
-    if ((rc = ensure(ix, ix->ws_misc, std::max<size_t>((size_t)nq * ix->d.F * 4, 4)))) return rc;
-    if ((rc = count_rows(ix, nq, stride, &c1, &c2))) return rc;
-    if ((rc = read_stored(ix, begin, nq, (int32_t *)ix->ws_misc.p))) return rc;
-    return query_hits_dev(ix, (const int32_t *)ix->ws_misc.p, nq, c1, c2, stride, (unsigned long long *)hit_off, hit_counts,
-                          hit_gids, capacity, false, nullptr);
-  }
-  // batches of query_batch stored sketches through the host path of niqki_query; hit_off is made of the batches'
-  // own offsets, which stay true totals beyond the capacity
-  const uint32_t qb = std::max<uint32_t>(ix->query_batch, 1);
-  uint64_t base = 0;
-  bool overflow = false;
-  hit_off[0] = 0;
-  for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
-    const uint32_t n = std::min(qb, nq - q0);
-    if ((rc = ensure(ix, ix->ws_misc, (size_t)n * ix->d.F * 4))) return rc;
-    if ((rc = read_stored(ix, begin + q0, n, (int32_t *)ix->ws_misc.p))) return rc;
-    const bool room = !overflow && base <= capacity;
-    rc = query_to_host(ix, (const int32_t *)ix->ws_misc.p, true, n, hit_off + q0, room ? hit_counts + base : nullptr,
-                       room ? hit_gids + base : nullptr, room ? capacity - base : 0);
-    if (rc == NIQKI_E_CAPACITY) overflow = true;
-    else if (rc) return rc;
-    for (uint32_t i = 1; i <= n; ++i) hit_off[q0 + i] += base;
-    hit_off[q0] = base;
-    base = hit_off[q0 + n];
-  }
-  return overflow ? NIQKI_E_CAPACITY : NIQKI_OK;
-}
-
-int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *n_clusters, int mem) {
-  if (!ix || (!labels && ix->n_genomes)) return NIQKI_E_INVALID;
-  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_cluster: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
-  NQ_HIP(ix, hipSetDevice(ix->device));
-  const uint32_t N = ix->n_genomes;
-  ix->cluster_splits = 0;
-  ix->cluster_pairs = 0;
-  for (double &m : ix->cluster_ms) m = 0;
-  if (N == 0) {
-    if (n_clusters) *n_clusters = 0;
-    return NIQKI_OK;
-  }
-  if (threshold == 0) {   // every pair is linked
-    if (mem == NIQKI_MEM_DEVICE) {
-      NQ_HIP(ix, hipMemsetAsync(labels, 0, (size_t)N * 4, ix->stream));
-    } else {
-      std::fill(labels, labels + N, 0u);
-    }
-    if (n_clusters) *n_clusters = 1;
-    return NIQKI_OK;
-  }
-  // the query path with the call's threshold and no top-k; the handle's own values come back whatever happens
-  const uint32_t ms = ix->d.min_score, pms = ix->p.min_score, k = ix->p.top_k;
-  ix->d.min_score = threshold;
-  ix->p.min_score = threshold;
-  ix->p.top_k = 0;
-  const int rc = cluster_run(ix, labels, n_clusters, mem);
-  ix->d.min_score = ms;
-  ix->p.min_score = pms;
-  ix->p.top_k = k;
-  return rc;
-}
-
-int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_representatives,
-                      int mem) {
-  if (!ix || (!labels && ix->n_genomes)) return NIQKI_E_INVALID;
-  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_dereplicate: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
-  NQ_HIP(ix, hipSetDevice(ix->device));
-  ix->derep_rounds = 0;
-  ix->derep_splits = 0;
-  ix->derep_pairs = 0;
-  for (double &m : ix->derep_ms) m = 0;
-  if (ix->n_genomes == 0) {
-    if (n_representatives) *n_representatives = 0;
-    return NIQKI_OK;
-  }
-  // the query path with the call's threshold and no top-k; the handle's own values come back whatever happens
-  const uint32_t ms = ix->d.min_score, pms = ix->p.min_score, k = ix->p.top_k;
-  ix->d.min_score = threshold;
-  ix->p.min_score = threshold;
-  ix->p.top_k = 0;
-  const int rc = derep_run(ix, threshold, labels, label_counts, n_representatives, mem);
-  ix->d.min_score = ms;
-  ix->p.min_score = pms;
-  ix->p.top_k = k;
-  return rc;
-}
-
-}  // extern "C"

@@ -1343,16 +1343,14 @@ int run_hits(niqki_group *g, uint32_t per, uint32_t N, uint64_t stride) {
     NQ_GH(g, hipSetDevice(ix->device));
     auto &w = g->ws[l];
     const uint16_t *plane2 = g->wide ? (const uint16_t *)w.red.p + std::max<size_t>((size_t)per * stride, 2) : nullptr;
-    if (!pd.host) {
-      NQ_G(g, l, nqi::hits_dev(ix, (const uint16_t *)w.red.p, per, stride, 0, N, (unsigned long long *)pd.hit_off[l], pd.hit_counts[l],
-                               pd.hit_gids[l], pd.capacity, false, nullptr, plane2));
-      continue;
+    nqi::HitOut out{(unsigned long long *)pd.hit_off[l], pd.hit_counts[l], pd.hit_gids[l], pd.capacity};
+    if (pd.host) {   // (the caller's arrays are host memory)
+      NQ_G(g, l, nqi::ensure(ix, w.hitoff, (size_t)(per + 1) * 8));
+      NQ_G(g, l, nqi::ensure(ix, w.hc, (size_t)std::max<uint64_t>(pd.capacity, 1) * 4));
+      NQ_G(g, l, nqi::ensure(ix, w.hg, (size_t)std::max<uint64_t>(pd.capacity, 1) * 4));
+      out = nqi::HitOut{(unsigned long long *)w.hitoff.p, (uint32_t *)w.hc.p, (uint32_t *)w.hg.p, pd.capacity};
     }
-    NQ_G(g, l, nqi::ensure(ix, w.hitoff, (size_t)(per + 1) * 8));
-    NQ_G(g, l, nqi::ensure(ix, w.hc, (size_t)std::max<uint64_t>(pd.capacity, 1) * 4));
-    NQ_G(g, l, nqi::ensure(ix, w.hg, (size_t)std::max<uint64_t>(pd.capacity, 1) * 4));
-    NQ_G(g, l, nqi::hits_dev(ix, (const uint16_t *)w.red.p, per, stride, 0, N, (unsigned long long *)w.hitoff.p, (uint32_t *)w.hc.p,
-                             (uint32_t *)w.hg.p, pd.capacity, false, nullptr, plane2));
+    NQ_G(g, l, nqi::hits_dev(ix, (const uint16_t *)w.red.p, plane2, per, stride, 0, N, out));
   }
   return NIQKI_OK;
 }

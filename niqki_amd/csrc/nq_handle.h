@@ -6,6 +6,7 @@
 #include "../../include/niqki_hip_bench.h"
 #include "nq_kernels.h"
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,14 @@ struct Buf {
 struct ProfSpan {
   int kc;
   hipEvent_t a, b;
+};
+
+// what niqki_get_stat reports of a self-join call (nq_api_selfjoin.hip)
+struct SelfJoinStats {
+  uint64_t splits = 0;   // batches the call had to halve
+  uint64_t pairs = 0;    // the hits its kernels went through (while profiling is on)
+  uint64_t rounds = 0;   // niqki_dereplicate: most decide rounds of a batch
+  double ms[4] = {0, 0, 0, 0};
 };
 
 void shared_free(struct ::niqki_index *ix);   // nq_shared.hip
@@ -104,13 +113,10 @@ struct niqki_index {
   int hit_lists = 1;             // option: queries of a single small tile leave the gather kernel as ordered hit lists (no counter rows)
   uint32_t hit_list_cap = 256;   // option: hits per query such a list holds; a query with more goes through its counter row
   uint32_t last_hits_form = 0;   // stat "last_hits_form": 1 = the last query call took the hit-list form
-  uint32_t cluster_ws_mib = 1024;   // option "cluster_ws_mib": device hit buffers of a niqki_cluster batch (nq_cluster.hip)
-  uint64_t cluster_splits = 0;      // stat "cluster_splits": batches the last niqki_cluster call had to halve
-  double cluster_ms[4] = {0, 0, 0, 0};   // the last niqki_cluster call, while profiling is on: store read, gather + hits, link, flatten
-  uint64_t cluster_pairs = 0;       // ... and the hits its link kernel went through
-  uint64_t derep_rounds = 0, derep_splits = 0;   // stats of the last niqki_dereplicate call: most decide rounds of a batch, halved batches
-  double derep_ms[4] = {0, 0, 0, 0};   // ... while profiling is on: store read, gather + hits, decide, assign
-  uint64_t derep_pairs = 0;         // ... and the hits its kernels went through
+  uint32_t cluster_ws_mib = 1024;   // option "cluster_ws_mib": device hit buffers of a niqki_cluster batch (nq_api_selfjoin.hip)
+  // the last niqki_cluster / niqki_dereplicate call (stats "cluster_*", "derep_*").  ms, while profiling is on: store
+  // read, gather + hits, then link and flatten (cluster) or decide and assign (derep)
+  nqi::SelfJoinStats cluster_stats, derep_stats;
 
   nqi::Buf ws_seq, ws_recoff, ws_entry, ws_sk, ws_counts, ws_blk, ws_hitoff, ws_hc, ws_hg, ws_tc, ws_tg,
       ws_misc, ws_stash, ws_hl, ws_parent;
@@ -187,26 +193,54 @@ void swap_segment(niqki_index *ix);   // flat index members <-> alt ("Delta segm
 int build_range(niqki_index *ix, uint32_t g_base, uint32_t N);
 int build_if_needed(niqki_index *ix);
 int build_single(niqki_index *ix);    // ONE index over all genomes (dump export, per-bucket statistics)
+// the stored sketches of genomes [t0, t0 + n) as device query rows (resident store, or zero-copy from the paged host store)
+int stored_sketch_rows(niqki_index *ix, uint32_t t0, uint32_t n, int32_t *dst);
 // ---- nq_api_query.hip: counters and hits ----
 uint32_t page_slots(const niqki_index *ix);
 int load_page(niqki_index *ix, uint32_t s0, uint32_t s1);
 int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride, uint32_t q_off, uint32_t nq, uint16_t *counts,
                     uint64_t stride, bool accumulate, uint16_t *counts2 = nullptr, const nq::CandOut *co = nullptr);
-int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint16_t *c1, uint16_t *c2, uint64_t stride,
-                   unsigned long long *hit_off, uint32_t *hc, uint32_t *hg, uint64_t capacity, bool check_capacity,
-                   uint64_t *total_out);
-int query_to_host(niqki_index *ix, const int32_t *sketches, bool sk_dev, uint32_t nq, uint64_t *hit_off, uint32_t *hit_counts,
-                  uint32_t *hit_gids, uint64_t capacity);
-// the handle counts whole sketches (no slot-range shard): what the self-join calls need (nq_cluster.hip)
-bool whole_range(const niqki_index *ix);
 // hit counters of nq device-resident sketches (rows q_stride apart, this shard's slots at q_off)
 // counts2: the second counter plane of a whole-range S = 16 handle (nq_kernels.h, kPassSlots), else nullptr
 // co: also the candidate lists of the rows (nq_kernels.h CandOut; presets them itself), not on paged or S = 16 handles
 int counts_dev(niqki_index *ix, const int32_t *sketches, uint32_t q_stride, uint32_t q_off, uint32_t nq,
                uint16_t *counts, uint64_t stride, uint16_t *counts2 = nullptr, const nq::CandOut *co = nullptr);
-int hits_dev(niqki_index *ix, const uint16_t *counts, uint32_t nq, uint64_t stride, uint32_t gid_begin,
-             uint32_t n_gids, unsigned long long *hit_off, uint32_t *hc, uint32_t *hg, uint64_t capacity,
-             bool check_capacity, uint64_t *total_out, const uint16_t *counts2 = nullptr);
+// The counter planes of n query rows in ws_counts: one, or two on a two-plane handle (c2 is null otherwise).
+struct Planes {
+  uint16_t *c1 = nullptr, *c2 = nullptr;
+};
+int counter_planes(niqki_index *ix, uint32_t n, uint64_t stride, Planes &pl, bool zeroed = false);
+// Where the hits of a step go, in device memory: off (n + 1 offsets, off[n] = the total), then `capacity` places for
+// counts and gids.  check: read the total back (a synchronise) into `total` and return NIQKI_E_CAPACITY, with nothing
+// written to counts / gids, where it exceeds the capacity; without it more hits than `capacity` are the caller's error.
+struct HitOut {
+  unsigned long long *off = nullptr;
+  uint32_t *counts = nullptr, *gids = nullptr;
+  uint64_t capacity = 0;
+  bool check = false;
+  uint64_t total = 0;   // out, with check
+};
+// ... in the handle's own buffers (ws_hitoff, ws_hc, ws_hg) for n queries and `capacity` hits, checked
+int hit_out_ws(niqki_index *ix, uint32_t n, uint64_t capacity, HitOut &out);
+// off[0..n] of a checked step (rc: what it returned) and, where it fitted, its hits to host memory; synchronises.
+// Returns rc.
+int hits_to_host(niqki_index *ix, int rc, const HitOut &out, uint32_t n, void *hit_off, uint32_t *hit_counts, uint32_t *hit_gids);
+// threshold + order of nq counter rows (counts2: the second plane or null) over genomes [gid_begin, gid_begin + n_gids)
+int hits_dev(niqki_index *ix, const uint16_t *counts, const uint16_t *counts2, uint32_t nq, uint64_t stride, uint32_t gid_begin,
+             uint32_t n_gids, HitOut &out);
+int query_hits_dev(niqki_index *ix, const int32_t *sketches, uint32_t nq, const Planes &pl, uint64_t stride, HitOut &out);
+// Hits of nq queries into HOST arrays, batches of qb queries, hits appended in query order.  src makes the sketches of
+// queries [q0, q0 + n) device-resident whole rows and names them in *d_sk.
+using SketchSource = std::function<int(uint32_t q0, uint32_t n, const int32_t **d_sk)>;
+SketchSource host_rows(niqki_index *ix, const int32_t *sketches);      // through ws_sk
+SketchSource device_rows(niqki_index *ix, const int32_t *sketches);
+SketchSource stored_rows(niqki_index *ix, uint32_t begin);             // genomes from `begin` on, through ws_misc
+uint32_t query_rows_per_batch(const niqki_index *ix);   // option "query_batch", or more where no counter rows are written
+int query_to_host(niqki_index *ix, const SketchSource &src, uint32_t nq, uint32_t qb, uint64_t *hit_off, uint32_t *hit_counts,
+                  uint32_t *hit_gids, uint64_t capacity);
+// ---- nq_api_selfjoin.hip ----
+// the handle counts whole sketches (no slot-range shard): what the self-join calls need
+bool whole_range(const niqki_index *ix);
 // sketches of the handle's staged batch (niqki_stage_raw) into ix->ws_stsk, once per batch
 int staged_sketch_ws(niqki_index *ix);
 // appends n device-resident sketches (same addressing as counts_dev) to the sketch store

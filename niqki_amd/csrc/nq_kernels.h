@@ -133,7 +133,7 @@ hipError_t launch_import(const Derived &d, const uint32_t *words, const uint64_t
                          uint16_t *store, uint64_t cap, uint32_t n_genomes, uint32_t *bad,
                          uint32_t s0, uint32_t n_slots, hipStream_t stream);
 
-// ---- query (nq_query.hip) ----------------------------------------------------
+// ---- query: counters (nq_gather.hip) ------------------------------------------
 // gather-histogram: counts[q*stride + g] for all genomes (u16), one workgroup
 // per (query, tile).
 // stash: nq x (n_tiles-1) x f_local Entry scratch (unused for n_tiles == 1)
@@ -185,10 +185,10 @@ hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t n
                          uint16_t *counts, uint16_t *counts2, uint64_t stride, Entry *stash, const uint32_t *order,
                          int variant, bool pre, hipStream_t stream, const CandOut &co = CandOut());
 // out[i] = a[i] + b[i]: as u16 with wrap-around (the reference's uint16 matrix counters, src/niqki_index.cpp:572)
-// or as u32
+// or as u32 (the two planes of a launch_gather above; the kernels are in nq_hits.hip)
 hipError_t launch_plane_add16(uint16_t *a, const uint16_t *b, uint64_t n, hipStream_t stream);
 hipError_t launch_plane_sum32(const uint16_t *a, const uint16_t *b, uint32_t *out, uint64_t n, hipStream_t stream);
-// Slot-major look-up pre-pass for the queries of a launch (nq_query.hip): fills
+// Slot-major look-up pre-pass for the queries of a launch (nq_gather.hip): fills
 // pre[q][tile][slot] (lookup_pre_bytes of scratch) from the table streamed once.
 bool launch_lookup_usable(const IndexView &v);
 // The pre-pass reads a packed copy of the table (4 bytes per entry) where its row-staging kernel applies
@@ -204,6 +204,7 @@ hipError_t launch_order(const IndexView &v, const int32_t *sketches, uint32_t nq
 hipError_t launch_gathered(const IndexView &v, const int32_t *sketches, uint32_t nq,
                            unsigned long long *per_query, hipStream_t stream);
 
+// ---- query: hits (nq_hits.hip) -------------------------------------------------
 // threshold + compaction + order.  blk_counts: nq x n_blk scratch;
 // hit_off nq+1 (u64); tmp_*: capacity-sized scratch for the sort.
 struct HitsArgs {
@@ -256,7 +257,8 @@ hipError_t launch_cluster_link(uint32_t *parent, uint32_t n, const unsigned long
 hipError_t launch_cluster_flatten(const uint32_t *parent, uint32_t n, uint32_t *labels, uint32_t *n_roots, hipStream_t stream);
 
 // ---- greedy representatives (nq_cluster.hip) -------------------------------------
-// state[g]: 0 undecided, 1 representative, 2 covered.  Decides the queries t0 + q, q < nq, of a batch whose hit lists
+enum : uint8_t { kUndecided = 0, kRep = 1, kCovered = 2 };   // state[g]; the caller presets it
+// Decides the queries t0 + q, q < nq, of a batch whose hit lists
 // are (hit_off, hit_gids) and whose earlier genomes are all decided: two launches over the batch, then one workgroup
 // that runs the remaining rounds.  info: 4 words, zeroed once per call; info[0] = the most rounds a batch needed.
 hipError_t launch_derep_decide(uint8_t *state, uint32_t n, const unsigned long long *hit_off, const uint32_t *hit_gids, uint32_t t0,

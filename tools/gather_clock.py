@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a gather workgroup's time goes (measurement build: make -C niqki_amd/csrc HIPFLAGS+=-DNQ_GATHER_CLOCK,
-which adds a 100 MHz clock read of thread 0 at the phase boundaries of nq::gather_kernel).  Runs bench.py with the
+which adds a 100 MHz clock read of thread 0 at the phase boundaries of nq::gather_kernel, nq_gather.hip).  Runs bench.py with the
 given arguments, then condenses the clocks of the last gather launch: mean microseconds per phase, and per CU
 the idle gap between one workgroup's end and the next one's start.
   python tools/gather_clock.py --shard-of 8 --no-cpu --no-extra --steps 3"""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a SHORT-READ gather workgroup's time goes: tools/bench_reads4.py under a measurement build of the library
-(nq_query.hip compiled with -DNQ_GATHER_CLOCK, linked into tools/bin/libniqki_hip_clk.so, named by NIQKI_EXP_LIB: a
+(nq_gather.hip compiled with -DNQ_GATHER_CLOCK, linked into tools/bin/libniqki_hip_clk.so, named by NIQKI_EXP_LIB: a
 100 MHz clock read of thread 0 at the phase boundaries of nq::gather_kernel).  Condenses the clocks of the LAST gather
 launch (65 536 one-read workgroups): mean microseconds per phase.
     NIQKI_EXP_LIB=tools/bin/libniqki_hip_clk.so python tools/gather_clock_reads.py --reads 262144"""

@@ -56,7 +56,7 @@ NIQKI_FORCE_DIST=1 timeout -k 10 600 python3 bench.py --full --no-cpu --no-extra
 bash tools/profile_reads4.sh ${TAG} > /dev/null 2>&1
 timeout -k 10 600 python3 bench.py --full --genomes 500000 --no-legs --steps 6 --warmup 2 > $RES/${TAG}_bench_500k_genomes.json 2> $RES/${TAG}_bench_500k.err
 # LAST (it rebuilds the library of this scratch copy with clock reads in the gather kernel): phase clocks of a gather workgroup
-touch niqki_amd/csrc/nq_query.hip && make -C niqki_amd/csrc HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DNQ_GATHER_CLOCK" > $RES/${TAG}_clock_build.log 2>&1 && {
+touch niqki_amd/csrc/nq_gather.hip && make -C niqki_amd/csrc HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DNQ_GATHER_CLOCK" > $RES/${TAG}_clock_build.log 2>&1 && {
   timeout -k 10 300 python3 tools/gather_clock.py --full --shard-of 8 --no-cpu --no-extra --steps 3 2>&1 | grep -v "^{\|amdgpu.ids" > $RES/${TAG}_gather_phase_clocks_shard_of_8.txt
   timeout -k 10 300 python3 tools/gather_clock.py --full --no-cpu --no-extra --steps 3 2>&1 | grep -v "^{\|amdgpu.ids" > $RES/${TAG}_gather_phase_clocks_whole_range.txt
 }

@@ -1,7 +1,7 @@
 // ubench_sector.hip -- does a partial read of a random 128-byte line cost less than the whole line?
 // Every wave-instruction reads the first `n_ids` u16 of one random 128-byte aligned line (lanes past
 // n_ids re-read id n_ids-1), 16 loads per round, two rounds in flight -- the access shape of the
-// gather kernel's bucket walk (nq_query.hip walk64).  Reports wave-loads/s; run under
+// gather kernel's bucket walk (nq_gather.hip walk64).  Reports wave-loads/s; run under
 // rocprofv3 --pmc FETCH_SIZE / TCC_EA0_RDREQ_32B / TCC_EA0_RDREQ for the bytes actually fetched.
 // Build: hipcc -O3 --offload-arch=gfx950 tools/ubench_sector.hip -o gpurun_out/ubench_sector
 #include <hip/hip_runtime.h>
