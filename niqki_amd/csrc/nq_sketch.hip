@@ -191,6 +191,19 @@ __device__ void densify_lds_distinct(uint32_t *sk, const Derived &d, uint32_t *s
   }
 }
 
+// The smaller of two k-mer words as ONE v_min_f64 instead of v_cmp_lt_u64 + 2 x v_cndmask_b32.
+// Precondition: a, b < 2^62 (2K <= 62: K is validated once, nq_api.hip derive()).  Then the sign bit is 0 and
+// bit 62 is 0, so the exponent field is never all ones (no NaN, no infinity), and for non-negative doubles the
+// IEEE order is the integer order of the bit patterns: the instruction returns one of its inputs bit for bit.
+// Words below 2^52 are subnormal patterns: kernels are compiled with the 64-bit denormal mode that keeps them
+// (.amdhsa_float_denorm_mode_16_64 3, no fast-math or flush option in HIPFLAGS; tests/test_gpu_canonical_min.py
+// pins it).  Inline asm, not __builtin_fmin: in IEEE mode the compiler would canonicalise both inputs first.
+__device__ __forceinline__ uint64_t min62(uint64_t a, uint64_t b) {
+  uint64_t r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 // Rolling update of the forward / reverse-complement words with the code-table
 // entry `e` of the incoming base (src/niqki_index.cpp:225-236) and the canonical
 // k-mer (:345).  KFIX != 0 fixes K at compile time (K = 31: constant shifts).
@@ -205,7 +218,7 @@ __device__ __forceinline__ uint64_t roll_step(uint32_t e, uint64_t &fw, uint64_t
     fw = ((fw << 2) | (uint64_t)(e & 3u)) & d.kmer_mask;
     rc = (rc >> 2) | ((uint64_t)((e >> 2) & 3u) << rc_shift);
   }
-  return fw < rc ? fw : rc;
+  return min62(fw, rc);
 }
 
 // slot + fingerprint of a canonical k-mer and the per-slot min (:346-355)
@@ -227,8 +240,10 @@ __device__ __forceinline__ void sketch_update(uint64_t canon, const Derived &d, 
 // v_and / v_or / v_xor / v_mov / v_lshrrev_b32 take ~2.4 SIMD cycles per wave instruction, EVERY other
 // vector opcode ~4.3 -- 32-bit multiplies, v_mad_u64_u32 (4.4), 64-bit shifts and compares included.
 // So the step below is written for the fewest instructions, multiplies are not what to avoid:
-//   * the code table for K = 31 holds 8-byte entries {forward code, rc code << 28}: both rolling
-//     updates are one 64-bit shift plus an `or` (5 instructions instead of 7);
+//   * the code table for K = 31 holds 8-byte entries {forward code, rc code << 30}: the forward update is
+//     ONE v_lshl_add_u64 with the entry as the 64-bit addend plus the `and` of the high word (the rc code
+//     lands in bits 2K, 2K + 1, above the mask), the reverse update an `or` of the high word and one 64-bit
+//     shift (4 instructions instead of 7); the canonical choice is one v_min_f64 (min62());
 //   * the 64 x 64 -> 64 multiplies run as chains of v_mad_u64_u32 (the addend carries the cross terms);
 //   * candidates are stored under the exec mask (compare, 2 x mbcnt, 1 address instruction) into a
 //     wave-private LIFO stack whose top lives in a scalar register: no ring wrap, no scratch slot.
@@ -266,12 +281,17 @@ __device__ __forceinline__ void mix_round(uint32_t &lo, uint32_t &hi, uint32_t c
   lo = (uint32_t)q;
   hi = (uint32_t)p + (uint32_t)(q >> 32);
 }
-// the same round when only the high word of the product is wanted
+// the same round when only the high word of the product is wanted: lo32(y * chi) + lo32(hi * clo) +
+// hi32(y * clo) mod 2^32.  The v_mul_hi rides in the LOW word of the first mad's addend (carries only go
+// into the high words, which are dropped), so the addend's high word may hold anything: it is left
+// unwritten, no v_mov.  4 instructions instead of 5.
 __device__ __forceinline__ uint32_t mix_round_hi(uint32_t lo, uint32_t hi, uint32_t clo, uint32_t chi) {
+  typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
   const uint32_t y = lo ^ hi;
-  const uint64_t t = mul64(hi, clo);
-  const uint64_t p = mad64(y, chi, t);
-  return (uint32_t)p + __umulhi(y, clo);
+  u32x2_t a = __builtin_nondeterministic_value(a);   // (any value, but a defined one)
+  a.x = __umulhi(y, clo);
+  const uint64_t t = mad64(hi, clo, __builtin_bit_cast(uint64_t, a));
+  return (uint32_t)mad64(y, chi, t);
 }
 __device__ __forceinline__ uint32_t rev64_hi_mad(uint64_t canon) {
   uint32_t lo = (uint32_t)canon, hi = (uint32_t)(canon >> 32);
@@ -279,7 +299,7 @@ __device__ __forceinline__ uint32_t rev64_hi_mad(uint64_t canon) {
   return mix_round_hi(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
 }
 
-constexpr uint32_t kFastKMin = 17;   // smallest K of the fast filtered path: 2K - 2 >= 32
+constexpr uint32_t kFastKMin = 17;   // smallest K of the fast filtered path: the rc code, at bit 2K - 2 of the reverse word, is in its high word
 constexpr uint32_t kStack = 192;  // candidate k-mers per wave-private stack: < 64 left by a drain + two steps of <= 64
 
 // Candidate store of one step: lanes whose hash word hh is below thr push canon onto the wave's stack
@@ -307,7 +327,7 @@ __device__ __forceinline__ void push_candidates(uint32_t hh, uint32_t thr, uint6
 // LDS layout of sketch_kernel (byte offsets from the start of its dynamic LDS, which is LDS address 0: the
 // kernel has no static LDS): the K = 31 code table first, so that a look-up address is the byte value
 // times 8 (one SDWA shift), and the sketch cells at a fixed offset (an instruction immediate).
-constexpr uint32_t kLut64Off = 0;       // 256 x {forward code, rc code << 28}
+constexpr uint32_t kLut64Off = 0;       // 256 x {forward code, rc code << 30}
 constexpr uint32_t kLutOff = 2048;      // 256 code_entry bytes
 constexpr uint32_t kFlagOff = 2304;     // 4 words
 constexpr uint32_t kCellOff = 2320;     // the sketch cells; behind them the distinct-value tables or the candidate stacks
@@ -354,6 +374,12 @@ __device__ __forceinline__ uint64_t shl2_64(uint64_t x) {
 __device__ __forceinline__ uint64_t shr2_64(uint64_t x) {
   uint64_t r;
   asm("v_lshrrev_b64 %0, 2, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+// (x << 2) + e in one instruction: the forward roll with a whole code table entry as the addend
+__device__ __forceinline__ uint64_t shl2_add64(uint64_t x, uint64_t e) {
+  uint64_t r;
+  asm("v_lshl_add_u64 %0, %1, 2, %2" : "=v"(r) : "v"(x), "v"(e));
   return r;
 }
 
@@ -466,9 +492,11 @@ __device__ void roll_records(const SketchArgs &a, uint32_t entry, uint32_t part,
       uint64_t fw = 0, rc = 0;
       if (FAST && fast_k && __all(i0 >= Km1 + warm_back)) {
         // no lane of the wave starts inside a record's first K-1 positions (all chunks but a record's
-        // first): the 30 steps are plain rolling updates from the 8-byte code table, 4 instructions each.
-        // (K < 31: 30 steps all the same, from 31 - K bases further back -- the forward word is masked below,
-        // the reverse word's older codes leave at the bottom.)
+        // first): the 30 steps are plain rolling updates from the 8-byte code table, 3 instructions each.
+        // (K < 31: 30 steps all the same, from 31 - K bases further back -- the reverse word's older codes
+        // leave at the bottom.  The forward word is left unmasked: the entries' rc codes and the older
+        // forward codes sit at bit 2K and above, where sums only carry upwards, and both forms of the hash
+        // step mask the word after their own shift.)
         ByteStream ws;
         ws.open(base + i0 - warm_back);
         uint64_t ew[32];
@@ -483,10 +511,9 @@ __device__ void roll_records(const SketchArgs &a, uint32_t entry, uint32_t part,
         }
 #pragma unroll
         for (int j = 0; j < 30; ++j) {
-          fw = shl2_64(fw) | (uint32_t)ew[j];
-          rc = shr2_64(rc) | (ew[j] & 0xFFFFFFFF00000000ULL);
+          fw = shl2_add64(fw, ew[j]);
+          rc = shr2_64(rc | (ew[j] & 0xFFFFFFFF00000000ULL));   // (rc < 2^2K: the code's two bits are free)
         }
-        if (KFIX != 31) fw &= fw_mask;   // (K = 31: 30 steps from zero stay below 2^60)
       } else {
         uint32_t ok = 1;
         if (i0 < Km1) {
@@ -548,10 +575,10 @@ __device__ void roll_records(const SketchArgs &a, uint32_t entry, uint32_t part,
         }
         auto step = [&](uint64_t ent, bool check) {
           // :225-229 and :233-236 with the entry's pre-placed codes
-          fw = shl2_64(fw);
-          fw = (fw | (uint32_t)ent) & fw_mask;   // (only the high word's `and` is an instruction)
-          rc = shr2_64(rc) | (ent & 0xFFFFFFFF00000000ULL);
-          const uint64_t canon = fw < rc ? fw : rc;   // :345
+          // (the entry's rc code and any carry out of it land at bit 2K and above: the `and` clears them)
+          rc = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
+          fw = shl2_add64(fw, ent) & fw_mask;   // (only the high word's `and` is an instruction)
+          const uint64_t canon = min62(fw, rc);   // :345
           push_candidates(rev64_hi_mad(canon), thr, canon, top);
           // two steps add at most 128 to fewer than 64.  Unlikely: the drain is laid out behind the loop,
           // the common path has no taken branch
@@ -641,7 +668,7 @@ __global__ __launch_bounds__(BLOCK) void sketch_kernel(SketchArgs a) {
 #endif
   const Derived &d = a.d;
   const uint32_t Fc = d.F / a.halves;               // cells this workgroup keeps
-  uint2 *lut64 = (uint2 *)(smem + kLut64Off / 4);   // 256 x {forward code, rc code << 28} (K = 31 filtered path)
+  uint2 *lut64 = (uint2 *)(smem + kLut64Off / 4);   // 256 x {forward code, rc code << 30} (K = 31 filtered path)
   uint8_t *lut = (uint8_t *)(smem + kLutOff / 4);   // 256 bytes
   uint32_t *s_flag = smem + kFlagOff / 4;           // 4 words
   uint32_t *sk = smem + kCellOff / 4;               // Fc cells
@@ -657,8 +684,9 @@ __global__ __launch_bounds__(BLOCK) void sketch_kernel(SketchArgs a) {
   for (uint32_t i = tid; i < 256; i += BLOCK) {
     const uint32_t e = code_entry(i);
     lut[i] = (uint8_t)e;
-    // rc code at bit 2K - 2 of the reverse word = bit 2K - 34 of the entry's high word (K >= 17; else unused)
-    lut64[i] = make_uint2(e & 3u, d.K >= kFastKMin ? ((e >> 2) & 3u) << (2u * d.K - 34u) : 0u);
+    // rc code at bit 2K of the reverse word BEFORE its shift = bit 2K - 32 of the entry's high word (K >= 17;
+    // else unused); added into the forward word it sits above the k-mer mask
+    lut64[i] = make_uint2(e & 3u, d.K >= kFastKMin ? ((e >> 2) & 3u) << (2u * d.K - 32u) : 0u);
   }
   if (a.accumulate) {
     const uint32_t *src = (const uint32_t *)a.sketches + (uint64_t)entry * d.F + (uint64_t)half * Fc;
@@ -1133,7 +1161,7 @@ __global__ __launch_bounds__(64) void sketch_reads_kernel(SketchArgs a) {
               rc |= (uint64_t)(c >> 2) << (2u * j);
             }
           }
-          const uint64_t canon = fw < rc ? fw : rc;   // :345
+          const uint64_t canon = min62(fw, rc);   // :345
           sketch_update(canon, d, sk, live);
         }
       }
@@ -1446,10 +1474,10 @@ __global__ __launch_bounds__(1024) void alu_probe_kernel(uint32_t iters, uint32_
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const uint32_t c = (e >> (2 * j)) & 3u;
-        fw = shl2_64(fw);
-        fw = (fw | c) & ((1ULL << 62) - 1ULL);
-        rc = shr2_64(rc) | ((uint64_t)((3u - c) << 28) << 32);
-        const uint64_t canon = fw < rc ? fw : rc;
+        const uint64_t ent = ((uint64_t)((3u - c) << 30) << 32) | c;   // a code table entry
+        rc = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
+        fw = shl2_add64(fw, ent) & ((1ULL << 62) - 1ULL);
+        const uint64_t canon = min62(fw, rc);
         pass += rev64_hi_mad(canon) < (1u << 29);
       }
       e = e * 1664525u + 1013904223u;

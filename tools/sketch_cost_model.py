@@ -25,7 +25,7 @@ ALIAS = {
     "v_lshrrev_b64": "LSHRREV_B64", "v_mul_lo_u32": "MUL_LO_U32", "v_mul_hi_u32": "MUL_HI_U32", "v_mad_u64_u32": "MAD_U64_U32",
     "v_mbcnt_lo_u32_b32": "MBCNT_LO", "v_mbcnt_hi_u32_b32": "MBCNT_HI", "v_ffbh_u32": "FFBH_U32", "v_min3_u32": "MIN3_U32",
     "v_min_u32": "MIN_U32", "v_lshlrev_b32_sdwa": "ADD_U32_SDWA", "v_add_u32_sdwa": "ADD_U32_SDWA", "v_bitop3_b32": "AND_OR_B32",
-    "v_lshl_add_u64": "LSHLREV_B64", "v_add_co_u32": "ADD_CO_U32", "v_addc_co_u32": "ADDC_CO_U32", "v_readfirstlane_b32": "READFIRSTLANE",
+    "v_lshl_add_u64": "LSHL_ADD_U64", "v_min_f64": "MIN_F64", "v_add_co_u32": "ADD_CO_U32", "v_addc_co_u32": "ADDC_CO_U32", "v_readfirstlane_b32": "READFIRSTLANE",
     "v_mov_b64": "MOV_B32",
 }
 

@@ -21,7 +21,7 @@ enum Op {
   LSHLREV_B64, LSHRREV_B64, MUL_LO_U32, MUL_HI_U32, MAD_U64_U32, MUL_U32_U24, MUL_HI_U32_U24, MAD_U32_U24,
   MBCNT_LO, MBCNT_HI, FFBH_U32, MIN3_U32, MIN_U32, ADD_U32_SDWA, ADD_CO_U32, ADDC_CO_U32, SUB_CLAMP, READFIRSTLANE, READLANE,
   MAD_U32_U16, PK_MUL_LO_U16, PK_ADD_U16, ADD_LSHL_U32, MOV_DPP, DS_WRITE_B64, DS_READ_U8, DS_MIN_U32_RANDOM, DS_READ_B64,
-  MUL_LO_U32_LIT, SAD_U32, MAD_U64_U32_ACC, NOP, N_OPS
+  MUL_LO_U32_LIT, SAD_U32, MAD_U64_U32_ACC, MIN_F64, LSHL_ADD_U64, MAD_U64_U32_HALF_ADDEND, NOP, N_OPS
 };
 
 struct OpInfo { const char *name; int wave_insts_per_unit; };
@@ -33,6 +33,17 @@ __global__ __launch_bounds__(1024) void k(uint32_t *out, uint32_t iters, uint32_
   uint32_t a0 = t, a1 = t * 3 + 1, a2 = t ^ 0x1234567u, a3 = t + 77, a4 = t * 5 + 3, a5 = ~t, a6 = t + 9, a7 = t * 7 + 5;
   uint32_t b = t * 2654435761u | 1u, c = (t >> 3) | 0x10001u;
   uint64_t w0 = t * 0x9E3779B97F4A7C15ULL, w1 = ~w0, w2 = w0 * 3, w3 = w0 + 12345, w4 = w0 ^ 0x5555, w5 = w1 * 7, w6 = w1 + 99, w7 = w0 * 11;
+  if (OP == MIN_F64) {
+    // k-mer words: below 2^62, so no NaN or infinity pattern (the sketch kernel's min62()); w1 is a subnormal pattern
+    w0 &= (1ULL << 62) - 1; w1 &= (1ULL << 52) - 1; w2 &= (1ULL << 62) - 1; w3 &= (1ULL << 62) - 1;
+    w4 &= (1ULL << 62) - 1; w5 &= (1ULL << 62) - 1; w6 &= (1ULL << 62) - 1; w7 &= (1ULL << 62) - 1;
+  }
+  const uint64_t wb = ((uint64_t)(t & 3u) << 62) | (b & 3u);   // a code table entry: forward code, rc code in the top bits
+  // a 64-bit addend of which only the low word was ever written (mix_round_hi's v_mul_hi result)
+  typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+  u32x2_t half = __builtin_nondeterministic_value(half);
+  half.x = c;
+  const uint64_t wh = __builtin_bit_cast(uint64_t, half);
   uint32_t s0 = seed * 13u + 0x6659FD93u;  // wave-uniform: lives in an SGPR
   s0 = __builtin_amdgcn_readfirstlane(s0);
   uint32_t ldsaddr = (threadIdx.x & 1023u) * 8u;  // conflict-free 8-byte stride
@@ -162,6 +173,18 @@ __global__ __launch_bounds__(1024) void k(uint32_t *out, uint32_t iters, uint32_
 #undef X
       } else if (OP == MAD_U64_U32_ACC) {
 #define X(n) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(W(n)) : "v"(A(n)), "s"(s0) : "vcc");
+        REP8(X)
+#undef X
+      } else if (OP == MAD_U64_U32_HALF_ADDEND) {
+#define X(n) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(W(n)) : "v"(A(n)), "s"(s0), "v"(wh) : "vcc");
+        REP8(X)
+#undef X
+      } else if (OP == MIN_F64) {
+#define X(n) asm volatile("v_min_f64 %0, %0, %1" : "+v"(W(n)) : "v"(w1));
+        REP8(X)
+#undef X
+      } else if (OP == LSHL_ADD_U64) {
+#define X(n) asm volatile("v_lshl_add_u64 %0, %0, 2, %1" : "+v"(W(n)) : "v"(wb));
         REP8(X)
 #undef X
       } else if (OP == MUL_U32_U24) {
@@ -326,6 +349,8 @@ int main(int argc, char **argv) {
   R(MBCNT_LO, 0); R(MBCNT_HI, 0); R(FFBH_U32, 0); R(MIN3_U32, 0); R(MIN_U32, 0); R(ADD_U32_SDWA, 0); R(ADD_CO_U32, 0);
   R(ADDC_CO_U32, 0); R(SUB_CLAMP, 0); R(READFIRSTLANE, 0); R(READLANE, 0); R(MOV_DPP, 0);
   R(DS_WRITE_B64, 0); R(DS_READ_B64, 0); R(DS_READ_U8, 1); R(DS_MIN_U32_RANDOM, 3); R(NOP, 0);
+  // the 64-bit-wide forms of the canonical choice, the forward roll and the folded hash round (r07)
+  R(MIN_F64, 0); R(LSHL_ADD_U64, 0); R(MAD_U64_U32_HALF_ADDEND, 0);
   if (csv) fclose(csv);
   return 0;
 }

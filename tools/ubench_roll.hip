@@ -8,6 +8,13 @@
 //   3  form 1 with the candidates ranked by the LDS instead of v_mbcnt: ds_add_rtn_u32 on a wave-private counter
 //      returns every passing lane its place, the store follows one step later (software pipelined)
 //   0  form 1 without the push (what the push costs)
+//   4  form 1 with the canonical choice as one v_min_f64 (min62) instead of v_cmp_lt_u64 + 2 x v_cndmask_b32
+//   5  form 1 with the forward roll as one v_lshl_add_u64 on the whole table entry (rc code two bits higher in the
+//      entry, the reverse word's `or` before its shift)
+//   6  form 1 with the second round of the filter hash in four instructions (v_mul_hi in the first mad's addend)
+//   7  forms 4 + 5 + 6 together: the product's loop since r07
+// Form 1 is the loop as it was up to r06, built from 32-bit pieces and restated here (ub_*), so that the two stay
+// comparable in one run.
 // Same occupancy as the kernel: 1024-thread workgroups, one per CU (130 KB of dynamic LDS), 4 waves per SIMD.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude tools/ubench_roll.hip -o tools/bin/ubench_roll
 //   tools/bin/ubench_roll [groups_per_lane=512] [reps=5]
@@ -21,6 +28,21 @@
 using namespace nq;
 
 __device__ unsigned long long ub_clk[2];
+
+// the second hash round as it was up to r06: 5 instructions, the v_mul_hi added at the end
+__device__ __forceinline__ uint32_t ub_mix_round_hi5(uint32_t lo, uint32_t hi, uint32_t clo, uint32_t chi) {
+  const uint32_t y = lo ^ hi;
+  const uint64_t t = mul64(hi, clo);
+  const uint64_t p = mad64(y, chi, t);
+  return (uint32_t)p + __umulhi(y, clo);
+}
+template <bool H4>
+__device__ __forceinline__ uint32_t ub_rev64_hi_mad(uint64_t canon) {
+  uint32_t lo = (uint32_t)canon, hi = (uint32_t)(canon >> 32);
+  mix_round(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
+  return H4 ? mix_round_hi(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32))
+            : ub_mix_round_hi5(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
+}
 constexpr uint32_t kRegion = 32;   // groups of 16 bases a lane's input region holds (re-read: cache resident)
 
 template <int VAR>
@@ -28,10 +50,11 @@ __global__ __launch_bounds__(1024) void roll_kernel(const uint8_t *bytes, const 
                                                     uint32_t *sink) {
   extern __shared__ __align__(16) uint32_t smem[];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  constexpr bool MINF = VAR == 4 || VAR == 7, ROLL = VAR == 5 || VAR == 7, H4 = VAR == 6 || VAR == 7;
   uint2 *lut64 = (uint2 *)smem;
   for (uint32_t i = tid; i < 256; i += 1024) {
     const uint32_t e = code_entry(i);
-    lut64[i] = make_uint2(e & 3u, ((e >> 2) & 3u) << 28);
+    lut64[i] = make_uint2(e & 3u, ((e >> 2) & 3u) << (ROLL ? 30 : 28));
   }
   __syncthreads();
   const unsigned long long c0 = __builtin_readcyclecounter(), r0 = wall_clock64();
@@ -76,7 +99,7 @@ __global__ __launch_bounds__(1024) void roll_kernel(const uint8_t *bytes, const 
         fw = ((uint64_t)fhi << 32) | flo;
         rc = ((uint64_t)rhi << 32) | rlo;
         const uint64_t canon = fw < rc ? fw : rc;
-        push_candidates(rev64_hi_mad(canon), thr, canon, top);
+        push_candidates(ub_rev64_hi_mad<false>(canon), thr, canon, top);
       }
       if (top >= bottom + 4096u) top = bottom;
       w2 = w1; w1 = wc; v2 = v1; v1 = vc;
@@ -101,12 +124,17 @@ __global__ __launch_bounds__(1024) void roll_kernel(const uint8_t *bytes, const 
     uint64_t p_mask = 0, p_canon = 0;
     uint32_t p_at = 0;
     auto step = [&](uint64_t ent) {
-      fw = shl2_64(fw);
-      fw = (fw | (uint32_t)ent) & ((1ULL << 62) - 1ULL);
-      rc = shr2_64(rc) | (ent & 0xFFFFFFFF00000000ULL);
-      const uint64_t canon = fw < rc ? fw : rc;
-      const uint32_t hh = rev64_hi_mad(canon);
-      if (VAR == 1) {
+      if (ROLL) {
+        rc = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
+        fw = shl2_add64(fw, ent) & ((1ULL << 62) - 1ULL);
+      } else {
+        fw = shl2_64(fw);
+        fw = (fw | (uint32_t)ent) & ((1ULL << 62) - 1ULL);
+        rc = shr2_64(rc) | (ent & 0xFFFFFFFF00000000ULL);
+      }
+      const uint64_t canon = MINF ? min62(fw, rc) : (fw < rc ? fw : rc);
+      const uint32_t hh = ub_rev64_hi_mad<H4>(canon);
+      if (VAR == 1 || VAR >= 4) {
         push_candidates(hh, thr, canon, top);
       } else if (VAR == 3) {
         uint32_t at;
@@ -149,7 +177,7 @@ __global__ __launch_bounds__(1024) void roll_kernel(const uint8_t *bytes, const 
 #pragma unroll
       for (int j = 8; j < 16; ++j) step(e[j]);
       lut64_8<1>(w, 0, e);
-      if (VAR == 1 && top >= bottom + 4096u) top = bottom;
+      if ((VAR == 1 || VAR >= 4) && top >= bottom + 4096u) top = bottom;
       if (VAR == 3) {   // 16 steps x <= 64 places of 8 bytes: back to the bottom (all lanes write the same word)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         *(lds_u32_t *)(uintptr_t)ctr_addr = bottom;
@@ -214,17 +242,22 @@ int main(int argc, char **argv) {
   const uint64_t n_fill = n_bytes / 16 + 1 > n_words ? n_bytes / 16 + 1 : n_words;
   hipLaunchKernelGGL(fill_kernel, dim3((uint32_t)((n_fill + 255) / 256)), dim3(256), 0, 0, bytes, packed, n_bytes, n_words);
   CK(hipDeviceSynchronize());
-  double ns[4], cy[4];
+  double ns[8], cy[8];
   if (run<1>(bytes, packed, groups, reps, sink, &ns[1], &cy[1])) return 1;
   if (run<0>(bytes, packed, groups, reps, sink, &ns[0], &cy[0])) return 1;
   if (run<2>(bytes, packed, groups, reps, sink, &ns[2], &cy[2])) return 1;
   if (run<3>(bytes, packed, groups, reps, sink, &ns[3], &cy[3])) return 1;
+  if (run<4>(bytes, packed, groups, reps, sink, &ns[4], &cy[4])) return 1;
+  if (run<5>(bytes, packed, groups, reps, sink, &ns[5], &cy[5])) return 1;
+  if (run<6>(bytes, packed, groups, reps, sink, &ns[6], &cy[6])) return 1;
+  if (run<7>(bytes, packed, groups, reps, sink, &ns[7], &cy[7])) return 1;
   if (run<1>(bytes, packed, groups, reps, sink, &ns[1], &cy[1])) return 1;   // (again, after everything is warm)
-  const char *name[4] = {"0  byte table, no push", "1  byte table + mbcnt push (product)", "2  2-bit packed windows + mbcnt push",
-                         "3  byte table + LDS-ranked push"};
+  const char *name[8] = {"0  byte table, no push", "1  byte table + mbcnt push (product to r06)", "2  2-bit packed windows + mbcnt push",
+                         "3  byte table + LDS-ranked push", "4  form 1, canonical choice by v_min_f64", "5  form 1, forward roll by v_lshl_add_u64",
+                         "6  form 1, second hash round in 4", "7  forms 4 + 5 + 6 (product since r07)"};
   printf("hot loop of sketch_kernel<1024,32,31> in isolation: %u groups of 16 k-mer steps per lane, 256 workgroups x 1024 threads, no drains\n", groups);
   printf("%-42s %14s %22s %10s\n", "form", "ps/step/lane", "SIMD cycles/wave step", "vs form 1");
-  for (int v : {1, 0, 2, 3})
+  for (int v : {1, 0, 2, 3, 4, 5, 6, 7})
     printf("%-42s %14.2f %22.1f %10.3f\n", name[v], ns[v] * 1e3, cy[v], ns[v] / ns[1]);
   return 0;
 }
