@@ -15,6 +15,7 @@
 // hash steps.  The kernel is integer-ALU bound (4 64-bit multiplies per
 // k-mer), HBM traffic is 1 byte per base.
 #include "nq_kernels.h"
+#include "nq_sketch_lines.h"
 #include "../../include/niqki_hip.h"
 
 #include <cstdlib>
@@ -81,7 +82,7 @@ __device__ __forceinline__ uint32_t dword_of(const uint4 &v, int i) {
 // first-writer rule.  Returns with cells still empty only where the reference
 // would loop forever (F consecutive passes without a fill prove a fixpoint).
 template <int BLOCK>
-__device__ void densify_lds(uint32_t *sk, const Derived &d, uint32_t *s_flag) {
+__device__ __forceinline__ void densify_lds(uint32_t *sk, const Derived &d, uint32_t *s_flag) {
   const uint32_t F = d.F;
   const uint32_t tid = threadIdx.x;
   // count empties
@@ -137,7 +138,7 @@ __device__ void densify_lds(uint32_t *sk, const Derived &d, uint32_t *s_flag) {
 // as densify_lds.  aux: 3*R words of LDS (mi, A = low word of unrev(v), B = low word
 // of rev(v)).
 template <int BLOCK>
-__device__ void densify_lds_distinct(uint32_t *sk, const Derived &d, uint32_t *s_flag, uint32_t *aux) {
+__device__ __forceinline__ void densify_lds_distinct(uint32_t *sk, const Derived &d, uint32_t *s_flag, uint32_t *aux) {
   const uint32_t F = d.F, R = d.R, W = d.W;
   const uint32_t tid = threadIdx.x;
   uint32_t *mi = aux, *ha = aux + R, *hb = aux + 2 * R;
@@ -364,6 +365,13 @@ __device__ __forceinline__ void lut64_8(const uint4 &v, uint32_t lds0, uint64_t 
   }
 #undef NQ_E
 }
+// ... of the four bytes of one dword, into e[0..4) (HALF = 0) or e[4..8)
+template <int HALF>
+__device__ __forceinline__ void lut64_4(uint32_t w, uint32_t lds0, uint64_t (&e)[8]) {
+#define NQ_E(J, B) e[4 * HALF + J] = *(lds_u64_t *)(uintptr_t)(lds0 + kLut64Off + byte_x8<B>(w));
+  NQ_E(0, 0) NQ_E(1, 1) NQ_E(2, 2) NQ_E(3, 3)
+#undef NQ_E
+}
 // 64-bit shifts the compiler cannot look into (it otherwise re-derives halves of the result with extra
 // instructions)
 __device__ __forceinline__ uint64_t shl2_64(uint64_t x) {
@@ -417,8 +425,9 @@ __device__ __forceinline__ void candidate_update(uint64_t canon, const Derived &
 // chunks over the workgroup's lanes is nearly full (5 Mbp over 1024 lanes: 10 rounds of 496 k-mers).
 // ZERO: the kernel's LDS layout starts at LDS address 0 (checked at kernel entry), so the fast path
 // addresses the code table and the cells with instruction immediates.
+// (always inline: a call would put the kernel's arguments in scratch memory and their values in vector registers)
 template <int BLOCK, int GROUPS, int KFIX, bool FILTER, bool HALF, bool ZERO>
-__device__ void roll_records(const SketchArgs &a, uint32_t entry, uint32_t part, uint32_t *sk, const uint8_t *lut,
+__device__ __forceinline__ void roll_records(const SketchArgs &a, uint32_t entry, uint32_t part, uint32_t *sk, const uint8_t *lut,
                              uint64_t *stack_base, uint32_t thr, uint32_t hsel) {
   const Derived &d = a.d;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -654,6 +663,270 @@ __device__ void roll_records(const SketchArgs &a, uint32_t entry, uint32_t part,
   if (FILTER && top != bottom) drain_rest();
 }
 
+// ---- the line-aligned form of the fast filtered loop (1024 x 32 launch shape, K in 17..31) --------------------
+// 16 bytes from any byte address (the hardware takes unaligned vector loads); loads exactly [p, p + 16)
+__device__ __forceinline__ uint4 load16u(const uint8_t *p) {
+  uint4 v;
+  __builtin_memcpy(&v, p, 16);
+  return v;
+}
+typedef uint32_t u32x32_t __attribute__((ext_vector_type(32)));   // a line in 32 registers that a uniform index reaches
+
+// the 16 bytes at address x, of which only [x + dlt, ...) (dlt > 0) or (..., x + 16 + dlt) (dlt < 0) could be
+// loaded, from x + dlt: moved back to their places, zeroes where nothing was loaded
+__device__ __forceinline__ uint4 replace16(const uint4 &v, int dlt) {
+  uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32), hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
+  if (dlt >= 16 || dlt <= -16) {
+    lo = hi = 0;
+  } else if (dlt > 0) {
+    const uint32_t s = 8u * (uint32_t)dlt;
+    if (s >= 64u) { hi = lo << (s - 64u); lo = 0; }
+    else { hi = (hi << s) | (lo >> (64u - s)); lo <<= s; }
+  } else if (dlt < 0) {
+    const uint32_t s = 8u * (uint32_t)(-dlt);
+    if (s >= 64u) { lo = hi >> (s - 64u); hi = 0; }
+    else { lo = (lo >> s) | (hi << (64u - s)); hi >>= s; }
+  }
+  return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+
+// All records of one sketch, this workgroup's part, with the geometry of nq_sketch_lines.h: every lane owns one run
+// of whole 128-byte lines of a record part, fetches each line once with eight back-to-back 16-byte loads and takes
+// its 128 hash steps from registers: no re-alignment, no line shared between lanes, one warm-up per lane and
+// record.  A round is one line per lane; the wave's lanes step together (the candidate stack is wave-collective).
+//   * the plain round (every lane's whole line is hash bytes): the step of the chunked fast loop;
+//   * the predicated round (a record's first and last line, lanes with one line fewer than their neighbours, lanes
+//     without lines): the same step, but a dead step leaves the rolling words alone and its hash word is all ones, so
+//     it never passes the filter.
+// A line that does not lie inside the buffer (the buffer's alignment is unknown: its first and last line may not be
+// whole) is loaded in 16-byte pieces clamped to [seqs, seqs + rec_off[end of this sketch's records] + NIQKI_SEQ_PAD):
+// no byte outside is ever loaded.  Every load address comes from the helpers of nq_sketch_lines.h (warm_load, round_line,
+// line_inside, clamp_piece), which the CPU test walks against the buffer.  Addresses become pointers as offsets from
+// a.seqs: a pointer made from a bare integer would lose the global address space, and its loads would be flat loads,
+// which the LDS look-ups' lgkmcnt waits wait for too.
+template <int BLOCK, int KFIX>
+__device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t entry, uint32_t part, const uint8_t *lut,
+                                   uint64_t *stack_base, uint32_t thr) {
+  const Derived &d = a.d;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t Km1 = d.K - 1u;
+  const uint32_t rc_shift = 2u * d.K - 2u;
+  const uint32_t mask_hi = KFIX == 31 ? 0x3FFFFFFFu : __builtin_amdgcn_readfirstlane((uint32_t)(d.kmer_mask >> 32));
+  const uint64_t fw_mask = ((uint64_t)mask_hi << 32) | 0xFFFFFFFFull;
+  constexpr uint32_t lds0 = 0;
+  uint64_t *stack = stack_base + (tid >> 6) * kStack;
+  const uint32_t bottom = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_u64_t *)stack);
+  uint32_t top = bottom;
+  const uint32_t lane8 = lane * 8u;
+  auto drain64 = [&]() {   // the 64 youngest candidates
+    const uint64_t c = *(lds_u64_t *)(uintptr_t)(top - 512u + lane8);
+    candidate_update(c, d, lds0, true);
+    top -= 512u;
+  };
+
+  const uint32_t r0 = a.entry_rec ? a.entry_rec[entry] : entry;
+  const uint32_t r1 = a.entry_rec ? a.entry_rec[entry + 1] : entry + 1;
+  // the pad behind this sketch's last record belongs to the buffer whatever follows: a bound that needs no record count
+  const uint64_t end_off = a.rec_off[r1];
+  // (the empty asm hides where the number came from: the compiler would otherwise fold a.seqs + (x - seqs_addr) back
+  // into a pointer made from the integer x)
+  uint64_t seqs_addr = (uint64_t)(uintptr_t)a.seqs;
+  asm("" : "+s"(seqs_addr));
+  const uint64_t buf_lo = seqs_addr, buf_hi = seqs_addr + end_off + NIQKI_SEQ_PAD;
+  auto gptr = [&](uint64_t addr) { return a.seqs + (int64_t)(addr - seqs_addr); };
+  for (uint32_t rec = r0; rec < r1; ++rec) {
+    const uint64_t b0 = a.rec_off[rec], b1 = a.rec_off[rec + 1];
+    if (b1 - b0 <= d.K) continue;          // src/niqki_index.cpp:395,:450
+    const LaneLines g = lane_lines(seqs_addr, b0, b1, d.K, a.splits, part, BLOCK,
+                                   __builtin_amdgcn_readfirstlane(tid >> 6), lane);
+    const uint32_t nl = g.n_lines;
+    uint32_t nl_max = nl;
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) {
+      const uint32_t o = (uint32_t)__shfl_xor((int)nl_max, dd, 64);
+      nl_max = o > nl_max ? o : nl_max;
+    }
+    nl_max = __builtin_amdgcn_readfirstlane(nl_max);
+    if (nl_max == 0) continue;             // (uniform) no line of this record for the wave
+    const uint8_t *const base = a.seqs + b0;
+    // ---- warm-up, once per lane and record (see roll_records; the 32 bytes come as two unaligned loads) ----
+    uint64_t fw = 0, rc = 0;
+    const bool wave_fast = __all(g.warm_fast != 0u || nl == 0u) != 0;   // (a lane without lines rolls the record's first bytes, for nothing)
+    const uint8_t *const wp = gptr(warm_load(g, d.K, wave_fast));
+    if (wave_fast) {
+      uint64_t ew[32];
+      {
+        uint64_t e16[16];
+        lut64_16(load16u(wp), lds0, e16);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) ew[j] = e16[j];
+        lut64_16(load16u(wp + 16), lds0, e16);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) ew[16 + j] = e16[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 30; ++j) {
+        fw = shl2_add64(fw, ew[j]);
+        rc = shr2_64(rc | (ew[j] & 0xFFFFFFFF00000000ULL));
+      }
+    } else {
+      // a lane of the fast form beside one that starts inside the prefix: its K - 1 bases are the last of its 30
+      const uint8_t *const gp = wp;
+      const uint64_t i0 = g.first_kmer;
+      uint32_t ok = 1;
+      if (reads_prefix(g, d.K)) {
+        const uint4 p0 = load16u(base), p1 = load16u(base + 16);
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+          uint32_t w = dword_of(j < 16 ? p0 : p1, (j & 15) >> 2);
+          uint32_t e = lut[(w >> (8 * (j & 3))) & 0xFFu];
+          if ((uint32_t)j < Km1) ok &= (e >> 6) & 1u;
+        }
+      }
+      const uint4 g0 = load16u(gp), g1 = load16u(gp + 16);
+      uint32_t ew[32];
+#pragma unroll
+      for (int j = 0; j < 32; ++j) {
+        uint32_t w = dword_of(j < 16 ? g0 : g1, (j & 15) >> 2);
+        ew[j] = lut[(w >> (8 * (j & 3))) & 0xFFu];
+      }
+#pragma unroll
+      for (int j = 0; j < 32; ++j) {
+        if ((uint32_t)j < Km1) {
+          const uint32_t e = ew[j];
+          const bool pfx = i0 + (uint32_t)j < Km1;
+          uint32_t dgt = ok ? ((e >> 4) & 3u) : 0u;
+          uint32_t cf = pfx ? dgt : (e & 3u);
+          uint32_t cr = pfx ? (3u - dgt) : ((e >> 2) & 3u);
+          fw = (fw << 2) | cf;
+          rc = (rc >> 2) | ((uint64_t)cr << rc_shift);
+        }
+      }
+    }
+    // ---- the rounds ----
+    // The round's line: 32 registers that the pass loop indexes with its (uniform) counter -- one v_mov in
+    // register-index mode per dword, so the loop's body stays 16 steps, not a line of 128.
+    u32x32_t L;
+    // whole: (uniform) every lane may load all of the line at `line`.  Otherwise every 16-byte piece is clamped to the
+    // buffer and moved back to its place.
+    auto load_line = [&](uint64_t line, bool whole) {
+      if (whole) {
+        const uint8_t *const p = gptr(line);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const uint4 v = *(const uint4 *)(p + 16 * q);
+          L[4 * q] = v.x; L[4 * q + 1] = v.y; L[4 * q + 2] = v.z; L[4 * q + 3] = v.w;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const uint64_t x = line + 16u * q, c = clamp_piece(x, buf_lo, buf_hi);
+          uint4 v = load16u(gptr(c));
+          if (c != x) v = replace16(v, (int)(int64_t)(c - x));
+          L[4 * q] = v.x; L[4 * q + 1] = v.y; L[4 * q + 2] = v.z; L[4 * q + 3] = v.w;
+        }
+      }
+    };
+    auto is_whole = [&](uint64_t line, bool want) { return __all(want && line_inside(line, buf_lo, buf_hi)) != 0; };
+    auto dword_at = [&](uint32_t i) { return L[__builtin_amdgcn_readfirstlane(i)]; };   // (i uniform)
+    const uint64_t rec_addr = seqs_addr + b0;
+    // the lane's hash bytes, counted from the start of its first line
+    const uint32_t rel_lo = (uint32_t)(g.hash_lo - (g.line0 << kLineLog2)), rel_hi = (uint32_t)(g.hash_hi - (g.line0 << kLineLog2));
+    {
+      const uint64_t line = round_line(g, 0, rec_addr);
+      load_line(line, is_whole(line, nl != 0u));
+    }
+    // the entries of the next eight steps: four are looked up (one dword of the line) as soon as four have been used up
+    uint64_t e[8];
+    lut64_4<0>(L[0], lds0, e);
+    lut64_4<1>(L[1], lds0, e);
+    auto step = [&](uint64_t ent, bool check) {
+      // :225-229 and :233-236 with the entry's pre-placed codes (see roll_records)
+      rc = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
+      fw = shl2_add64(fw, ent) & fw_mask;
+      const uint64_t canon = min62(fw, rc);   // :345
+      push_candidates(rev64_hi_mad(canon), thr, canon, top);
+      if (check && __builtin_expect(top >= bottom + 512u, 0)) {
+        drain64();
+        if (top >= bottom + 512u) drain64();
+      }
+    };
+    // the same step for a lane whose hash bytes in the line are [wlo, wlo + wn): pos = the step's byte - wlo (wraps below
+    // wlo).  The empty asm keeps the compare inside its step: sixteen lane masks computed ahead would take 32 scalar registers.
+    auto step_pred = [&](uint64_t ent, uint32_t &pos, uint32_t wn, bool check) {
+      asm volatile("" : "+v"(pos));
+      const bool live = pos < wn;
+      pos += 1u;
+      const uint64_t rc2 = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
+      const uint64_t fw2 = shl2_add64(fw, ent) & fw_mask;
+      rc = live ? rc2 : rc;
+      fw = live ? fw2 : fw;
+      const uint64_t canon = min62(fw, rc);
+      const uint32_t hh = rev64_hi_mad(canon);
+      push_candidates(live ? hh : 0xFFFFFFFFu, thr, canon, top);
+      if (check && __builtin_expect(top >= bottom + 512u, 0)) {
+        drain64();
+        if (top >= bottom + 512u) drain64();
+      }
+    };
+    for (uint32_t rd = 0; rd < nl_max; ++rd) {
+      // the lane's hash bytes in this line: [wlo, wlo + wn)
+      const uint32_t off = rd << kLineLog2;   // (a lane's run is far shorter than 4 GB)
+      const uint32_t wlo = rel_lo > off ? rel_lo - off : 0u;
+      const uint32_t whi = rel_hi > off ? (rel_hi - off < (uint32_t)kLineBytes ? rel_hi - off : (uint32_t)kLineBytes) : 0u;
+      const uint32_t wn = rd < nl && whi > wlo ? whi - wlo : 0u;
+      const bool plain = __all(wn == (uint32_t)kLineBytes) != 0;
+      // the next round's line, requested in this line's last pass
+      auto request_next = [&]() {
+        if (rd + 1u < nl_max) {   // (uniform)
+          const uint64_t line = round_line(g, rd + 1u, rec_addr);
+          load_line(line, is_whole(line, rd + 1u < nl));
+        }
+      };
+      // A pass of the loops below is 16 steps = four dwords of the line; the entries of dword n are looked up behind
+      // the steps of dword n - 2.  The line's last pass looks up its last two dwords from copies and the next line's
+      // first two from the registers that the next line is loaded into: the request goes out 12 steps before its first
+      // bytes are needed, and with every byte of this line already looked up or copied.
+#define NQ_LINE_PASS(STEP, D0, D1, D2, D3)                 \
+  do {                                                     \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) STEP(j); \
+    lut64_4<0>(D0, lds0, e);                               \
+    _Pragma("unroll") for (int j = 4; j < 8; ++j) STEP(j); \
+    lut64_4<1>(D1, lds0, e);                               \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) STEP(j); \
+    lut64_4<0>(D2, lds0, e);                               \
+    _Pragma("unroll") for (int j = 4; j < 8; ++j) STEP(j); \
+    lut64_4<1>(D3, lds0, e);                               \
+  } while (0)
+      if (plain) {
+#define NQ_STEP(J) step(e[J], ((J) & 1) != 0)
+        for (uint32_t it = 0; it < 7u; ++it)
+          NQ_LINE_PASS(NQ_STEP, dword_at(4u * it + 2u), dword_at(4u * it + 3u), dword_at(4u * it + 4u), dword_at(4u * it + 5u));
+        const uint32_t t0 = L[30], t1 = L[31];
+        request_next();
+        NQ_LINE_PASS(NQ_STEP, t0, t1, L[0], L[1]);
+#undef NQ_STEP
+      } else {
+        uint32_t pos = 0u - wlo;
+#define NQ_STEP(J) step_pred(e[J], pos, wn, ((J) & 1) != 0)
+        for (uint32_t it = 0; it < 7u; ++it)
+          NQ_LINE_PASS(NQ_STEP, dword_at(4u * it + 2u), dword_at(4u * it + 3u), dword_at(4u * it + 4u), dword_at(4u * it + 5u));
+        const uint32_t t0 = L[30], t1 = L[31];
+        request_next();
+        NQ_LINE_PASS(NQ_STEP, t0, t1, L[0], L[1]);
+#undef NQ_STEP
+      }
+#undef NQ_LINE_PASS
+    }
+  }
+  if (top != bottom) {   // fewer than 64 left
+    const uint32_t n = (top - bottom) >> 3;
+    const bool live = lane < n;
+    const uint64_t c = live ? stack[lane] : 0ull;
+    candidate_update(c, d, lds0, live);
+  }
+}
+
 // GROUPS 16-byte groups of hash steps per chunk: CHUNK = 16*GROUPS k-mers.
 #ifdef NQ_SKETCH_CLOCK
 __device__ unsigned long long nq_sketch_clk[2];   // shader cycles / 100 MHz ticks spent by one workgroup (tools/ubench_sketch.hip)
@@ -720,6 +993,8 @@ __global__ __launch_bounds__(BLOCK) void sketch_kernel(SketchArgs a) {
     if (thr) {
       // the generic filtered form also serves a layout that does not start at LDS address 0
       if (hsel || lds0 != 0) roll_records<BLOCK, GROUPS, KFIX, true, true, false>(a, entry, part, sk, lut, (uint64_t *)aux, thr, hsel);
+      // the longest records' shape: whole lines per lane
+      else if (GROUPS == 32 && (KFIX == 31 || (d.K >= kFastKMin && d.K <= kLineFastKMax))) roll_records_lines<BLOCK, KFIX>(a, entry, part, lut, (uint64_t *)aux, thr);
       else roll_records<BLOCK, GROUPS, KFIX, true, false, true>(a, entry, part, sk, lut, (uint64_t *)aux, thr, 0);
       __syncthreads();
       uint32_t local = 0;

@@ -3,7 +3,7 @@
 
     python tools/sketch_cost_model.py <nq_sketch gfx950 .s> profiles/r03_opcode_costs.csv [measured_cycles_per_step]
 
-Finds the K = 31 filtered fast loop of nq::sketch_kernel<1024, 32, 31> (the group loop: 16 k-mer
+Finds the K = 31 filtered fast loop of nq::sketch_kernel<1024, 32, 31> (the pass loop of the line form: 16 k-mer
 steps, 16 candidate pushes, drains laid out behind it), counts its instructions per opcode,
 prices every vector opcode with the issue cost measured by tools/ubench_opcodes.hip (SIMD cycles
 per wave instruction with 4 waves per SIMD) and prints the per-k-mer-step total next to the
@@ -76,24 +76,23 @@ def main():
     uniform = cost.get("LSHL_ADD_U32", 4.3)
     k = kernel_lines(spath, "sketch_kernelILi1024ELi32ELi31")
     push = [i for i, l in enumerate(k) if "s_lshl3_add_u32" in l]
-    # the fast loop: 16 pushes in a row with no ds_min between them
-    best = None
+    # the fast loop: 16 pushes in a row with no ds_min between them, inside the tightest loop (label .. backward branch)
+    # around any such run -- the line loop's pass of 16 steps; the peeled last pass of a line, which only the round loop
+    # encloses, is left out by that
+    labels = {m.group(1): i for i, l in enumerate(k) for m in [re.match(r"^(\.LBB\S+):", l)] if m}
+    start = end = None
     for a in range(len(push) - 15):
         seg = k[push[a]:push[a + 15] + 1]
         if any("ds_min_u32" in l for l in seg) or any("v_mul_lo_u32" in l for l in seg):
             continue
-        if best is None or push[a + 15] - push[a] < best[1] - best[0]:
-            best = (push[a], push[a + 15])
-    assert best, "fast loop not found"
-    # extend to the loop: back to the label the loop's backward branch targets, forward to that branch
-    labels = {m.group(1): i for i, l in enumerate(k) for m in [re.match(r"^(\.LBB\S+):", l)] if m}
-    end = None
-    for i in range(best[1], min(best[1] + 400, len(k))):
-        m = re.match(r"\s+s_cbranch_\S+\s+(\.LBB\S+)", k[i])
-        if m and labels.get(m.group(1), 1 << 30) < best[0]:
-            end, start = i, labels[m.group(1)]
-            break
-    assert end is not None, "loop branch not found"
+        # extend to the loop: back to the label the loop's backward branch targets, forward to that branch
+        for i in range(push[a + 15], min(push[a + 15] + 400, len(k))):
+            m = re.match(r"\s+s_c?branch\S*\s+(\.LBB\S+)", k[i])
+            if m and labels.get(m.group(1), 1 << 30) < push[a]:
+                if end is None or i - labels[m.group(1)] < end - start:
+                    end, start = i, labels[m.group(1)]
+                break
+    assert end is not None, "fast loop not found"
     loop = ops_of(k[start:end + 1])
     rows, a, b = price(loop, cost, uniform)
     nv = sum(n for op, (n, _, _) in rows.items())
