@@ -485,6 +485,28 @@ int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_
 int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts,
                       uint32_t *n_representatives, int mem);
 
+/* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
+ * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
+ * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses
+ * keep / new_ids in place, in stream order.  The call synchronises once (the kept count sizes the new store).
+ * Definition: after the call the handle is indistinguishable, through every call of this header, from a fresh handle
+ * with the same parameters and options into which niqki_get_sketches of the kept genomes was inserted in ascending
+ * old-id order.  So a kept genome's new id is the number of kept genomes below it; niqki_genome_count,
+ * niqki_get_sketches, every query call, niqki_matrix_range, the self-join calls and the dump bytes are those of that
+ * fresh handle; genomes inserted afterwards get ids from n_kept on; min_score, top_k and all options are untouched.
+ * All kept: nothing changes (a built index stays built, new_ids is the identity).  None kept: an empty, usable index.
+ * No genomes: NIQKI_OK, *n_kept = 0.  Handles as niqki_cluster: whole-range single-GPU handles, resident or paged,
+ * S <= 16; NIQKI_E_STATE on a slot-range shard.  Groups cannot drop genomes (out of scope: build a single-GPU index).
+ * NIQKI_E_NOMEM (the new store could not be allocated): the genome set is unchanged, the index is rebuilt on the next
+ * use, the handle stays consistent.
+ * A rank pass turns the flags into ids and per-block destinations, a kernel compacts the kept columns of the sketch
+ * store into a new, smaller one, and the inverted index (both segments) is dropped: the next use builds one main
+ * segment (stats "store_bytes" shrinks, "delta_genomes" reads 0).  A paged handle's store is host memory and is
+ * compacted in place by the host.  Staged batches and batches sketched ahead are untouched.
+ * While profiling is on the call times its two device phases with events: "retain_us_rank", "retain_us_compact"
+ * (microseconds, the last call; tools/bench_retain.py). */
+int niqki_retain(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32_t *n_kept, int mem);
+
 /* dump_index_disk payload (src/niqki_index.cpp:42-55), before gzip and
  * without the trailing names: 6 x u32 header {lF,K,H,W,min_score,N} then per
  * bucket u32 size + size x u32 gid, buckets in fp + slot*2^W order, gids

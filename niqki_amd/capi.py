@@ -118,6 +118,7 @@ ABI = [
     ("niqki_neighbors_range", _int, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, _int]),
     ("niqki_cluster", _int, [_vp, _u32, _vp, C.POINTER(_u32), _int]),
     ("niqki_dereplicate", _int, [_vp, _u32, _vp, _vp, C.POINTER(_u32), _int]),
+    ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
     ("niqki_export_dump_header", _int, [_vp, _vp]),
@@ -554,6 +555,18 @@ class Engine:
         n = _u32(0)
         self._ck(self.L.niqki_dereplicate(self.h, int(threshold), _p(labels), _p(lc) if counts else None, C.byref(n), MEM_HOST))
         return (labels, lc, int(n.value)) if counts else (labels, int(n.value))
+
+    def retain(self, keep):
+        """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),
+        new_ids[g] = the new id of old genome g (the kept genomes below it), 0xFFFFFFFF for a dropped one.  The handle
+        then equals a fresh one holding the kept genomes in their old order."""
+        k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8).reshape(-1)
+        if k.size != self.n_genomes:
+            raise ValueError("retain: %d keep flags for %d genomes" % (k.size, self.n_genomes))
+        ids = np.empty(k.size, dtype=np.uint32)
+        n = _u32(0)
+        self._ck(self.L.niqki_retain(self.h, _p(k) if k.size else None, _p(ids) if k.size else None, C.byref(n), MEM_HOST))
+        return int(n.value), ids
 
     def get_sketches(self, begin, n):
         out = np.empty((n, self.F), dtype=np.int32)

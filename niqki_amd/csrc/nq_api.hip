@@ -574,6 +574,9 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "derep_us_decide")) { *value = (uint64_t)(ix->derep_stats.ms[2] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "derep_us_assign")) { *value = (uint64_t)(ix->derep_stats.ms[3] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "derep_pairs")) { *value = ix->derep_stats.pairs; return NIQKI_OK; }
+  // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
+  if (!std::strcmp(key, "retain_us_rank")) { *value = (uint64_t)(ix->retain_ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "retain_us_compact")) { *value = (uint64_t)(ix->retain_ms[1] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "inflate_files_in_flight") || !std::strcmp(key, "inflate_files_in_flight_8k")) {
     // how many files a launch of the device inflate runs at once (workgroups the device keeps resident), by kernel form
     (void)hipSetDevice(ix->device);

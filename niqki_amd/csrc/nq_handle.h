@@ -117,6 +117,8 @@ struct niqki_index {
   // the last niqki_cluster / niqki_dereplicate call (stats "cluster_*", "derep_*").  ms, while profiling is on: store
   // read, gather + hits, then link and flatten (cluster) or decide and assign (derep)
   nqi::SelfJoinStats cluster_stats, derep_stats;
+  // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
+  double retain_ms[2] = {0, 0};
 
   nqi::Buf ws_seq, ws_recoff, ws_entry, ws_sk, ws_counts, ws_blk, ws_hitoff, ws_hc, ws_hg, ws_tc, ws_tg,
       ws_misc, ws_stash, ws_hl, ws_parent;

@@ -93,6 +93,148 @@ hipError_t launch_store_read(const Derived &d, const uint16_t *store, uint64_t c
   return hipGetLastError();
 }
 
+// ---- niqki_retain: keep flags -> ranks, then the kept columns of every store row to the front of a NEW store ----
+// Block arithmetic and the destination's 16-byte grid: nq_retain_blocks.h.
+//
+// Rank pass, step 1: per block of kRetainBlock columns its keep bits as 64-bit words and its kept count (blk_dst[b]).
+__global__ __launch_bounds__(256) void retain_words_kernel(const uint8_t *keep, uint32_t n, unsigned long long *words,
+                                                          uint32_t *blk_dst) {
+  __shared__ uint32_t part[4];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t c0 = (uint64_t)blockIdx.x * kRetainBlock;
+  uint32_t cnt = 0;
+  for (uint32_t w = wave; w < kRetainWords; w += 4) {
+    const uint64_t c = c0 + w * 64 + lane;
+    const unsigned long long m = __ballot(c < n && keep[c] != 0);
+    if (lane == 0) words[(uint64_t)blockIdx.x * kRetainWords + w] = m;
+    cnt += (uint32_t)__popcll(m);
+  }
+  if (lane == 0) part[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) blk_dst[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// step 2: the kept counts, in place, into each block's first destination column; blk_dst[n_blocks] = the total
+__global__ __launch_bounds__(64) void retain_scan_kernel(uint32_t *blk_dst, uint32_t n_blocks) {
+  const uint32_t lane = threadIdx.x;
+  uint32_t run = 0;
+  for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64) {
+    const uint32_t b = b0 + lane;
+    const uint32_t x = b < n_blocks ? blk_dst[b] : 0u;
+    const uint32_t incl = wave_incl_scan(x, lane);
+    if (b < n_blocks) blk_dst[b] = run + incl - x;
+    run += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) blk_dst[n_blocks] = run;
+}
+
+// a block's keep words and the kept columns below each word into LDS (all threads; ends with a barrier)
+__device__ __forceinline__ void retain_block_ranks(const unsigned long long *words, uint64_t *w_s, uint32_t *rank_s) {
+  if (threadIdx.x < 64) {
+    const uint64_t w = words[threadIdx.x];
+    const uint32_t x = (uint32_t)__popcll(w);
+    w_s[threadIdx.x] = w;
+    rank_s[threadIdx.x] = wave_incl_scan(x, threadIdx.x) - x;
+  }
+  __syncthreads();
+}
+
+// step 3 (only where the caller wants them): every genome's new id, 0xFFFFFFFF for a dropped one
+__global__ __launch_bounds__(256) void retain_ids_kernel(const unsigned long long *words, const uint32_t *blk_dst, uint32_t n,
+                                                        uint32_t *new_ids) {
+  __shared__ uint64_t w_s[kRetainWords];
+  __shared__ uint32_t rank_s[kRetainWords];
+  retain_block_ranks(words + (uint64_t)blockIdx.x * kRetainWords, w_s, rank_s);
+  const uint64_t c0 = (uint64_t)blockIdx.x * kRetainBlock;
+  const uint32_t dst0 = blk_dst[blockIdx.x];
+  for (uint32_t i = threadIdx.x; i < kRetainBlock && c0 + i < n; i += 256)
+    new_ids[c0 + i] = ((w_s[i >> 6] >> (i & 63u)) & 1u) ? dst0 + retain_rank(w_s, rank_s, i) : 0xFFFFFFFFu;
+}
+
+hipError_t launch_retain_ranks(const uint8_t *keep, uint32_t n, unsigned long long *words, uint32_t *blk_dst, uint32_t *new_ids,
+                               hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint32_t n_blocks = (uint32_t)(((uint64_t)n + kRetainBlock - 1) / kRetainBlock);
+  hipLaunchKernelGGL(retain_words_kernel, dim3(n_blocks), dim3(256), 0, stream, keep, n, words, blk_dst);
+  hipLaunchKernelGGL(retain_scan_kernel, dim3(1), dim3(64), 0, stream, blk_dst, n_blocks);
+  if (new_ids) hipLaunchKernelGGL(retain_ids_kernel, dim3(n_blocks), dim3(256), 0, stream, words, blk_dst, n, new_ids);
+  return hipGetLastError();
+}
+
+// Compaction: workgroup (b, y) moves source block b of slot rows [y * rows_per, ...) -- out of place: a block's
+// destination range overlaps source columns of lower blocks that another workgroup may not have read yet.  The ranks of
+// the thread's two groups of 8 columns come from the keep words once and serve every row.  Per row: 16-byte loads of
+// the groups that keep anything (the next row's are issued before this one is compacted), the kept elements into
+// the LDS image at off + rank, a barrier, then the image out along the destination's 16-byte grid (RetainSpan).  Two
+// images in turn: the barrier of row r + 1 lies between the reads of row r and the writes of row r + 2.
+__device__ __forceinline__ void retain_scatter8(uint16_t *at, const uint4 &v, uint32_t m) {
+  const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (uint32_t e = 0; e < 8; ++e) {
+    if ((m >> e) & 1u) *at++ = (uint16_t)(x[e >> 1] >> ((e & 1u) * 16u));
+  }
+}
+
+__global__ __launch_bounds__(256) void store_compact_kernel(const uint16_t *src, uint64_t src_cap, uint16_t *dst, uint64_t dst_cap,
+                                                           uint32_t f_local, uint32_t rows_per, const unsigned long long *words,
+                                                           const uint32_t *blk_dst) {
+  __shared__ uint64_t w_s[kRetainWords];
+  __shared__ uint32_t rank_s[kRetainWords];
+  __shared__ __align__(16) uint16_t img[2][kRetainImage];
+  const uint32_t b = blockIdx.x, tid = threadIdx.x;
+  const uint32_t dst0 = blk_dst[b], kept = blk_dst[b + 1] - dst0;
+  if (kept == 0) return;   // the whole workgroup: a block with nothing kept reads nothing
+  retain_block_ranks(words + (uint64_t)b * kRetainWords, w_s, rank_s);
+  const RetainSpan sp = retain_span(dst0, kept);
+  uint32_t m[2], at[2];
+#pragma unroll
+  for (uint32_t k = 0; k < 2; ++k) {
+    const uint32_t c = (tid + 256u * k) * 8u;
+    m[k] = (uint32_t)(w_s[c >> 6] >> (c & 63u)) & 0xFFu;   // (a group with a kept column lies below the source's capacity)
+    at[k] = sp.off + retain_rank(w_s, rank_s, c);
+  }
+  const uint32_t r0 = blockIdx.y * rows_per, r1 = r0 + rows_per < f_local ? r0 + rows_per : f_local;
+  const uint16_t *s = src + (uint64_t)r0 * src_cap + (uint64_t)b * kRetainBlock + tid * 8u;
+  uint16_t *d = dst + (uint64_t)r0 * dst_cap + (dst0 - sp.off);   // image element 0: a multiple of 8 columns
+  uint4 cur[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)}, nxt[2] = {cur[0], cur[0]};
+#pragma unroll
+  for (uint32_t k = 0; k < 2; ++k)
+    if (m[k]) cur[k] = *(const uint4 *)(s + 2048u * k);
+  for (uint32_t r = r0; r < r1; ++r) {
+    if (r + 1 < r1) {
+#pragma unroll
+      for (uint32_t k = 0; k < 2; ++k)
+        if (m[k]) nxt[k] = *(const uint4 *)(s + src_cap + 2048u * k);
+    }
+    uint16_t *im = img[(r - r0) & 1u];
+    retain_scatter8(im + at[0], cur[0], m[0]);
+    retain_scatter8(im + at[1], cur[1], m[1]);
+    __syncthreads();
+    for (uint32_t p = tid; p < sp.pieces; p += 256) {
+      if (p >= sp.whole_lo && p < sp.whole_hi) {
+        *(uint4 *)(d + p * 8u) = *(const uint4 *)(im + p * 8u);
+      } else {
+        for (uint32_t i = p * 8u; i < p * 8u + 8u; ++i)
+          if (i >= sp.off && i < sp.end) d[i] = im[i];
+      }
+    }
+    cur[0] = nxt[0];
+    cur[1] = nxt[1];
+    s += src_cap;
+    d += dst_cap;
+  }
+}
+
+hipError_t launch_store_compact(const uint16_t *src, uint64_t src_cap, uint32_t n_src, uint16_t *dst, uint64_t dst_cap,
+                                uint32_t f_local, const unsigned long long *words, const uint32_t *blk_dst, hipStream_t stream) {
+  if (n_src == 0 || f_local == 0) return hipSuccess;
+  const uint32_t n_blocks = (uint32_t)(((uint64_t)n_src + kRetainBlock - 1) / kRetainBlock);
+  const uint32_t rows_per = 16;   // the ranks are derived once per workgroup: enough rows to make that nothing
+  hipLaunchKernelGGL(store_compact_kernel, dim3(n_blocks, (f_local + rows_per - 1) / rows_per), dim3(256), 0, stream, src, src_cap,
+                     dst, dst_cap, f_local, rows_per, words, blk_dst);
+  return hipGetLastError();
+}
+
 // ---- index build: one wave per (tile, slot) row, stable counting sort on fp ----
 // FILL = false: units (1 << align_log2 ids) the row needs -> slot_units[t][s]
 // FILL = true : entries {start, len} of every fingerprint + the ascending id lists

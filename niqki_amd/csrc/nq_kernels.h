@@ -2,6 +2,7 @@
 // gfx950 kernels.  All pointers are device pointers unless noted.
 #pragma once
 #include "nq_common.h"
+#include "nq_retain_blocks.h"
 
 namespace nq {
 
@@ -110,6 +111,15 @@ hipError_t launch_store_insert(const Derived &d, const int32_t *sketches, uint32
                                hipStream_t stream);
 hipError_t launch_store_read(const Derived &d, const uint16_t *store, uint64_t cap,
                              uint32_t begin, uint32_t n, int32_t *sketches, hipStream_t stream);
+// niqki_retain (nq_retain_blocks.h: blocks of kRetainBlock source columns).  Rank pass: keep[n] flags (nonzero = stays)
+// -> words (kRetainWords per block: its keep bits), blk_dst (n_blocks + 1: each block's first destination column, then
+// the kept total) and, where new_ids is not null, every genome's new id (0xFFFFFFFF: dropped).
+hipError_t launch_retain_ranks(const uint8_t *keep, uint32_t n, unsigned long long *words, uint32_t *blk_dst, uint32_t *new_ids,
+                               hipStream_t stream);
+// ... then the kept columns of the n_src columns of every row, in order, to the front of ANOTHER store (dst_cap >= the
+// kept total; both capacities multiples of 8 columns, both stores 16-byte aligned)
+hipError_t launch_store_compact(const uint16_t *src, uint64_t src_cap, uint32_t n_src, uint16_t *dst, uint64_t dst_cap,
+                                uint32_t f_local, const unsigned long long *words, const uint32_t *blk_dst, hipStream_t stream);
 // Build, phase 1: units per (tile, slot) -> exclusive prefix per tile in
 // slot_units, tile totals as a prefix (in ids) in tile_base.
 hipError_t launch_build_sizes(const IndexView &v, uint32_t *slot_units, uint64_t *tile_base,

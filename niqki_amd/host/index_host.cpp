@@ -24,6 +24,7 @@
 #include <memory>
 #include <stdexcept>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../csrc/nq_pack.h"
@@ -109,6 +110,7 @@ Index::Index(uint32_t ilF, uint32_t iK, uint32_t iW, uint32_t iH, const std::str
     if (rc) throw std::runtime_error(std::string("niqki_group_create: ") + niqki_status_string(rc) + " (" + niqki_last_error(h_) + ")");
   }
   K = iK; W = iW; H = iH; lF = ilF; F = 1u << ilF; min_score = p.min_score;
+  out_path_ = out_filename;
   outfile.reset(new ParallelTextWriter(out_filename, host_threads()));
 }
 
@@ -192,6 +194,7 @@ Index::Index(const std::string &dump_file, bool pretty, const std::string &out_f
     const int rc = niqki_group_create(sh_.data(), (uint32_t)sh_.size(), 0, (uint32_t)sh_.size(), nullptr, &grp_);
     if (rc) throw std::runtime_error(std::string("niqki_group_create: ") + niqki_status_string(rc) + " (" + niqki_last_error(h_) + ")");
   }
+  out_path_ = out_filename;
   outfile.reset(new ParallelTextWriter(out_filename, host_threads()));
 }
 
@@ -978,11 +981,14 @@ using cluster_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, int)
 using derep_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, int);
 neighbors_fn engine_neighbors() { return (neighbors_fn)dlsym(RTLD_DEFAULT, "niqki_neighbors_range"); }
 cluster_fn engine_cluster() { return (cluster_fn)dlsym(RTLD_DEFAULT, "niqki_cluster"); }
+using retain_fn = int (*)(niqki_index *, const uint8_t *, uint32_t *, uint32_t *, int);
 derep_fn engine_derep() { return (derep_fn)dlsym(RTLD_DEFAULT, "niqki_dereplicate"); }
+retain_fn engine_retain() { return (retain_fn)dlsym(RTLD_DEFAULT, "niqki_retain"); }
 }  // namespace
 
 bool Index::has_self_join() { return engine_neighbors() != nullptr && engine_cluster() != nullptr; }
 bool Index::has_dereplication() { return engine_derep() != nullptr; }
+bool Index::has_retain() { return engine_retain() != nullptr; }
 
 void Index::query_neighbors() {
   const neighbors_fn call = engine_neighbors();
@@ -1045,7 +1051,7 @@ void Index::cluster_to_file(const std::string &filestr) {
   write_groups(filestr, labels);
 }
 
-void Index::dereplicate_to_file(const std::string &filestr) {
+void Index::dereplicate(const std::string &list_file, const std::string &dump_file) {
   const derep_fn call = engine_derep();
   if (!call || grp_) throw std::runtime_error("this engine has no dereplication");
   const uint32_t N = (uint32_t)filenames.size();
@@ -1054,7 +1060,52 @@ void Index::dereplicate_to_file(const std::string &filestr) {
   std::vector<uint32_t> labels(N);
   check(call(h_, p.min_score, labels.data(), nullptr, nullptr, NIQKI_MEM_HOST), "niqki_dereplicate");
   // a representative may stand for genomes that precede it in the index: its own line still leads its group
-  write_groups(filestr, labels);
+  if (!list_file.empty()) write_groups(list_file, labels);
+  if (dump_file.empty()) return;
+  std::vector<uint8_t> keep(N);
+  for (uint32_t g = 0; g < N; ++g) keep[g] = labels[g] == g;
+  retain(keep);
+  dump_index_disk(dump_file);
+}
+
+// ---- dropping genomes ---------------------------------------------------------------
+
+void Index::retain(const std::vector<uint8_t> &keep) {
+  const retain_fn call = engine_retain();
+  if (!call || grp_) throw std::runtime_error("this engine cannot drop genomes");
+  if (keep.size() != filenames.size()) throw std::runtime_error("retain: one flag per indexed genome");
+  uint32_t n_kept = 0;
+  check(call(h_, keep.data(), nullptr, &n_kept, NIQKI_MEM_HOST), "niqki_retain");
+  size_t at = 0;
+  for (size_t g = 0; g < keep.size(); ++g)
+    if (keep[g]) {
+      if (at != g) filenames[at] = std::move(filenames[g]);
+      ++at;
+    }
+  filenames.resize(at);
+  if (at != n_kept) throw std::runtime_error("niqki_retain kept another number of genomes than asked");
+}
+
+void Index::remove_listed(const std::string &filestr) {
+  std::ifstream in(filestr);
+  if (!in) throw std::runtime_error("--remove: cannot open '" + filestr + "'");
+  std::unordered_set<std::string> listed, seen;
+  std::vector<std::string> in_order;
+  for (std::string line; std::getline(in, line);) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (!line.empty() && listed.insert(line).second) in_order.push_back(line);
+  }
+  std::vector<uint8_t> keep(filenames.size(), 1);
+  for (size_t g = 0; g < filenames.size(); ++g)
+    if (listed.count(filenames[g])) { keep[g] = 0; seen.insert(filenames[g]); }
+  for (const std::string &name : in_order)
+    if (!seen.count(name)) {
+      // refused before anything is written: the output file the constructor made goes away again
+      outfile->close();
+      (void)::unlink(out_path_.c_str());
+      throw std::runtime_error("--remove: no indexed genome is named '" + name + "'");
+    }
+  if (!listed.empty()) retain(keep);
 }
 
 // ---- dump ------------------------------------------------------------------------

@@ -69,7 +69,18 @@ class Index {
   // greedy representatives at min_score in index order, as lines representative<TAB>member: groups in the order of
   // their representative's index position, the representative's own line first, then its members in index order
   static bool has_dereplication();
-  void dereplicate_to_file(const std::string &filestr);
+  void dereplicate_to_file(const std::string &filestr) { dereplicate(filestr, ""); }
+  // Dropping genomes (long options --remove / --derep-dump; single-GPU index; niqki_retain, looked up at run time like
+  // the calls above).  retain: the genomes with a zero flag leave the engine's index and `filenames`; the rest keep
+  // their order.  remove_listed: drops every genome that carries a name of the file (one per line); a name no genome
+  // carries is an error, and then nothing is written, the -O file included.
+  static bool has_retain();
+  void retain(const std::vector<uint8_t> &keep);
+  void remove_listed(const std::string &filestr);
+  // ONE niqki_dereplicate call for --derep and --derep-dump: the list of the full index into list_file (unless empty),
+  // then, unless dump_file is empty, only the representatives are retained and dumped there (dump_index_disk); the
+  // index in memory is the dereplicated one from then on
+  void dereplicate(const std::string &list_file, const std::string &dump_file);
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
@@ -95,6 +106,7 @@ class Index {
   void query_staged(size_t n, Hits &h);
   void write_hits(const Hits &h);
   std::string out_text_;                // write_hits' lines before they go to the writer
+  std::string out_path_;                // the -O file (remove_listed takes it away again when it refuses)
   void stream_lines(const std::string &filestr, bool insert);
   void check(int rc, const char *what) const;
   void check_group(int rc, const char *what) const;

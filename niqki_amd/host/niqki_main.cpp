@@ -10,6 +10,9 @@
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
 //   --derep <f>    greedy representatives at the -J threshold, in index order, into f: representative<TAB>member
 //                  (niqki_dereplicate); the lines whose two names are equal are the dereplicated list
+//   --remove <f>   drop every indexed genome named in f (one name per line) before -D and the queries (niqki_retain)
+//   --derep-dump <f>  dereplicate at the -J threshold, keep the representatives only and dump that index into f (as -D);
+//                  the rest of the run (-M, --neighbors, -Q, -l) is answered by the dereplicated index
 #include <libgen.h>
 #include <limits.h>
 #include <unistd.h>
@@ -36,7 +39,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -69,6 +72,8 @@ const Desc kDesc[] = {
     {NEIGHBORS, "", "neighbors", NONE, "  --neighbors                   Query the index with its own genomes, in index order (output as -Q)."},
     {CLUSTER, "", "cluster", NONEMPTY, "  --cluster <filename>          Single-linkage clusters at the -J threshold: lines representative<TAB>member."},
     {DEREP, "", "derep", NONEMPTY, "  --derep <filename>            Dereplication at the -J threshold: greedy representatives in index order, lines representative<TAB>member."},
+    {REMOVE, "", "remove", NONEMPTY, "  --remove <filename>           Drop the indexed genomes named in the file (one name per line) before -D and the queries."},
+    {DEREP_DUMP, "", "derep-dump", NONEMPTY, "  --derep-dump <filename>       Dereplicate at the -J threshold and dump the index of the representatives (as -D); the rest of the run is answered by that index."},
 };
 
 struct Parsed {
@@ -275,17 +280,22 @@ int main(int argc, char *argv[]) {
     top_k = (uint32_t)v;
   }
 
-  // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts
-  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP)) {
+  // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts; and only a
+  // single-GPU index can drop genomes
+  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP)) {
     if (n_gpus > 1) {
       cerr << "niqki: the self-join (--neighbors, --cluster, --derep) needs a single-GPU index (--gpus 1)" << endl;
+      return EXIT_FAILURE;
+    }
+    if ((o.has(REMOVE) || o.has(DEREP_DUMP)) && !nqhost::Index::has_retain()) {
+      cerr << "niqki: this engine cannot drop genomes" << endl;
       return EXIT_FAILURE;
     }
     if ((o.has(NEIGHBORS) || o.has(CLUSTER)) && !nqhost::Index::has_self_join()) {
       cerr << "niqki: this engine has no self-join" << endl;
       return EXIT_FAILURE;
     }
-    if (o.has(DEREP) && !nqhost::Index::has_dereplication()) {
+    if ((o.has(DEREP) || o.has(DEREP_DUMP)) && !nqhost::Index::has_dereplication()) {
       cerr << "niqki: this engine has no dereplication" << endl;
       return EXIT_FAILURE;
     }
@@ -304,16 +314,24 @@ int main(int argc, char *argv[]) {
     RunClock clk;
     for (const Phase &ph : kIndexPhases) run_phase(*ix, o, ph);
     if (o.has(DOWNLAD)) cout << "--indexdownload needs network access and is not part of this build" << endl;
+    RunClock::tp remove_begin, remove_end;
+    if (o.has(REMOVE)) {   // after everything that indexes, before the dump: -L old --remove names -D new
+      remove_begin = system_clock::now();
+      ix->remove_listed(o.last(REMOVE));
+      remove_end = system_clock::now();
+    }
     if (o.has(DUMP)) ix->dump_index_disk(o.last(DUMP));
     clk.index_done();
+    if (o.has(REMOVE)) RunClock::row("| Remove lasted (s)                 |", remove_begin, remove_end);
     if (o.has(CLUSTER)) {   // a phase of its own between indexing and the queries
       ix->cluster_to_file(o.last(CLUSTER));
       const RunClock::tp now = system_clock::now();
       RunClock::row("| Cluster lasted (s)                |", clk.index_end, now);
       clk.index_end = now;
     }
-    if (o.has(DEREP)) {   // ... and so is the dereplication, after the clusters where both are asked for
-      ix->dereplicate_to_file(o.last(DEREP));
+    if (o.has(DEREP) || o.has(DEREP_DUMP)) {   // ... and so is the dereplication, after the clusters where both are asked for
+      // one engine call for the list and the dump; after --derep-dump the index in memory is the dereplicated one
+      ix->dereplicate(o.has(DEREP) ? o.last(DEREP) : string(), o.has(DEREP_DUMP) ? o.last(DEREP_DUMP) : string());
       const RunClock::tp now = system_clock::now();
       RunClock::row("| Dereplication lasted (s)          |", clk.index_end, now);
       clk.index_end = now;
