@@ -332,6 +332,8 @@ constexpr uint32_t kLut64Off = 0;       // 256 x {forward code, rc code << 30}
 constexpr uint32_t kLutOff = 2048;      // 256 code_entry bytes
 constexpr uint32_t kFlagOff = 2304;     // 4 words
 constexpr uint32_t kCellOff = 2320;     // the sketch cells; behind them the distinct-value tables or the candidate stacks
+constexpr uint32_t kLevelStateWords = 8;   // line form: a wave's own leveling state, behind its stack
+constexpr uint32_t kLevelLdsBytes = 4 * kLevelWords + 16 * 4 * kLevelStateWords;   // ... and behind the 16 stacks the progress words
 
 // byte B of w, times 8: the offset of its 8-byte code table entry
 template <int B>
@@ -690,6 +692,13 @@ __device__ __forceinline__ uint4 replace16(const uint4 &v, int dlt) {
   return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
 }
 
+#ifdef NQ_SKETCH_CLOCK
+// per workgroup of the line form: the 100 MHz tick before the loop, the one behind the barrier after it, and the tick at
+// which each of its 16 waves leaves roll_records_lines (tools/ubench_sketch.hip: finish times per SIMD)
+constexpr uint32_t kWaveTraceWgs = 512;
+__device__ unsigned long long nq_sketch_wave[18 * kWaveTraceWgs];
+#endif
+
 // All records of one sketch, this workgroup's part, with the geometry of nq_sketch_lines.h: every lane owns one run
 // of whole 128-byte lines of a record part, fetches each line once with eight back-to-back 16-byte loads and takes
 // its 128 hash steps from registers: no re-alignment, no line shared between lanes, one warm-up per lane and
@@ -704,9 +713,13 @@ __device__ __forceinline__ uint4 replace16(const uint4 &v, int dlt) {
 // line_inside, clamp_piece), which the CPU test walks against the buffer.  Addresses become pointers as offsets from
 // a.seqs: a pointer made from a bare integer would lose the global address space, and its loads would be flat loads,
 // which the LDS look-ups' lgkmcnt waits wait for too.
+// LEVELING (nq_sketch_lines.h): at the head of a round at which its progress has moved a step, and only there, a wave
+// writes the progress to its word of the sixteen at LDS address `level_lds`, reads the four words of its SIMD and sets
+// its issue priority by level_prio().  No wave waits for a word and no branch depends on another wave's: the words
+// only choose the operand of s_setprio.  n_entry: the entry's hash bytes, the n the filter strength comes from.
 template <int BLOCK, int KFIX>
 __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t entry, uint32_t part, const uint8_t *lut,
-                                   uint64_t *stack_base, uint32_t thr) {
+                                   uint64_t *stack_base, uint32_t thr, uint64_t n_entry, uint32_t level_lds) {
   const Derived &d = a.d;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t Km1 = d.K - 1u;
@@ -714,7 +727,7 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
   const uint32_t mask_hi = KFIX == 31 ? 0x3FFFFFFFu : __builtin_amdgcn_readfirstlane((uint32_t)(d.kmer_mask >> 32));
   const uint64_t fw_mask = ((uint64_t)mask_hi << 32) | 0xFFFFFFFFull;
   constexpr uint32_t lds0 = 0;
-  uint64_t *stack = stack_base + (tid >> 6) * kStack;
+  uint64_t *stack = stack_base + (tid >> 6) * (kStack + kLevelStateWords / 2);   // (behind every stack: the wave's leveling state)
   const uint32_t bottom = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_u64_t *)stack);
   uint32_t top = bottom;
   const uint32_t lane8 = lane * 8u;
@@ -734,9 +747,85 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
   asm("" : "+s"(seqs_addr));
   const uint64_t buf_lo = seqs_addr, buf_hi = seqs_addr + end_off + NIQKI_SEQ_PAD;
   auto gptr = [&](uint64_t addr) { return a.seqs + (int64_t)(addr - seqs_addr); };
+  // leveling: the wave's own state lives in LDS too, in the eight words behind its candidate stack; its address comes from
+  // `bottom`, which the steps keep anyway.  The kernel has no register to spare across the rounds: state kept in scalar
+  // registers takes a second vector register for spilled scalars, an address kept in a vector register takes that one,
+  // and so do more than a handful of vector temporaries at the head of a round -- either way the drains then reload their
+  // lane offset from scratch.  So a look loads a few words at a time, makes scalars of them at once (all lanes of the wave
+  // read and write the same words with the same values) and computes on those.
+  //   words 0, 1: hash bytes of the records the wave is through; 2, 3: those of the current record;
+  //   4, 5: level_next(), the bytes into the record at which its progress moves next;
+  //   6: the scale's shift | the progress published last << 8; 7: LDS address of its progress word.
+  //   (The progress never passes 63 -- level_shift() puts the entry's last step there at most -- so it fits the byte and
+  //   0xFF in it means "none yet".  The SIMD's four words are the 16 bytes around the wave's own: level_word() puts them
+  //   side by side, and `level_lds` and every wave's state start at multiples of 16 bytes, as everything before them in
+  //   the layout does: kCellOff, 4 F bytes of cells (launch_sketch gives this shape no sketch of fewer than 4 cells)
+  //   and the stacks with their state.)
+  static_assert(kCellOff % 16 == 0 && (8 * kStack + 4 * kLevelStateWords) % 16 == 0 && kLevelStateWords == 8 && kLevelWords == 16,
+                "leveling: sixteen progress words and eight words of state per wave, all at multiples of 16 bytes");
+  typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) u32x2_t lds_u32x2_t;
+  typedef __attribute__((address_space(3))) u32x4_t lds_u32x4_t;
+  auto lv_fence = [&]() { asm volatile("" ::: "memory"); };   // (keeps the loads of one group apart from the next one's)
+  auto lv_pair = [&](uint32_t addr, uint64_t &x) {
+    lv_fence();
+    const u32x2_t v = *(lds_u32x2_t *)(uintptr_t)addr;
+    x = (uint64_t)__builtin_amdgcn_readfirstlane(v.x) | ((uint64_t)__builtin_amdgcn_readfirstlane(v.y) << 32);
+    lv_fence();
+  };
+  auto lv_quad = [&](uint32_t addr, uint32_t (&w)[4]) {
+    lv_fence();
+    const u32x4_t v = *(lds_u32x4_t *)(uintptr_t)addr;
+    w[0] = __builtin_amdgcn_readfirstlane(v.x); w[1] = __builtin_amdgcn_readfirstlane(v.y);
+    w[2] = __builtin_amdgcn_readfirstlane(v.z); w[3] = __builtin_amdgcn_readfirstlane(v.w);
+    lv_fence();
+  };
+  auto lv_put = [&](uint32_t addr, uint64_t x) {
+    u32x2_t v;
+    v.x = (uint32_t)x; v.y = (uint32_t)(x >> 32);
+    *(lds_u32x2_t *)(uintptr_t)addr = v;
+  };
+  auto lv_own = [&]() { return bottom + 8u * kStack; };
+  lv_put(lv_own(), 0);
+  lv_put(lv_own() + 24u, (uint64_t)(level_shift(n_entry) | 0xFF00u) | ((uint64_t)(level_lds + 4u * level_word(tid >> 6)) << 32));
+  // the look at the head of round rd of the current record
+  auto level = [&](uint32_t rd) {
+    const uint64_t in = level_round_bytes(rd, BLOCK, a.splits);
+    uint64_t next;
+    lv_pair(lv_own() + 16u, next);
+    if (in >= next) {   // (uniform)
+      uint32_t q[4];
+      uint64_t sw;
+      lv_quad(lv_own(), q);
+      lv_pair(lv_own() + 24u, sw);
+      const uint64_t done = (uint64_t)q[0] | ((uint64_t)q[1] << 32), rec_n = (uint64_t)q[2] | ((uint64_t)q[3] << 32);
+      const uint32_t shift = (uint32_t)sw & 0xFFu, last = ((uint32_t)sw >> 8) & 0xFFu, word = (uint32_t)(sw >> 32);
+      const uint32_t p = level_progress(done, rec_n, rd, BLOCK, a.splits, shift);
+      lv_put(lv_own() + 16u, level_next(done, rec_n, p, shift));
+      if (p != last) {   // a step boundary of its own progress (a record's first round is looked at whatever it brings)
+        lv_put(lv_own() + 24u, (uint64_t)(shift | (p << 8)) | ((uint64_t)word << 32));
+        *(lds_u32_t *)(uintptr_t)word = p;
+        uint32_t w[4];
+        lv_quad(word & ~15u, w);
+        const uint32_t pr = level_prio(p, w);
+        if (pr == 0u) __builtin_amdgcn_s_setprio(0);   // (the instruction takes an immediate)
+        else if (pr == 1u) __builtin_amdgcn_s_setprio(1);
+        else if (pr == 2u) __builtin_amdgcn_s_setprio(2);
+        else __builtin_amdgcn_s_setprio(3);
+      }
+    }
+  };
+  auto level_record = [&](uint64_t rec_n) { lv_put(lv_own() + 8u, rec_n); lv_put(lv_own() + 16u, 0); };
+  auto level_record_done = [&]() {
+    uint32_t q[4];
+    lv_quad(lv_own(), q);
+    lv_put(lv_own(), ((uint64_t)q[0] | ((uint64_t)q[1] << 32)) + ((uint64_t)q[2] | ((uint64_t)q[3] << 32)));
+  };
   for (uint32_t rec = r0; rec < r1; ++rec) {
     const uint64_t b0 = a.rec_off[rec], b1 = a.rec_off[rec + 1];
     if (b1 - b0 <= d.K) continue;          // src/niqki_index.cpp:395,:450
+    level_record(b1 - b0 - d.K);
     const LaneLines g = lane_lines(seqs_addr, b0, b1, d.K, a.splits, part, BLOCK,
                                    __builtin_amdgcn_readfirstlane(tid >> 6), lane);
     const uint32_t nl = g.n_lines;
@@ -747,7 +836,7 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
       nl_max = o > nl_max ? o : nl_max;
     }
     nl_max = __builtin_amdgcn_readfirstlane(nl_max);
-    if (nl_max == 0) continue;             // (uniform) no line of this record for the wave
+    if (nl_max == 0) { level_record_done(); continue; }   // (uniform) no line of this record for the wave
     const uint8_t *const base = a.seqs + b0;
     // ---- warm-up, once per lane and record (see roll_records; the 32 bytes come as two unaligned loads) ----
     uint64_t fw = 0, rc = 0;
@@ -870,6 +959,7 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
       }
     };
     for (uint32_t rd = 0; rd < nl_max; ++rd) {
+      level(rd);
       // the lane's hash bytes in this line: [wlo, wlo + wn)
       const uint32_t off = rd << kLineLog2;   // (a lane's run is far shorter than 4 GB)
       const uint32_t wlo = rel_lo > off ? rel_lo - off : 0u;
@@ -918,13 +1008,24 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
       }
 #undef NQ_LINE_PASS
     }
+    level_record_done();
   }
+  // out of the loop: the word no longer counts for the SIMD's least, and the drain and the barriers run at the kernel's own priority
+  {
+    uint64_t sw;
+    lv_pair(lv_own() + 24u, sw);
+    *(lds_u32_t *)(uintptr_t)(uint32_t)(sw >> 32) = kLevelDone;
+  }
+  __builtin_amdgcn_s_setprio(0);
   if (top != bottom) {   // fewer than 64 left
     const uint32_t n = (top - bottom) >> 3;
     const bool live = lane < n;
     const uint64_t c = live ? stack[lane] : 0ull;
     candidate_update(c, d, lds0, live);
   }
+#ifdef NQ_SKETCH_CLOCK
+  if (lane == 0 && blockIdx.x < kWaveTraceWgs) nq_sketch_wave[18 * blockIdx.x + 2 + (tid >> 6)] = wall_clock64();
+#endif
 }
 
 // GROUPS 16-byte groups of hash steps per chunk: CHUNK = 16*GROUPS k-mers.
@@ -961,6 +1062,8 @@ __global__ __launch_bounds__(BLOCK) void sketch_kernel(SketchArgs a) {
     // else unused); added into the forward word it sits above the k-mer mask
     lut64[i] = make_uint2(e & 3u, d.K >= kFastKMin ? ((e >> 2) & 3u) << (2u * d.K - 32u) : 0u);
   }
+  // the leveling words of the line form, behind the candidate stacks (only a filtered launch of that shape has them)
+  if (BLOCK == 1024 && GROUPS == 32 && a.filter && tid < kLevelWords) aux[(2 * kStack + kLevelStateWords) * (BLOCK / 64) + tid] = 0;
   if (a.accumulate) {
     const uint32_t *src = (const uint32_t *)a.sketches + (uint64_t)entry * d.F + (uint64_t)half * Fc;
     for (uint32_t i = tid; i < Fc; i += BLOCK) sk[i] = src[i];
@@ -973,8 +1076,8 @@ __global__ __launch_bounds__(BLOCK) void sketch_kernel(SketchArgs a) {
     // Filter strength from the k-mers per slot: expected undecided slots
     // F*(1-2^-T)^(n/F) must be negligible (a miss only costs the exact re-run below).
     uint32_t thr = 0;
+    uint64_t n = 0;   // the entry's k-mers = its hash bytes
     if (a.filter) {
-      uint64_t n = 0;
       const uint32_t r0 = a.entry_rec ? a.entry_rec[entry] : entry;
       const uint32_t r1 = a.entry_rec ? a.entry_rec[entry + 1] : entry + 1;
       for (uint32_t rec = r0; rec < r1; ++rec) {
@@ -994,9 +1097,18 @@ __global__ __launch_bounds__(BLOCK) void sketch_kernel(SketchArgs a) {
       // the generic filtered form also serves a layout that does not start at LDS address 0
       if (hsel || lds0 != 0) roll_records<BLOCK, GROUPS, KFIX, true, true, false>(a, entry, part, sk, lut, (uint64_t *)aux, thr, hsel);
       // the longest records' shape: whole lines per lane
-      else if (GROUPS == 32 && (KFIX == 31 || (d.K >= kFastKMin && d.K <= kLineFastKMax))) roll_records_lines<BLOCK, KFIX>(a, entry, part, lut, (uint64_t *)aux, thr);
+      else if (GROUPS == 32 && (KFIX == 31 || (d.K >= kFastKMin && d.K <= kLineFastKMax))) {
+#ifdef NQ_SKETCH_CLOCK
+        if (tid == 0 && blockIdx.x < kWaveTraceWgs) nq_sketch_wave[18 * blockIdx.x] = wall_clock64();
+#endif
+        roll_records_lines<BLOCK, KFIX>(a, entry, part, lut, (uint64_t *)aux, thr, n,
+                                         kCellOff + 4u * d.F + (8u * kStack + 4u * kLevelStateWords) * (BLOCK / 64));   // (halves = 1 here: Fc = F, a kernel argument)
+      }
       else roll_records<BLOCK, GROUPS, KFIX, true, false, true>(a, entry, part, sk, lut, (uint64_t *)aux, thr, 0);
       __syncthreads();
+#ifdef NQ_SKETCH_CLOCK
+      if (tid == 0 && blockIdx.x < kWaveTraceWgs) nq_sketch_wave[18 * blockIdx.x + 1] = wall_clock64();
+#endif
       uint32_t local = 0;
       for (uint32_t i = tid; i < Fc; i += BLOCK) local += (sk[i] == kEmpty32);
       if (tid == 0) s_flag[2] = 0;
@@ -1505,8 +1617,10 @@ __global__ __launch_bounds__(64) void sketch_reads_kernel(SketchArgs a) {
   else for (uint32_t i = lane; i < F; i += 64) out[i] = sk[i];
 }
 
+// (behind the 16 stacks of a 1024-lane workgroup: the leveling words of the line form)
 static size_t sketch_lds_bytes(const Derived &d, bool distinct, uint32_t ring_waves, uint32_t halves = 1) {
-  return (size_t)(d.F / halves) * 4 + 16 + 256 + 2048 + (distinct ? (size_t)d.R * 12 : 0) + (size_t)ring_waves * kStack * 8;
+  return (size_t)(d.F / halves) * 4 + 16 + 256 + 2048 + (distinct ? (size_t)d.R * 12 : 0) + (size_t)ring_waves * kStack * 8 +
+         (ring_waves == 16 ? kLevelLdsBytes : 0);
 }
 constexpr size_t kLdsLimit = 160 * 1024;
 
@@ -1708,8 +1822,9 @@ hipError_t launch_sketch(const SketchArgs &a_in, uint32_t n_entry, uint64_t avg_
                              4u * a.d.R <= a.d.F && a.d.R <= (uint32_t)kLateValues * 1024u && late_lds <= kLdsLimit;
   if (late_distinct) a.densify = 0;
   const size_t lds = sketch_lds_bytes(a.d, a.distinct != 0, a.filter ? (short_records ? 4 : 16) : 0, a.halves);
+  if (lds > kLdsLimit) return hipErrorInvalidValue;   // (cells, stacks and leveling words: S <= 15 per half fits)
   dim3 grid(n_entry * a.splits * a.halves);
-#define NQ_LAUNCH_SKETCH(B, G, KF)                                                               \
+#define NQ_LAUNCH_SKETCH(B, G, KF)                                                              \
   do {                                                                                           \
     auto k = sketch_kernel<B, G, KF>;                                                            \
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -1720,7 +1835,7 @@ hipError_t launch_sketch(const SketchArgs &a_in, uint32_t n_entry, uint64_t avg_
     if (a.d.K == 31) NQ_LAUNCH_SKETCH(256, 1, 31); else NQ_LAUNCH_SKETCH(256, 1, 0);
   } else if (avg_len < (1u << 18)) {
     if (a.d.K == 31) NQ_LAUNCH_SKETCH(1024, 2, 31); else NQ_LAUNCH_SKETCH(1024, 2, 0);
-  } else if (avg_len < (1u << 21)) {
+  } else if (avg_len < (1u << 21) || a.d.F < 4) {   // (F = 2: the line form's LDS state would not sit at multiples of 16 bytes)
     if (a.d.K == 31) NQ_LAUNCH_SKETCH(1024, 8, 31); else NQ_LAUNCH_SKETCH(1024, 8, 0);
   } else {
     if (a.d.K == 31) NQ_LAUNCH_SKETCH(1024, 32, 31); else NQ_LAUNCH_SKETCH(1024, 32, 0);

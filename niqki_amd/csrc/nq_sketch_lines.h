@@ -106,4 +106,43 @@ NQ_HD LaneLines lane_lines(uint64_t seqs, uint64_t b0, uint64_t b1, uint32_t K,
   return g;
 }
 
+// ---- leveling a SIMD's four waves ----
+// The issue arbiter serves a SIMD's waves by priority, then age: left alone, the oldest wave of a SIMD runs ahead and
+// the youngest ends the workgroup alone, at a rate one wave cannot keep up (a lane is one dependent chain).  So every
+// wave publishes how far it is through the entry, on a scale all waves share, and takes the top priority while it is
+// the one furthest behind on its SIMD.  Nothing waits on these words: a stale one costs a priority, never a result.
+//
+// PROGRESS: the hash bytes of the entry (all parts') in the records the wave is through plus the line rounds it is
+// through in the current one, a round of a part standing for block * splits lines of the record; in steps of
+// 2^shift bytes, 32 to 63 of them over the entry's n hash bytes.  Wave-uniform, never falls, and after the last
+// record it is n >> shift for every wave.
+constexpr uint32_t kLevelDone = 0xFFFFFFFFu;   // the word of a wave that has left the loop
+constexpr uint32_t kLevelWords = 16;           // one word per wave of the 1024-lane workgroup
+NQ_HD uint32_t level_shift(uint64_t n) { return n >= 64u ? 58u - (uint32_t)__builtin_clzll(n) : 0u; }
+// the bytes of a record that `rounds` line rounds of a part stand for
+NQ_HD uint64_t level_round_bytes(uint32_t rounds, uint32_t block, uint32_t splits) { return ((uint64_t)rounds * block * splits) << kLineLog2; }
+// rec_n: the current record's hash bytes; rounds: line rounds of it the wave is through (a wave without lines in a
+// record never gets here: the record goes into done_recs at once)
+NQ_HD uint32_t level_progress(uint64_t done_recs, uint64_t rec_n, uint32_t rounds, uint32_t block, uint32_t splits, uint32_t shift) {
+  const uint64_t in = level_round_bytes(rounds, block, splits);
+  return (uint32_t)((done_recs + (in < rec_n ? in : rec_n)) >> shift);
+}
+// The bytes into the current record (rounds * block * splits lines) at which the progress leaves p, the value
+// level_progress() has now: the next step boundary.  All ones: none before the record's end.
+NQ_HD uint64_t level_next(uint64_t done_recs, uint64_t rec_n, uint32_t p, uint32_t shift) {
+  const uint64_t t = (((uint64_t)p + 1u) << shift) - done_recs;
+  return t > rec_n ? ~0ull : t;
+}
+// the word of wave w among the sixteen: the four waves of SIMD w % 4 side by side
+NQ_HD uint32_t level_word(uint32_t w) { return (w & 3u) * 4u + (w >> 2); }
+// THE RULE: 3 for the wave (or waves) at the least progress among those of the SIMD still in the loop, one level
+// less per step of lead, down to 0.  simd[]: the SIMD's four words, this wave's among them (kLevelDone is the
+// largest word, so a wave that has left is never the least); mine: this wave's progress (not kLevelDone).
+NQ_HD uint32_t level_prio(uint32_t mine, const uint32_t simd[4]) {
+  uint32_t least = mine;
+  for (int i = 0; i < 4; ++i) least = simd[i] < least ? simd[i] : least;
+  const uint32_t lead = mine - least;
+  return lead < 3u ? 3u - lead : 0u;
+}
+
 }  // namespace nq

@@ -6,6 +6,7 @@
 #define NQ_SKETCH_CLOCK 1
 #include "../niqki_amd/csrc/nq_sketch.hip"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -46,6 +47,10 @@ int main(int argc, char **argv) {
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   CK(nq::launch_sketch(a, n, L, 0));
   CK(hipDeviceSynchronize());
+  {   // (no tick of an earlier launch may pass for one of the last launch's: a workgroup that records none reads as zeros)
+    const std::vector<unsigned long long> zero(18 * nq::kWaveTraceWgs, 0ull);
+    CK(hipMemcpyToSymbol(HIP_SYMBOL(nq::nq_sketch_wave), zero.data(), zero.size() * 8));
+  }
   CK(hipEventRecord(e0));
   for (int r = 0; r < reps; ++r) CK(nq::launch_sketch(a, n, L, 0));
   CK(hipEventRecord(e1));
@@ -57,6 +62,40 @@ int main(int argc, char **argv) {
     unsigned long long clk[2];
     CK(hipMemcpyFromSymbol(clk, HIP_SYMBOL(nq::nq_sketch_clk), 16));
     printf("workgroup 0: %llu shader cycles in %.1f us = %.3f GHz\n", clk[0], clk[1] * 0.01, clk[0] / (clk[1] * 10.0));
+  }
+  {
+    // When the waves of a SIMD finish (line form only: records of 2^21 bases and more).  Wave w runs on SIMD w % 4; the
+    // times are shares of the loop, from the tick before it to the one behind the barrier after it, means over the
+    // recorded workgroups of the last launch.  The bound prices the time a SIMD spends with two waves and with one at
+    // the rates measured with two and one wave per SIMD (1.21 x and 1.90 x the cycles of four, profiles/r03); three
+    // waves count as free.
+    std::vector<unsigned long long> wv(18 * nq::kWaveTraceWgs);
+    CK(hipMemcpyFromSymbol(wv.data(), HIP_SYMBOL(nq::nq_sketch_wave), wv.size() * 8));
+    double share[4][4] = {}, all[4] = {}, idle = 0, loop_us = 0, two = 0, one = 0;
+    uint32_t wgs = 0;
+    for (uint32_t b = 0; b < nq::kWaveTraceWgs && b < n; ++b) {
+      const unsigned long long *t = &wv[18 * b];
+      if (t[1] <= t[0]) continue;   // (not the line form: nothing recorded)
+      const double dur = (double)(t[1] - t[0]);
+      for (int s = 0; s < 4; ++s) {
+        double f[4];
+        for (int j = 0; j < 4; ++j) f[j] = (double)(t[2 + 4 * j + s] - t[0]) / dur;
+        std::sort(f, f + 4);
+        for (int j = 0; j < 4; ++j) { share[s][j] += f[j]; all[j] += f[j] / 4; }
+        two += (f[2] - f[1]) / 4; one += (f[3] - f[2]) / 4; idle += (1.0 - f[3]) / 4;
+      }
+      loop_us += dur * 0.01;
+      ++wgs;
+    }
+    if (wgs) {
+      printf("wave finish times, shares of the loop (%u workgroups, loop %.1f us on average)\n", wgs, loop_us / wgs);
+      printf("%-6s %8s %8s %8s %8s\n", "SIMD", "first", "second", "third", "last");
+      for (int s = 0; s < 4; ++s) printf("%-6d %8.4f %8.4f %8.4f %8.4f\n", s, share[s][0] / wgs, share[s][1] / wgs, share[s][2] / wgs, share[s][3] / wgs);
+      printf("%-6s %8.4f %8.4f %8.4f %8.4f\n", "all", all[0] / wgs, all[1] / wgs, all[2] / wgs, all[3] / wgs);
+      printf("share of the loop a SIMD runs two waves %.4f, one wave %.4f, none (until the barrier) %.4f\n", two / wgs, one / wgs, idle / wgs);
+      printf("bound of the gain from level waves: %.4f of the loop (two waves x (1 - 1/1.21) + one wave x (1 - 1/1.90))\n",
+             two / wgs * (1.0 - 1.0 / 1.21) + one / wgs * (1.0 - 1.0 / 1.90));
+    }
   }
   if (getenv("SK_TRACE")) {
     std::vector<unsigned long long> tr(3 * 8192);
