@@ -485,6 +485,20 @@ int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_
 int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts,
                       uint32_t *n_representatives, int mem);
 
+/* Dereplication that takes the genomes below `first` as given (a database update: which of the genomes added behind
+ * `first` does the collection not represent yet?).  Arguments, mem, stats ("derep_*": the last call of either entry
+ * point) and the restored min_score / top_k as niqki_dereplicate; rule 1 is replaced:
+ *   0. every genome g < first is a representative, whatever it is linked to;
+ *   1. a genome t >= first is a representative iff no representative g < t, given or new, is linked to t;
+ *   2. labels / label_counts as above for t >= first (the linked representative with the largest count, ties to the
+ *      smallest id, later ones count too); labels[g] = g and label_counts[g] = 0 for every g < first.
+ * first = 0 is niqki_dereplicate, bit for bit.  first >= the genome count: everything is a representative and nothing
+ * is launched.  Only the hit lists of the genomes [first, n) are made: the self-join batches start at `first`, and
+ * since the given representatives have no lists of their own, each batch reads their offers off its own lists
+ * (counts are symmetric). */
+int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, uint32_t *labels,
+                           uint32_t *label_counts, uint32_t *n_representatives, int mem);
+
 /* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
  * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
  * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses
@@ -544,6 +558,35 @@ int niqki_export_dump_slots(niqki_index *ix, uint32_t slot_begin, uint32_t slot_
 int niqki_import_begin(const niqki_params *params, const uint8_t header[24], niqki_index **out);
 int niqki_import_slots(niqki_index *ix, uint32_t slot_begin, uint32_t slot_end,
                        const uint8_t *buf, uint64_t len, uint64_t *consumed);
+
+/* Appends the genomes of a dump (the bytes niqki_import_dump reads) to a handle that may already hold genomes, without
+ * a genome being sketched again.  Definition: let B be the handle niqki_import_dump makes from the same bytes, N_B its
+ * genome count.  A committed append leaves ix indistinguishable, through every call of this header, from ix after
+ * niqki_insert(ix, niqki_get_sketches(B, 0, N_B)): the dump's genome g becomes id n_before + g; min_score, top_k and
+ * all options stay the handle's (the dump's min_score word is ignored); a delta segment or a rebuild follows as after
+ * an insert (option "incremental_build"); the dump bytes afterwards are those of a fresh handle into which all
+ * n_before + N_B sketches were inserted in that order.
+ * The header's lF, K, W and H must equal the handle's current ones (H: the value after any niqki_select_best_H), else
+ * NIQKI_E_INVALID, niqki_last_error names the field, nothing changes.
+ * niqki_append_begin grows the sketch store (resident, or the paged host store) to n_before + N_B columns and presets
+ * the new ones to empty.  niqki_append_slots takes the payload of whole slots [slot_begin, slot_end) (*consumed = the
+ * bytes used): ascending, contiguous from slot 0, in any grouping.  The append COMMITS when slot 2^S - 1 has been
+ * taken: the genome count grows by N_B and the inserts are pending for the next build.  Until then the index is the
+ * old one for every reader (queries, niqki_genome_count, dumps), and the calls that add or drop genomes -- niqki_insert,
+ * niqki_insert_shared, niqki_staged_insert, niqki_retain, a second niqki_append_begin -- return NIQKI_E_STATE.  A
+ * failing niqki_append_slots (a payload that ends inside a slot, a genome id >= N_B, slots out of order:
+ * NIQKI_E_INVALID) cancels the append itself; niqki_append_cancel (NIQKI_OK also when none is pending) and a failure
+ * both leave the index exactly as before: same count, same dump bytes, still built if it was built.
+ * N_B = 0 commits at once (no niqki_append_slots call follows).  An append into an empty handle equals an import.
+ * niqki_append_dump is the one-shot form: header and payload in one buffer (*consumed = offset of the first name byte).
+ * Handles as niqki_retain: whole-range single-GPU handles, resident or paged, S <= 16; NIQKI_E_STATE on a slot-range
+ * shard.  Groups cannot append (out of scope: append on a single-GPU handle, or pair niqki_get_sketches with
+ * niqki_insert in device memory).  DESIGN.md 4.6e. */
+int niqki_append_begin(niqki_index *ix, const uint8_t header[24]);
+int niqki_append_slots(niqki_index *ix, uint32_t slot_begin, uint32_t slot_end,
+                       const uint8_t *buf, uint64_t len, uint64_t *consumed);
+int niqki_append_cancel(niqki_index *ix);
+int niqki_append_dump(niqki_index *ix, const uint8_t *buf, uint64_t len, uint64_t *consumed);
 
 /* Reads back the stored sketches of genomes [begin, begin+n) as n x F int32
  * (slots outside the shard's range read -1). */

@@ -118,6 +118,7 @@ ABI = [
     ("niqki_neighbors_range", _int, [_vp, _u32, _u32, _vp, _vp, _vp, _u64, _int]),
     ("niqki_cluster", _int, [_vp, _u32, _vp, C.POINTER(_u32), _int]),
     ("niqki_dereplicate", _int, [_vp, _u32, _vp, _vp, C.POINTER(_u32), _int]),
+    ("niqki_dereplicate_from", _int, [_vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
@@ -126,6 +127,10 @@ ABI = [
     ("niqki_export_dump_slots", _int, [_vp, _u32, _u32, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_begin", _int, [C.POINTER(Params), _vp, C.POINTER(_vp)]),
     ("niqki_import_slots", _int, [_vp, _u32, _u32, _vp, _u64, C.POINTER(_u64)]),
+    ("niqki_append_begin", _int, [_vp, _vp]),
+    ("niqki_append_slots", _int, [_vp, _u32, _u32, _vp, _u64, C.POINTER(_u64)]),
+    ("niqki_append_cancel", _int, [_vp]),
+    ("niqki_append_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_get_sketches", _int, [_vp, _u32, _u32, _vp, _int]),
     ("niqki_query_gathered", _int, [_vp, _vp, _u32, _vp, _int]),
     ("niqki_group_slot_range", None, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
@@ -556,6 +561,17 @@ class Engine:
         self._ck(self.L.niqki_dereplicate(self.h, int(threshold), _p(labels), _p(lc) if counts else None, C.byref(n), MEM_HOST))
         return (labels, lc, int(n.value)) if counts else (labels, int(n.value))
 
+    def dereplicate_from(self, first, threshold, counts=False):
+        """dereplicate with the genomes below `first` given: all of them are representatives (labels[g] = g, count 0),
+        a genome from `first` on is one iff no representative below it, given or new, is linked to it.  Same returns
+        as dereplicate; first=0 is dereplicate."""
+        labels = np.empty(self.n_genomes, dtype=np.uint32)
+        lc = np.empty(self.n_genomes, dtype=np.uint32) if counts else None
+        n = _u32(0)
+        self._ck(self.L.niqki_dereplicate_from(self.h, int(first), int(threshold), _p(labels), _p(lc) if counts else None,
+                                               C.byref(n), MEM_HOST))
+        return (labels, lc, int(n.value)) if counts else (labels, int(n.value))
+
     def retain(self, keep):
         """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),
         new_ids[g] = the new id of old genome g (the kept genomes below it), 0xFFFFFFFF for a dropped one.  The handle
@@ -585,6 +601,29 @@ class Engine:
         buf = np.empty(size.value, dtype=np.uint8)
         self._ck(self.L.niqki_export_dump(self.h, _p(buf), buf.size, C.byref(size)))
         return buf.tobytes()
+
+    def append_dump(self, data):
+        """Appends the genomes of a dump (export_dump's bytes, names may follow) behind the handle's own: genome g of
+        the dump becomes id n_genomes + g.  Returns the offset of the first name byte."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        consumed = _u64(0)
+        self._ck(self.L.niqki_append_dump(self.h, _p(buf), buf.size, C.byref(consumed)))
+        return consumed.value
+
+    def append_begin(self, header):
+        """Streaming append: the dump's 24-byte header; then append_slots in slot order (the last slot commits)."""
+        hdr = np.frombuffer(bytes(header[:24]), dtype=np.uint8)
+        self._ck(self.L.niqki_append_begin(self.h, _p(hdr)))
+
+    def append_slots(self, slot_begin, slot_end, data):
+        """The payload bytes of whole slots [slot_begin, slot_end); returns the bytes used."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        used = _u64(0)
+        self._ck(self.L.niqki_append_slots(self.h, slot_begin, slot_end, _p(buf) if buf.size else None, buf.size, C.byref(used)))
+        return used.value
+
+    def append_cancel(self):
+        self._ck(self.L.niqki_append_cancel(self.h))
 
     @classmethod
     def import_dump(cls, data, device=-1, tile_genomes=0, resident_mib=0, top_k=0):

@@ -10,6 +10,9 @@
 
 namespace nqi {
 
+// the store columns a grown store must keep: the genomes and, while an append is pending, the columns it has written
+static uint64_t live_columns(const niqki_index *ix) { return (uint64_t)ix->n_genomes + (ix->append.active ? ix->append.n_new : 0); }
+
 // paged index: the store is page-locked host memory
 int reserve_host_store(niqki_index *ix, uint64_t want) {
   if (want <= ix->host_cap) return NIQKI_OK;
@@ -19,10 +22,11 @@ int reserve_host_store(niqki_index *ix, uint64_t want) {
   uint16_t *ns = nullptr;
   if (hipHostMalloc((void **)&ns, (size_t)f_all * cap * 2, hipHostMallocDefault) != hipSuccess)
     return fail(ix, NIQKI_E_NOMEM, "page-locked sketch store allocation failed");
-  if (ix->host_store && ix->n_genomes) {
+  const uint64_t n_live = live_columns(ix);
+  if (ix->host_store && n_live) {
     NQ_HIP(ix, hipStreamSynchronize(ix->stream));
     for (uint32_t s = 0; s < f_all; ++s)
-      std::memcpy(ns + (size_t)s * cap, ix->host_store + (size_t)s * ix->host_cap, (size_t)ix->n_genomes * 2);
+      std::memcpy(ns + (size_t)s * cap, ix->host_store + (size_t)s * ix->host_cap, (size_t)n_live * 2);
   }
   if (ix->host_store) (void)hipHostFree(ix->host_store);
   ix->host_store = ns;
@@ -43,8 +47,8 @@ int reserve_store(niqki_index *ix, uint64_t want) {
     e = hipMalloc((void **)&ns, (size_t)f_local * cap * 2);
   }
   if (e != hipSuccess) return fail(ix, NIQKI_E_NOMEM, "sketch store allocation failed");
-  if (ix->store && ix->n_genomes) {
-    NQ_HIP(ix, hipMemcpy2DAsync(ns, cap * 2, ix->store, ix->cap * 2, (size_t)ix->n_genomes * 2, f_local,
+  if (ix->store && live_columns(ix)) {
+    NQ_HIP(ix, hipMemcpy2DAsync(ns, cap * 2, ix->store, ix->cap * 2, (size_t)live_columns(ix) * 2, f_local,
                                 hipMemcpyDeviceToDevice, ix->stream));
     NQ_HIP(ix, hipStreamSynchronize(ix->stream));
   }
@@ -163,6 +167,7 @@ int build_single(niqki_index *ix) {
 
 int insert_dev(niqki_index *ix, const int32_t *sketches, uint32_t sk_stride, uint32_t sk_off, uint32_t n) {
   if (n == 0) return NIQKI_OK;
+  if (ix->append.active) return fail(ix, NIQKI_E_STATE, "an append is pending: finish it or call niqki_append_cancel before inserting");
   if ((uint64_t)ix->n_genomes + n > 0xFFFFFFFFull) return fail(ix, NIQKI_E_INVALID, "too many genomes");
   int rc = reserve_store(ix, (uint64_t)ix->n_genomes + n);
   if (rc) return rc;

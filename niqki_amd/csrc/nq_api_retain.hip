@@ -149,6 +149,7 @@ extern "C" {
 int niqki_retain(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32_t *n_kept, int mem) {
   if (!ix || (!keep && ix->n_genomes)) return NIQKI_E_INVALID;
   if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_retain: a slot-range shard holds part of every sketch; drop genomes on a whole-range handle");
+  if (ix->append.active) return fail(ix, NIQKI_E_STATE, "niqki_retain: an append is pending: finish it or call niqki_append_cancel first");
   NQ_HIP(ix, hipSetDevice(ix->device));
   if (ix->n_genomes == 0) {
     if (n_kept) *n_kept = 0;

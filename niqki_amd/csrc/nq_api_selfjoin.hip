@@ -1,12 +1,14 @@
 // nq_api_selfjoin.hip -- the self-join of an index behind the C ABI: niqki_neighbors_range (the hits of the stored
 // sketches, the sparse form of Index::query_range, src/niqki_index.cpp:570-610), niqki_cluster (single-linkage
-// clusters: the link and flatten kernels over the hit lists of the stored sketches) and niqki_dereplicate (greedy
-// representatives in index order: the decide, assign and finish kernels over the same hit lists).  The kernels are in
-// nq_cluster.hip, the hit lists come from the query path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c.
+// clusters: the link and flatten kernels over the hit lists of the stored sketches) and niqki_dereplicate /
+// niqki_dereplicate_from (greedy representatives in index order, the genomes below `first` given: the decide, assign
+// and finish kernels over the same hit lists).  The kernels are in nq_cluster.hip, the hit lists come from the query
+// path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c, 4.6f.
 #include "nq_handle.h"
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 namespace nqi {
 
@@ -103,8 +105,8 @@ int self_join_batch(SelfJoin &r, uint32_t t0, uint32_t n, uint32_t *fitted) {
   return NIQKI_OK;
 }
 
-// the hit buffers, the events, then the batches of genomes [0, n_run) in index order
-int self_join_batches(SelfJoin &r, uint32_t n_run) {
+// the hit buffers, the events, then the batches of genomes [begin, n_run) in index order
+int self_join_batches(SelfJoin &r, uint32_t n_run, uint32_t begin = 0) {
   niqki_index *ix = r.ix;
   const uint32_t N = ix->n_genomes;
   r.stride = NIQKI_ROW_STRIDE(N);
@@ -113,7 +115,7 @@ int self_join_batches(SelfJoin &r, uint32_t n_run) {
   r.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
   int rc = r.create_events();
   uint32_t qb = std::max<uint32_t>(ix->query_batch, 1);
-  for (uint32_t t0 = 0; t0 < n_run && !rc;) {
+  for (uint32_t t0 = begin; t0 < n_run && !rc;) {
     const uint32_t n = std::min(qb, n_run - t0);
     uint32_t fitted = n;
     rc = self_join_batch(r, t0, n, &fitted);
@@ -155,8 +157,10 @@ int cluster_run(niqki_index *ix, uint32_t *labels, uint32_t *n_clusters, int mem
 }
 
 // threshold 0 links every pair, so genome 0 is the only representative: only ITS list is made (at min_score 0 it holds
-// every genome with its count), the other genomes start as covered
-int derep_run(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_reps, int mem) {
+// every genome with its count), the other genomes start as covered.
+// first > 0 (niqki_dereplicate_from): the genomes below it start as representatives and have no lists; the batches
+// start at `first` and each one also takes the given representatives' offers from its own lists (nq_cluster.hip).
+int derep_run(niqki_index *ix, uint32_t first, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_reps, int mem) {
   const uint32_t N = ix->n_genomes;
   int rc = build_if_needed(ix);
   if (rc) return rc;
@@ -174,13 +178,17 @@ int derep_run(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *l
     int rc_ = r.mark(3);
     if (rc_) return rc_;
     NQ_HIP(ix, nq::launch_derep_assign(state, best, N, off, hc, hg, t0, n, ix->stream));
+    NQ_HIP(ix, nq::launch_derep_given(best, N, first, off, hc, hg, t0, n, ix->stream));
     return r.mark(4);
   };
   NQ_HIP(ix, hipMemsetAsync(best, 0, (size_t)N * 8, ix->stream));
   NQ_HIP(ix, hipMemsetAsync(info, 0, 16, ix->stream));
-  NQ_HIP(ix, hipMemsetAsync(state, threshold ? nq::kUndecided : nq::kCovered, N, ix->stream));
-  if (!threshold) NQ_HIP(ix, hipMemsetAsync(state, nq::kUndecided, 1, ix->stream));
-  if ((rc = self_join_batches(r, threshold ? N : 1))) return rc;
+  // (with given genomes threshold 0 needs no special case: every list holds a given representative)
+  const bool all_linked = !threshold && !first;
+  NQ_HIP(ix, hipMemsetAsync(state, all_linked ? nq::kCovered : nq::kUndecided, N, ix->stream));
+  if (all_linked) NQ_HIP(ix, hipMemsetAsync(state, nq::kUndecided, 1, ix->stream));
+  if (first) NQ_HIP(ix, hipMemsetAsync(state, nq::kRep, first, ix->stream));
+  if ((rc = self_join_batches(r, all_linked ? 1 : N, first))) return rc;
   uint32_t out[4] = {0, 0, 0, 0};
   NQ_HIP(ix, nq::launch_derep_finish(state, best, N, d_labels, d_counts, info + 3, ix->stream));
   if (!dev) NQ_HIP(ix, hipMemcpyAsync(labels, d_labels, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream));
@@ -245,18 +253,38 @@ int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_
   return cluster_run(ix, labels, n_clusters, mem);
 }
 
-int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_representatives,
-                      int mem) {
+int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, uint32_t *labels, uint32_t *label_counts,
+                           uint32_t *n_representatives, int mem) {
   if (!ix || (!labels && ix->n_genomes)) return NIQKI_E_INVALID;
   if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_dereplicate: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
   NQ_HIP(ix, hipSetDevice(ix->device));
   ix->derep_stats = SelfJoinStats();
-  if (ix->n_genomes == 0) {
+  const uint32_t N = ix->n_genomes;
+  if (N == 0) {
     if (n_representatives) *n_representatives = 0;
     return NIQKI_OK;
   }
+  if (first >= N) {   // every genome is given: all are representatives, no kernel runs
+    if (mem == NIQKI_MEM_DEVICE) {
+      std::vector<uint32_t> ids(N);
+      for (uint32_t g = 0; g < N; ++g) ids[g] = g;
+      NQ_HIP(ix, hipMemcpyAsync(labels, ids.data(), (size_t)N * 4, hipMemcpyHostToDevice, ix->stream));
+      if (label_counts) NQ_HIP(ix, hipMemsetAsync(label_counts, 0, (size_t)N * 4, ix->stream));
+      NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // (ids leaves scope)
+    } else {
+      for (uint32_t g = 0; g < N; ++g) labels[g] = g;
+      if (label_counts) std::fill(label_counts, label_counts + N, 0u);
+    }
+    if (n_representatives) *n_representatives = N;
+    return NIQKI_OK;
+  }
   CallThreshold guard(ix, threshold);
-  return derep_run(ix, threshold, labels, label_counts, n_representatives, mem);
+  return derep_run(ix, first, threshold, labels, label_counts, n_representatives, mem);
+}
+
+int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_representatives,
+                      int mem) {
+  return niqki_dereplicate_from(ix, 0, threshold, labels, label_counts, n_representatives, mem);
 }
 
 }  // extern "C"

@@ -151,6 +151,15 @@ __global__ void cluster_flatten_kernel(const uint32_t *parent, uint32_t n, uint3
 // Representatives are pairwise unlinked, so a genome receives one atomic per representative it is linked to and no
 // word is hot.  A covered genome has at least one linked representative below it, so its best[] is set when the last
 // batch is through.
+//
+// Given genomes (niqki_dereplicate_from).  state[g] = kRep from the start for g < first and only the
+// lists of the genomes [first, n) are made; the decide rounds above run unchanged (a given genome is a decided
+// representative like any other).  The given representatives have no lists of their own to walk, so after the assign
+// step the wave of EVERY query t of the batch takes the hits g < first of t's own list: counts are symmetric, so
+// count(t, g) << 32 | ~g is the offer g would have made.  The wave reduces its offers to their maximum and lane 0
+// issues the one agent-scope 64-bit atomicMax on best[t] -- the same operation, on the same word, as the offers of
+// the batch's new representatives; best[] is only ever written by such atomics and read by the finish kernel of a
+// later launch.  An offer to a t that turned out a representative is ignored by the finish kernel like any other.
 
 constexpr uint32_t kFinisherBlock = 1024;
 
@@ -235,6 +244,30 @@ __global__ __launch_bounds__(kLinkBlock) void derep_assign_kernel(const uint8_t 
   }
 }
 
+// the offers of the given representatives g < first to the queries of the batch, read off the queries' own lists
+__global__ __launch_bounds__(kLinkBlock) void derep_given_kernel(unsigned long long *best, uint32_t n, uint32_t first,
+                                                                 const unsigned long long *hit_off, const uint32_t *hit_counts,
+                                                                 const uint32_t *hit_gids, uint32_t t0, uint32_t nq) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t q = blockIdx.x * (kLinkBlock / 64) + (threadIdx.x >> 6);   // wave-uniform
+  if (q >= nq) return;
+  const uint32_t t = t0 + q;
+  if (t >= n) return;
+  const unsigned long long lo = hit_off[q], hi = hit_off[q + 1];
+  unsigned long long v = 0;
+  for (unsigned long long i = lo + lane; i < hi; i += 64) {
+    const uint32_t g = hit_gids[i];
+    if (g >= first || g == t) continue;
+    const unsigned long long o = ((unsigned long long)hit_counts[i] << 32) | (uint32_t)~g;
+    v = o > v ? o : v;
+  }
+  for (int d = 32; d; d >>= 1) {
+    const unsigned long long o = (unsigned long long)__shfl_xor((long long)v, d);
+    v = o > v ? o : v;
+  }
+  if (lane == 0 && v) __hip_atomic_fetch_max(best + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // labels / label_counts (may be null) from state[] and best[]; the representatives are counted per wavefront
 __global__ void derep_finish_kernel(const uint8_t *state, const unsigned long long *best, uint32_t n, uint32_t *labels,
                                     uint32_t *label_counts, uint32_t *n_reps) {
@@ -287,6 +320,15 @@ hipError_t launch_derep_assign(const uint8_t *state, unsigned long long *best, u
   if (!nq || !n) return hipSuccess;
   const uint32_t per = kLinkBlock / 64;
   hipLaunchKernelGGL(derep_assign_kernel, dim3((nq + per - 1) / per), dim3(kLinkBlock), 0, stream, state, best, n, hit_off, hit_counts,
+                     hit_gids, t0, nq);
+  return hipGetLastError();
+}
+
+hipError_t launch_derep_given(unsigned long long *best, uint32_t n, uint32_t first, const unsigned long long *hit_off,
+                              const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream) {
+  if (!nq || !n || !first) return hipSuccess;
+  const uint32_t per = kLinkBlock / 64;
+  hipLaunchKernelGGL(derep_given_kernel, dim3((nq + per - 1) / per), dim3(kLinkBlock), 0, stream, best, n, first, hit_off, hit_counts,
                      hit_gids, t0, nq);
   return hipGetLastError();
 }

@@ -102,6 +102,13 @@ struct niqki_index {
   uint32_t delta_n = 0;    // genomes the delta segment covers (0 = there is none)
   int incremental = 1;     // option "incremental_build"
 
+  // niqki_append_begin .. the last niqki_append_slots: the dump's n_new genomes are being written into the store columns
+  // [n_genomes, n_genomes + n_new), which no reader looks at; the commit adds n_new to n_genomes (nq_api_dump.hip)
+  struct {
+    bool active = false;
+    uint32_t n_new = 0, next_slot = 0;
+  } append;
+
   void *shared_state = nullptr;   // nq_shared.hip: the combiner of the *_shared (many host threads) entry points
 
   int gather_variant = 0;

@@ -505,10 +505,11 @@ hipError_t launch_export(const IndexView &v, const unsigned long long *slot_word
 }
 
 // ---- dump stream import (src/niqki_index.cpp:78-85): one wave per slot ----
-// slots [s0, s0+n_slots): slot_word[i] = word position of slot s0+i inside `words`
+// slots [s0, s0+n_slots): slot_word[i] = word position of slot s0+i inside `words`.  The dump's genome g (valid below
+// n_genomes) goes to store column col_base + g: 0 for an import, the handle's genome count for an append.
 __global__ __launch_bounds__(256) void import_kernel(Derived d, const uint32_t *words,
                                                     const uint64_t *slot_word, uint16_t *store,
-                                                    uint64_t cap, uint32_t n_genomes, uint32_t *bad,
+                                                    uint64_t cap, uint32_t n_genomes, uint32_t col_base, uint32_t *bad,
                                                     uint32_t s0, uint32_t n_slots) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -521,7 +522,7 @@ __global__ __launch_bounds__(256) void import_kernel(Derived d, const uint32_t *
     uint32_t size = words[p];
     for (uint32_t j = lane; j < size; j += 64) {
       uint32_t g = words[p + 1 + j];
-      if (g < n_genomes) store[(uint64_t)s * cap + g] = (uint16_t)fp;
+      if (g < n_genomes) store[(uint64_t)s * cap + col_base + g] = (uint16_t)fp;
       else atomicAdd(bad, 1u);
     }
     p += 1 + (uint64_t)size;
@@ -530,11 +531,11 @@ __global__ __launch_bounds__(256) void import_kernel(Derived d, const uint32_t *
 }
 
 hipError_t launch_import(const Derived &d, const uint32_t *words, const uint64_t *slot_word,
-                         uint16_t *store, uint64_t cap, uint32_t n_genomes, uint32_t *bad,
+                         uint16_t *store, uint64_t cap, uint32_t n_genomes, uint32_t col_base, uint32_t *bad,
                          uint32_t s0, uint32_t n_slots, hipStream_t stream) {
   if (n_slots == 0) return hipSuccess;
   hipLaunchKernelGGL(import_kernel, dim3((n_slots + 3) / 4), dim3(256), 0, stream, d, words, slot_word,
-                     store, cap, n_genomes, bad, s0, n_slots);
+                     store, cap, n_genomes, col_base, bad, s0, n_slots);
   return hipGetLastError();
 }
 

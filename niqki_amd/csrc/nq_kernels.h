@@ -138,9 +138,11 @@ hipError_t launch_export_layout(const IndexView &v, unsigned long long *slot_wor
 hipError_t launch_export(const IndexView &v, const unsigned long long *slot_word, uint32_t *out,
                          uint32_t s0, uint32_t s1, hipStream_t stream);
 // inverse: walk the dump words of slots [s0, s0+n_slots) and write the sketch
-// store.  slot_word: n_slots+1 word positions of the slots inside `words`.
+// store.  slot_word: n_slots+1 word positions of the slots inside `words`.  Ids are valid below n_genomes (others
+// are counted in *bad and not stored); id g is written to column col_base + g (0: an import; an append: the
+// handle's genome count).
 hipError_t launch_import(const Derived &d, const uint32_t *words, const uint64_t *slot_word,
-                         uint16_t *store, uint64_t cap, uint32_t n_genomes, uint32_t *bad,
+                         uint16_t *store, uint64_t cap, uint32_t n_genomes, uint32_t col_base, uint32_t *bad,
                          uint32_t s0, uint32_t n_slots, hipStream_t stream);
 
 // ---- query: counters (nq_gather.hip) ------------------------------------------
@@ -276,6 +278,10 @@ hipError_t launch_derep_decide(uint8_t *state, uint32_t n, const unsigned long l
 // every representative of the batch: best[g] = max(best[g], count << 32 | ~t) over its hits g != t
 hipError_t launch_derep_assign(const uint8_t *state, unsigned long long *best, uint32_t n, const unsigned long long *hit_off,
                                const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream);
+// niqki_dereplicate_from: every query t0 + q of the batch: best[t] = max(best[t], count << 32 | ~g) over its own hits
+// g < first, the given representatives (nothing is launched for first == 0)
+hipError_t launch_derep_given(unsigned long long *best, uint32_t n, uint32_t first, const unsigned long long *hit_off,
+                              const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream);
 // labels[g] = g or the representative in best[g]; label_counts (may be null) = 0 or the count in best[g];
 // *n_reps (zeroed here) = number of representatives
 hipError_t launch_derep_finish(const uint8_t *state, const unsigned long long *best, uint32_t n, uint32_t *labels, uint32_t *label_counts,

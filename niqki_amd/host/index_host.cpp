@@ -21,6 +21,7 @@
 #include <fstream>
 #include <iostream>
 #include <future>
+#include <iterator>
 #include <memory>
 #include <stdexcept>
 #include <thread>
@@ -114,14 +115,17 @@ Index::Index(uint32_t ilF, uint32_t iK, uint32_t iW, uint32_t iH, const std::str
   outfile.reset(new ParallelTextWriter(out_filename, host_threads()));
 }
 
-Index::Index(const std::string &dump_file, bool pretty, const std::string &out_filename, int device, int n_gpus,
-             int resident_mib, uint32_t itop_k) {
-  pretty_printing = pretty;
-  // The dump is streamed: header, then the buckets in groups of whole slots (the payload of a 100k-genome index is
-  // 13.6 GB), then the names.  A dump this program wrote is a file of size-tagged gzip members (gzio.h): they are
-  // inflated side by side by the reader threads, a window ahead; any other gzip file (the reference's dumps are one
-  // member) comes through zlib's stream.  Either way the bytes arrive in pieces, and the walk over the buckets' size
-  // words -- the one serial thing about the format -- runs over memory, not over a reader call per bucket.
+namespace {
+// The streamed walk over a dump file, shared by the loading constructor (-L) and merge_dump (--merge): header, then the
+// buckets in groups of whole slots (the payload of a 100k-genome index is 13.6 GB), then the names.  A dump this
+// program wrote is a file of size-tagged gzip members (gzio.h): they are inflated side by side by the reader threads, a
+// window ahead; any other gzip file (the reference's dumps are one member) comes through zlib's stream.  Either way the
+// bytes arrive in pieces, and the walk over the buckets' size words -- the one serial thing about the format -- runs
+// over memory, not over a reader call per bucket.
+// header: the 24 header bytes, once, before any slot (it refuses a dump by throwing); slots: the payload of whole
+// slots [s0, s1), in order; names: the header's N lines behind the buckets (src/niqki_index.cpp:91-95) are appended.
+void walk_dump(const std::string &dump_file, const std::function<void(const uint8_t *)> &header,
+               const std::function<void(uint32_t, uint32_t, const uint8_t *, size_t)> &slots, std::vector<std::string> &names) {
   std::unique_ptr<TaggedGzReader> tagged;
   std::unique_ptr<GzReader> plain;
   if (TaggedGzReader::probe(dump_file)) {
@@ -149,22 +153,15 @@ Index::Index(const std::string &dump_file, bool pretty, const std::string &out_f
     return true;
   };
   if (!need(24)) throw std::runtime_error("'" + dump_file + "' is not a niqki dump");
-  uint8_t hdr[24];
+  uint32_t hdr[6];
   std::memcpy(hdr, buf.data(), 24);
   p = 24;
-  niqki_params prm{};
-  prm.resident_mib = resident_mib > 0 ? (uint32_t)resident_mib : 0u;
-  prm.top_k = top_k = itop_k;   // (the dump does not hold it: niqki_import_begin takes it from the params)
-  make_shards(prm, device, n_gpus, hdr);   // every shard keeps its own slots of the stream
-  niqki_params q{};
-  niqki_get_params(h_, &q);
-  K = q.K; W = q.W; H = q.H; lF = q.S; F = 1u << q.S; min_score = q.min_score;
-  const uint32_t R = 1u << W;
+  header(buf.data());
+  const uint32_t F = 1u << hdr[0], R = 1u << hdr[3];
   uint32_t s0 = 0;
   size_t g0 = p;   // where the slots not yet handed over start in buf
   auto flush = [&](uint32_t s1) {
-    uint64_t used = 0;
-    for (auto *h : sh_) check(niqki_import_slots(h, s0, s1, buf.data() + g0, p - g0, &used), "niqki_import_slots");
+    slots(s0, s1, buf.data() + g0, p - g0);
     buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)p);   // (what is left is less than one piece)
     p = g0 = 0;
     s0 = s1;
@@ -180,16 +177,36 @@ Index::Index(const std::string &dump_file, bool pretty, const std::string &out_f
     if (p - g0 >= kBatchBytes / 8) flush(s + 1);
   }
   flush(F);
-  // genome names, one per line after the buckets (src/niqki_index.cpp:91-95)
   while (more()) {}
-  const uint32_t n = niqki_genome_count(h_);
-  for (uint32_t i = 0; i < n; ++i) {
+  for (uint32_t i = 0; i < hdr[5]; ++i) {
     const uint8_t *b0 = buf.data() + p, *e0 = buf.data() + buf.size();
     const uint8_t *nl = p < buf.size() ? (const uint8_t *)memchr(b0, '\n', (size_t)(e0 - b0)) : nullptr;
     const uint8_t *end = nl ? nl : e0;
-    filenames.emplace_back(p < buf.size() ? std::string((const char *)b0, (size_t)(end - b0)) : std::string());
+    names.emplace_back(p < buf.size() ? std::string((const char *)b0, (size_t)(end - b0)) : std::string());
     p = nl ? (size_t)(nl + 1 - buf.data()) : buf.size();
   }
+}
+}  // namespace
+
+Index::Index(const std::string &dump_file, bool pretty, const std::string &out_filename, int device, int n_gpus,
+             int resident_mib, uint32_t itop_k) {
+  pretty_printing = pretty;
+  walk_dump(
+      dump_file,
+      [&](const uint8_t *hdr) {
+        niqki_params prm{};
+        prm.resident_mib = resident_mib > 0 ? (uint32_t)resident_mib : 0u;
+        prm.top_k = top_k = itop_k;   // (the dump does not hold it: niqki_import_begin takes it from the params)
+        make_shards(prm, device, n_gpus, hdr);   // every shard keeps its own slots of the stream
+        niqki_params q{};
+        niqki_get_params(h_, &q);
+        K = q.K; W = q.W; H = q.H; lF = q.S; F = 1u << q.S; min_score = q.min_score;
+      },
+      [&](uint32_t s0, uint32_t s1, const uint8_t *data, size_t len) {
+        uint64_t used = 0;
+        for (auto *h : sh_) check(niqki_import_slots(h, s0, s1, data, len, &used), "niqki_import_slots");
+      },
+      filenames);
   if (n_gpus > 1) {
     const int rc = niqki_group_create(sh_.data(), (uint32_t)sh_.size(), 0, (uint32_t)sh_.size(), nullptr, &grp_);
     if (rc) throw std::runtime_error(std::string("niqki_group_create: ") + niqki_status_string(rc) + " (" + niqki_last_error(h_) + ")");
@@ -983,12 +1000,22 @@ neighbors_fn engine_neighbors() { return (neighbors_fn)dlsym(RTLD_DEFAULT, "niqk
 cluster_fn engine_cluster() { return (cluster_fn)dlsym(RTLD_DEFAULT, "niqki_cluster"); }
 using retain_fn = int (*)(niqki_index *, const uint8_t *, uint32_t *, uint32_t *, int);
 derep_fn engine_derep() { return (derep_fn)dlsym(RTLD_DEFAULT, "niqki_dereplicate"); }
+using derep_from_fn = int (*)(niqki_index *, uint32_t, uint32_t, uint32_t *, uint32_t *, uint32_t *, int);
+derep_from_fn engine_derep_from() { return (derep_from_fn)dlsym(RTLD_DEFAULT, "niqki_dereplicate_from"); }
+using append_begin_fn = int (*)(niqki_index *, const uint8_t *);
+using append_slots_fn = int (*)(niqki_index *, uint32_t, uint32_t, const uint8_t *, uint64_t, uint64_t *);
+using append_cancel_fn = int (*)(niqki_index *);
+append_begin_fn engine_append_begin() { return (append_begin_fn)dlsym(RTLD_DEFAULT, "niqki_append_begin"); }
+append_slots_fn engine_append_slots() { return (append_slots_fn)dlsym(RTLD_DEFAULT, "niqki_append_slots"); }
+append_cancel_fn engine_append_cancel() { return (append_cancel_fn)dlsym(RTLD_DEFAULT, "niqki_append_cancel"); }
 retain_fn engine_retain() { return (retain_fn)dlsym(RTLD_DEFAULT, "niqki_retain"); }
 }  // namespace
 
 bool Index::has_self_join() { return engine_neighbors() != nullptr && engine_cluster() != nullptr; }
 bool Index::has_dereplication() { return engine_derep() != nullptr; }
 bool Index::has_retain() { return engine_retain() != nullptr; }
+bool Index::has_dereplication_from() { return engine_derep_from() != nullptr; }
+bool Index::has_append() { return engine_append_begin() != nullptr && engine_append_slots() != nullptr && engine_append_cancel() != nullptr; }
 
 void Index::query_neighbors() {
   const neighbors_fn call = engine_neighbors();
@@ -1016,7 +1043,7 @@ void Index::query_neighbors() {
 
 // lines label<TAB>member: the groups in the index order of their label (a member of its own group), inside a group the
 // label's own line first, then the other members in index order
-void Index::write_groups(const std::string &filestr, const std::vector<uint32_t> &labels) {
+void Index::write_groups(const std::string &filestr, const std::vector<uint32_t> &labels, uint32_t first) {
   const uint32_t N = (uint32_t)labels.size();
   std::vector<uint32_t> start(N + 1, 0), order(N);
   for (uint32_t g = 0; g < N; ++g) start[labels[g] + 1] += 1;
@@ -1028,6 +1055,7 @@ void Index::write_groups(const std::string &filestr, const std::vector<uint32_t>
   std::string text;
   for (uint32_t i = 0; i < N; ++i) {
     const uint32_t g = order[i];
+    if (g < first) continue;   // (--novel: the given genomes have no lines)
     text += filenames[labels[g]];
     text += '\t';
     text += filenames[g];
@@ -1066,6 +1094,56 @@ void Index::dereplicate(const std::string &list_file, const std::string &dump_fi
   for (uint32_t g = 0; g < N; ++g) keep[g] = labels[g] == g;
   retain(keep);
   dump_index_disk(dump_file);
+}
+
+// ---- merging dumps ------------------------------------------------------------------
+
+void Index::merge_dump(const std::string &dump_file) {
+  const append_begin_fn begin = engine_append_begin();
+  const append_slots_fn slots = engine_append_slots();
+  const append_cancel_fn cancel = engine_append_cancel();
+  if (!begin || !slots || !cancel || grp_) throw std::runtime_error("this engine cannot merge dumps");
+  std::vector<std::string> names;
+  bool pending = false;
+  try {
+    walk_dump(
+        dump_file,
+        [&](const uint8_t *hdr) {
+          check(begin(h_, hdr), "niqki_append_begin");
+          uint32_t n_new;
+          std::memcpy(&n_new, hdr + 20, 4);
+          pending = n_new != 0;   // (an empty dump is committed by its header)
+        },
+        [&](uint32_t s0, uint32_t s1, const uint8_t *data, size_t len) {
+          if (!pending) return;
+          uint64_t used = 0;
+          const int rc = slots(h_, s0, s1, data, len, &used);
+          if (rc) pending = false;   // (the engine has cancelled the append itself)
+          check(rc, "niqki_append_slots");
+          if (s1 == F) pending = false;
+        },
+        names);
+  } catch (const std::exception &e) {
+    // refused: the index is the one before the merge, and nothing is written, the -O file included
+    if (pending) (void)cancel(h_);
+    outfile->close();
+    (void)::unlink(out_path_.c_str());
+    throw std::runtime_error("--merge '" + dump_file + "': " + e.what());
+  }
+  filenames.insert(filenames.end(), std::make_move_iterator(names.begin()), std::make_move_iterator(names.end()));
+}
+
+void Index::keep_novel(uint32_t first, uint32_t threshold, const std::string &list_file) {
+  const derep_from_fn call = engine_derep_from();
+  if (!call || grp_) throw std::runtime_error("this engine has no dereplication");
+  const uint32_t N = (uint32_t)filenames.size();
+  std::vector<uint32_t> labels(N);
+  check(call(h_, first, threshold, labels.data(), nullptr, nullptr, NIQKI_MEM_HOST), "niqki_dereplicate_from");
+  write_groups(list_file, labels, first);
+  std::vector<uint8_t> keep(N);
+  bool all = true;
+  for (uint32_t g = 0; g < N; ++g) all &= (keep[g] = labels[g] == g) != 0;
+  if (!all) retain(keep);
 }
 
 // ---- dropping genomes ---------------------------------------------------------------

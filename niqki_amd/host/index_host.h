@@ -82,11 +82,24 @@ class Index {
   // index in memory is the dereplicated one from then on
   void dereplicate(const std::string &list_file, const std::string &dump_file);
 
+  // Merging dumps (long option --merge; single-GPU index; niqki_append_begin / _slots / _cancel, looked up at run time
+  // like the calls above).  The dump file is streamed through the readers of the loading constructor, whole slots go to
+  // the engine's pending append, and its names follow `filenames` (duplicates are kept as they are).  A dump the engine
+  // refuses (other lF / K / W / H, a broken payload) leaves the index as it was and is an error, and then nothing is
+  // written, the -O file included.
+  static bool has_append();
+  void merge_dump(const std::string &dump_file);
+  // The novelty filter (long option --novel; niqki_dereplicate_from + niqki_retain): the genomes below `first` are
+  // given; of the others the representatives at `threshold` (a co-occurrence count, as min_score) stay.  list_file gets the --derep lines of the genomes from
+  // `first` on; the index in memory holds the given genomes and the new representatives from then on.
+  static bool has_dereplication_from();
+  void keep_novel(uint32_t first, uint32_t threshold, const std::string &list_file);
+
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
 
  private:
-  void write_groups(const std::string &filestr, const std::vector<uint32_t> &labels);
+  void write_groups(const std::string &filestr, const std::vector<uint32_t> &labels, uint32_t first = 0);   // lines of members >= first
   struct Batch;
   void stage_batch(Batch &b, bool prefetch);
   void flush_insert(Batch &b);

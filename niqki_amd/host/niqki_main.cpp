@@ -13,6 +13,11 @@
 //   --remove <f>   drop every indexed genome named in f (one name per line) before -D and the queries (niqki_retain)
 //   --derep-dump <f>  dereplicate at the -J threshold, keep the representatives only and dump that index into f (as -D);
 //                  the rest of the run (-M, --neighbors, -Q, -l) is answered by the dereplicated index
+//   --merge <f>    append the genomes of the dump f to the index (niqki_append_*); may be repeated, ALL occurrences are
+//                  taken, in command-line order, after -L / -I / -i and before --remove and -D
+//   --novel <f>    after every index input and merge: dereplicate at the -J threshold with the genomes of -L given
+//                  (niqki_dereplicate_from), write representative<TAB>member of the other genomes into f and keep only
+//                  the representatives among them: -L db.dump --merge delta.dump --novel added.txt -J 0.9 -D db2.dump
 #include <libgen.h>
 #include <limits.h>
 #include <unistd.h>
@@ -39,7 +44,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -74,6 +79,8 @@ const Desc kDesc[] = {
     {DEREP, "", "derep", NONEMPTY, "  --derep <filename>            Dereplication at the -J threshold: greedy representatives in index order, lines representative<TAB>member."},
     {REMOVE, "", "remove", NONEMPTY, "  --remove <filename>           Drop the indexed genomes named in the file (one name per line) before -D and the queries."},
     {DEREP_DUMP, "", "derep-dump", NONEMPTY, "  --derep-dump <filename>       Dereplicate at the -J threshold and dump the index of the representatives (as -D); the rest of the run is answered by that index."},
+    {MERGE, "", "merge", NONEMPTY, "  --merge <filename>            Append the genomes of a dump to the index, after -L / -I / -i; may be repeated: every occurrence is taken, in order (of all other options only the last one counts)."},
+    {NOVEL, "", "novel", NONEMPTY, "  --novel <filename>            After all index inputs and merges: of the genomes behind those of -L keep only the representatives at the -J threshold (the -L genomes are given); lines representative<TAB>member."},
 };
 
 struct Parsed {
@@ -281,10 +288,22 @@ int main(int argc, char *argv[]) {
   }
 
   // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts; and only a
-  // single-GPU index can drop genomes
-  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP)) {
+  // single-GPU index can drop genomes or take the genomes of a dump
+  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL)) {
     if (n_gpus > 1) {
-      cerr << "niqki: the self-join (--neighbors, --cluster, --derep) needs a single-GPU index (--gpus 1)" << endl;
+      cerr << "niqki: the self-join (--neighbors, --cluster, --derep), dropping genomes and merging dumps (--merge, --novel) need a single-GPU index (--gpus 1)" << endl;
+      return EXIT_FAILURE;
+    }
+    if (o.has(MERGE) && !nqhost::Index::has_append()) {
+      cerr << "niqki: this engine cannot merge dumps" << endl;
+      return EXIT_FAILURE;
+    }
+    if (o.has(NOVEL) && !nqhost::Index::has_dereplication_from()) {
+      cerr << "niqki: this engine has no dereplication" << endl;
+      return EXIT_FAILURE;
+    }
+    if (o.has(NOVEL) && !nqhost::Index::has_retain()) {
+      cerr << "niqki: this engine cannot drop genomes" << endl;
       return EXIT_FAILURE;
     }
     if ((o.has(REMOVE) || o.has(DEREP_DUMP)) && !nqhost::Index::has_retain()) {
@@ -311,10 +330,19 @@ int main(int argc, char *argv[]) {
     else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib, top_k));
     if (const unsigned expect = (unsigned)int_opt(o, GENOME_SIZE, 0)) ix->select_best_H(expect);   // src/niqki.cpp:303-305
 
+    const uint32_t n_loaded = (uint32_t)ix->getNbGenomes();   // --novel: the genomes of -L are given (none without -L)
     RunClock clk;
     for (const Phase &ph : kIndexPhases) run_phase(*ix, o, ph);
     if (o.has(DOWNLAD)) cout << "--indexdownload needs network access and is not part of this build" << endl;
-    RunClock::tp remove_begin, remove_end;
+    if (o.has(MERGE))   // the one option of which every occurrence counts
+      for (const string &dump : o.opts.at(MERGE)) ix->merge_dump(dump);
+    RunClock::tp novel_begin, novel_end, remove_begin, remove_end;
+    if (o.has(NOVEL)) {
+      novel_begin = system_clock::now();
+      // the -J of THIS run where it is given: an index that -L loaded carries the min_score of its dump
+      ix->keep_novel(n_loaded, o.has(MIN) ? niqki_min_score(min_jaccard, ix->lF) : ix->min_score, o.last(NOVEL));
+      novel_end = system_clock::now();
+    }
     if (o.has(REMOVE)) {   // after everything that indexes, before the dump: -L old --remove names -D new
       remove_begin = system_clock::now();
       ix->remove_listed(o.last(REMOVE));
@@ -322,6 +350,7 @@ int main(int argc, char *argv[]) {
     }
     if (o.has(DUMP)) ix->dump_index_disk(o.last(DUMP));
     clk.index_done();
+    if (o.has(NOVEL)) RunClock::row("| Novelty filter lasted (s)         |", novel_begin, novel_end);
     if (o.has(REMOVE)) RunClock::row("| Remove lasted (s)                 |", remove_begin, remove_end);
     if (o.has(CLUSTER)) {   // a phase of its own between indexing and the queries
       ix->cluster_to_file(o.last(CLUSTER));
