@@ -46,8 +46,8 @@ NQ_HD uint32_t clz64(uint64_t x) {
 #endif
 }
 
-// get_fingerprint: src/niqki_index.cpp:277-287; h == 0 gives 0 (bsr(0) is UB
-// in the reference, observed 0).
+// get_fingerprint: src/niqki_index.cpp:277-287; h == 0 counts 64 leading zeros: 0 for H <= 6,
+// (2^H - 1 - 64) << M above (bsr(0) is undefined in the reference).
 NQ_HD uint32_t fingerprint(uint64_t h, uint32_t M, uint32_t mask_m, uint32_t max_rem) {
   uint32_t lz = clz64(h);
   uint32_t rem = lz < max_rem ? max_rem - lz : 0u;

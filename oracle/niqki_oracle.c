@@ -44,7 +44,10 @@ int32_t nqo_fingerprint(uint64_t h, uint32_t W, uint32_t H) {
    * (2^H-1 - leading_zeros) in the H bits above them. */
   uint32_t M = W - H;
   uint32_t mask_m = ((uint32_t)1 << M) - 1u;
-  int32_t lz = h ? __builtin_clzll(h) : 64; /* bsr(0) is UB there; observed 0 */
+  /* h == 0: the reference runs bsr on 0 (:199-206), whose result is undefined.  Here lz = 64: the
+   * fingerprint is 0 up to H = 6 and (2^H - 1 - 64) << M above.  (Observed in one build of the reference:
+   * lz = 63 -- the two differ for H >= 7 only.  tests/test_oracle_vs_reference.py pins this value.) */
+  int32_t lz = h ? __builtin_clzll(h) : 64;
   int32_t rem = (int32_t)(((uint32_t)1 << H) - 1u) - lz;
   if (rem < 0) rem = 0;
   return (int32_t)((uint32_t)(h & mask_m) + ((uint32_t)rem << M));
@@ -59,7 +62,7 @@ int32_t nqo_fingerprint_stale(uint64_t h, uint32_t W, uint32_t H, uint32_t H0) {
    * and may overlap or leave [0, 2^W). */
   uint32_t M = W - H;
   uint32_t mask_m = ((uint32_t)1 << (W - H0)) - 1u;
-  int32_t lz = h ? __builtin_clzll(h) : 64;
+  int32_t lz = h ? __builtin_clzll(h) : 64; /* h == 0: as in nqo_fingerprint, with the constructor's H0 */
   int32_t rem = (int32_t)(((uint32_t)1 << H0) - 1u) - lz;
   if (rem < 0) rem = 0;
   return (int32_t)((uint32_t)(h & mask_m) + ((uint32_t)rem << M));

@@ -48,8 +48,8 @@ uint32_t nqo_min_score(double min_fract, uint32_t S);
 uint64_t nqo_rev64(uint64_t x);
 uint64_t nqo_unrev64(uint64_t x);
 
-/* src/niqki_index.cpp:277-287 (+ asm_log2 :199-206).  h==0 -> 0 (bsr UB in the
- * reference, observed result 0). */
+/* src/niqki_index.cpp:277-287 (+ asm_log2 :199-206).  h == 0 counts 64 leading zeros:
+ * 0 for H <= 6, (2^H - 1 - 64) << (W - H) above (bsr on 0 is undefined in the reference). */
 int32_t nqo_fingerprint(uint64_t h, uint32_t W, uint32_t H);
 
 /* get_fingerprint with the stale mask_M / maximal_remainder a `-G` run has:
