@@ -299,12 +299,35 @@ __device__ __forceinline__ uint32_t rev64_hi_mad(uint64_t canon) {
   mix_round(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
   return mix_round_hi(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
 }
+// The same, handing out the word after the first round: x1 = ((canon >> 32) ^ canon) * kRevMul.  The filtered fast loops
+// push x1, not canon, and candidate_update() finishes both of a candidate's hashes from it.
+__device__ __forceinline__ uint32_t rev64_hi_mad_x1(uint64_t canon, uint64_t &x1) {
+  uint32_t lo = (uint32_t)canon, hi = (uint32_t)(canon >> 32);
+  mix_round(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
+  x1 = ((uint64_t)hi << 32) | lo;
+  return mix_round_hi(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
+}
+// mix_round without the xor: x = x * c, a plain 64 x 64 -> 64 product (3 x v_mad_u64_u32 + 1 add)
+__device__ __forceinline__ void mul_round(uint32_t &lo, uint32_t &hi, uint32_t clo, uint32_t chi) {
+  const uint64_t t = mul64(hi, clo);
+  const uint64_t p = mad64(lo, chi, t);   // low word: lo * chi + hi * clo
+  const uint64_t q = mul64(lo, clo);
+  lo = (uint32_t)q;
+  hi = (uint32_t)p + (uint32_t)(q >> 32);
+}
+// The two multipliers are inverses of each other mod 2^64 (that is what makes unrevhash64 the inverse of revhash64,
+// src/niqki_index.cpp:291-305), so with x1 = fold(canon) * kRevMul, fold(x) = x ^ (x >> 32):
+//   fold(canon) * kUnrevMul = x1 * kUnrevMul * kUnrevMul = x1 * kUnrevMul2
+// and the slot hash's first round is a plain product of the word the filter already has.
+constexpr uint64_t kUnrevMul2 = kUnrevMul * kUnrevMul;
+static_assert(kRevMul * kUnrevMul == 1ULL, "candidate_update() finishes the slot hash from the filter's first round: the multipliers must be inverses mod 2^64");
+static_assert(kUnrevMul2 == 0xEB9041BCFCD1CDD9ULL, "kUnrevMul squared mod 2^64");
 
 constexpr uint32_t kFastKMin = 17;   // smallest K of the fast filtered path: the rc code, at bit 2K - 2 of the reverse word, is in its high word
 constexpr uint32_t kStack = 192;  // candidate k-mers per wave-private stack: < 64 left by a drain + two steps of <= 64
 
-// Candidate store of one step: lanes whose hash word hh is below thr push canon onto the wave's stack
-// (LDS byte address of its top in `top`, wave-uniform, advanced here).  gfx950 wants two wait states
+// Candidate store of one step: lanes whose hash word hh is below thr push canon (the fast loops: the hash's first
+// round x1, rev64_hi_mad_x1()) onto the wave's stack (LDS byte address of its top in `top`, wave-uniform, advanced here).  gfx950 wants two wait states
 // between a vector compare and a vector instruction that reads its mask as an operand (the mbcnt): the two
 // scalar instructions in between are that.
 __device__ __forceinline__ void push_candidates(uint32_t hh, uint32_t thr, uint64_t canon, uint32_t &top) {
@@ -394,14 +417,16 @@ __device__ __forceinline__ uint64_t shl2_add64(uint64_t x, uint64_t e) {
 }
 
 // slot + fingerprint + per-slot min of up to 64 candidates (:346-355), whole sketch in LDS at kCellOff
-// upwards (S <= 15).  The hash of the filter is recomputed: passing its words through the stack costs
-// more register traffic than the 5 instructions saved.
-__device__ __forceinline__ void candidate_update(uint64_t canon, const Derived &d, uint32_t lds0, bool live) {
-  uint32_t lo = (uint32_t)canon, hi = (uint32_t)(canon >> 32);
+// upwards (S <= 15).  A candidate comes off the stack as x1, the word after the first round of its revhash64
+// (rev64_hi_mad_x1()): the hash takes its second round from there (passing the filter's second round through the
+// stack as well would cost more register traffic than those 5 instructions), and the slot hash's first round is
+// x1 * kUnrevMul2, 4 instructions.  22 vector instructions per drain of 64 candidates, 27 when both hashes started
+// from canon (profiles/r10_sketch_cost_model.txt).
+__device__ __forceinline__ void candidate_update(uint64_t x1, const Derived &d, uint32_t lds0, bool live) {
+  uint32_t lo = (uint32_t)x1, hi = (uint32_t)(x1 >> 32);
   uint32_t ulo = lo, uhi = hi;
-  mix_round(ulo, uhi, (uint32_t)kUnrevMul, (uint32_t)(kUnrevMul >> 32));
+  mul_round(ulo, uhi, (uint32_t)kUnrevMul2, (uint32_t)(kUnrevMul2 >> 32));
   const uint32_t uh = mix_round_hi(ulo, uhi, (uint32_t)kUnrevMul, (uint32_t)(kUnrevMul >> 32));
-  mix_round(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
   mix_round(lo, hi, (uint32_t)kRevMul, (uint32_t)(kRevMul >> 32));
   // get_fingerprint (:277-287) of h = hi : lo ^ hi.  A candidate's high word is below 2^29 and, but for one
   // hash in 2^29, not 0: its leading zeros are those of the high word (one v_ffbh); the rare zero high word
@@ -589,8 +614,9 @@ __device__ __forceinline__ void roll_records(const SketchArgs &a, uint32_t entry
           // (the entry's rc code and any carry out of it land at bit 2K and above: the `and` clears them)
           rc = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
           fw = shl2_add64(fw, ent) & fw_mask;   // (only the high word's `and` is an instruction)
-          const uint64_t canon = min62(fw, rc);   // :345
-          push_candidates(rev64_hi_mad(canon), thr, canon, top);
+          uint64_t x1;
+          const uint32_t hh = rev64_hi_mad_x1(min62(fw, rc), x1);   // :345
+          push_candidates(hh, thr, x1, top);
           // two steps add at most 128 to fewer than 64.  Unlikely: the drain is laid out behind the loop,
           // the common path has no taken branch
           if (check && __builtin_expect(top >= bottom + 512u, 0)) {
@@ -654,8 +680,15 @@ __device__ __forceinline__ void roll_records(const SketchArgs &a, uint32_t entry
           if (!FILTER) {
             sketch_update(canon, d, sk, live, hsel);
           } else {
-            // dead steps get an all-ones hash word and never pass
-            push_candidates(live ? rev64_hi(canon) : 0xFFFFFFFFu, thr, canon, top);
+            // dead steps get an all-ones hash word and never pass.  The stack's word is the one its drain takes:
+            // x1 where that is candidate_update() (this loop serves the fast form's partial chunks too)
+            if (FAST) {
+              uint64_t x1;
+              const uint32_t hh = rev64_hi_mad_x1(canon, x1);
+              push_candidates(live ? hh : 0xFFFFFFFFu, thr, x1, top);
+            } else {
+              push_candidates(live ? rev64_hi(canon) : 0xFFFFFFFFu, thr, canon, top);
+            }
             if (top >= bottom + 512u) drain64();
           }
         }
@@ -933,8 +966,9 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
       // :225-229 and :233-236 with the entry's pre-placed codes (see roll_records)
       rc = shr2_64(rc | (ent & 0xFFFFFFFF00000000ULL));
       fw = shl2_add64(fw, ent) & fw_mask;
-      const uint64_t canon = min62(fw, rc);   // :345
-      push_candidates(rev64_hi_mad(canon), thr, canon, top);
+      uint64_t x1;
+      const uint32_t hh = rev64_hi_mad_x1(min62(fw, rc), x1);   // :345
+      push_candidates(hh, thr, x1, top);
       if (check && __builtin_expect(top >= bottom + 512u, 0)) {
         drain64();
         if (top >= bottom + 512u) drain64();
@@ -950,9 +984,9 @@ __device__ __forceinline__ void roll_records_lines(const SketchArgs &a, uint32_t
       const uint64_t fw2 = shl2_add64(fw, ent) & fw_mask;
       rc = live ? rc2 : rc;
       fw = live ? fw2 : fw;
-      const uint64_t canon = min62(fw, rc);
-      const uint32_t hh = rev64_hi_mad(canon);
-      push_candidates(live ? hh : 0xFFFFFFFFu, thr, canon, top);
+      uint64_t x1;
+      const uint32_t hh = rev64_hi_mad_x1(min62(fw, rc), x1);
+      push_candidates(live ? hh : 0xFFFFFFFFu, thr, x1, top);
       if (check && __builtin_expect(top >= bottom + 512u, 0)) {
         drain64();
         if (top >= bottom + 512u) drain64();

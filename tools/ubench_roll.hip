@@ -13,6 +13,8 @@
 //      entry, the reverse word's `or` before its shift)
 //   6  form 1 with the second round of the filter hash in four instructions (v_mul_hi in the first mad's addend)
 //   7  forms 4 + 5 + 6 together: the product's loop since r07
+//   8  form 7 pushing x1, the word after the hash's first round, instead of the k-mer (rev64_hi_mad_x1): the product's
+//      loop since r10
 // Form 1 is the loop as it was up to r06, built from 32-bit pieces and restated here (ub_*), so that the two stay
 // comparable in one run.
 // Same occupancy as the kernel: 1024-thread workgroups, one per CU (130 KB of dynamic LDS), 4 waves per SIMD.
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(1024) void roll_kernel(const uint8_t *bytes, const 
                                                     uint32_t *sink) {
   extern __shared__ __align__(16) uint32_t smem[];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  constexpr bool MINF = VAR == 4 || VAR == 7, ROLL = VAR == 5 || VAR == 7, H4 = VAR == 6 || VAR == 7;
+  constexpr bool MINF = VAR == 4 || VAR >= 7, ROLL = VAR == 5 || VAR >= 7, H4 = VAR == 6 || VAR >= 7, X1 = VAR == 8;
   uint2 *lut64 = (uint2 *)smem;
   for (uint32_t i = tid; i < 256; i += 1024) {
     const uint32_t e = code_entry(i);
@@ -133,9 +135,10 @@ __global__ __launch_bounds__(1024) void roll_kernel(const uint8_t *bytes, const 
         rc = shr2_64(rc) | (ent & 0xFFFFFFFF00000000ULL);
       }
       const uint64_t canon = MINF ? min62(fw, rc) : (fw < rc ? fw : rc);
-      const uint32_t hh = ub_rev64_hi_mad<H4>(canon);
+      uint64_t x1 = canon;
+      const uint32_t hh = X1 ? rev64_hi_mad_x1(canon, x1) : ub_rev64_hi_mad<H4>(canon);
       if (VAR == 1 || VAR >= 4) {
-        push_candidates(hh, thr, canon, top);
+        push_candidates(hh, thr, x1, top);
       } else if (VAR == 3) {
         uint32_t at;
         uint64_t mask;
@@ -242,7 +245,7 @@ int main(int argc, char **argv) {
   const uint64_t n_fill = n_bytes / 16 + 1 > n_words ? n_bytes / 16 + 1 : n_words;
   hipLaunchKernelGGL(fill_kernel, dim3((uint32_t)((n_fill + 255) / 256)), dim3(256), 0, 0, bytes, packed, n_bytes, n_words);
   CK(hipDeviceSynchronize());
-  double ns[8], cy[8];
+  double ns[9], cy[9];
   if (run<1>(bytes, packed, groups, reps, sink, &ns[1], &cy[1])) return 1;
   if (run<0>(bytes, packed, groups, reps, sink, &ns[0], &cy[0])) return 1;
   if (run<2>(bytes, packed, groups, reps, sink, &ns[2], &cy[2])) return 1;
@@ -251,13 +254,15 @@ int main(int argc, char **argv) {
   if (run<5>(bytes, packed, groups, reps, sink, &ns[5], &cy[5])) return 1;
   if (run<6>(bytes, packed, groups, reps, sink, &ns[6], &cy[6])) return 1;
   if (run<7>(bytes, packed, groups, reps, sink, &ns[7], &cy[7])) return 1;
+  if (run<8>(bytes, packed, groups, reps, sink, &ns[8], &cy[8])) return 1;
   if (run<1>(bytes, packed, groups, reps, sink, &ns[1], &cy[1])) return 1;   // (again, after everything is warm)
-  const char *name[8] = {"0  byte table, no push", "1  byte table + mbcnt push (product to r06)", "2  2-bit packed windows + mbcnt push",
+  const char *name[9] = {"0  byte table, no push", "1  byte table + mbcnt push (product to r06)", "2  2-bit packed windows + mbcnt push",
                          "3  byte table + LDS-ranked push", "4  form 1, canonical choice by v_min_f64", "5  form 1, forward roll by v_lshl_add_u64",
-                         "6  form 1, second hash round in 4", "7  forms 4 + 5 + 6 (product since r07)"};
+                         "6  form 1, second hash round in 4", "7  forms 4 + 5 + 6 (product r07 to r09)",
+                         "8  form 7 pushing x1 (product since r10)"};
   printf("hot loop of sketch_kernel<1024,32,31> in isolation: %u groups of 16 k-mer steps per lane, 256 workgroups x 1024 threads, no drains\n", groups);
   printf("%-42s %14s %22s %10s\n", "form", "ps/step/lane", "SIMD cycles/wave step", "vs form 1");
-  for (int v : {1, 0, 2, 3, 4, 5, 6, 7})
+  for (int v : {1, 0, 2, 3, 4, 5, 6, 7, 8})
     printf("%-42s %14.2f %22.1f %10.3f\n", name[v], ns[v] * 1e3, cy[v], ns[v] / ns[1]);
   return 0;
 }
