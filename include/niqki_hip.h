@@ -499,6 +499,44 @@ int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uin
 int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, uint32_t *labels,
                            uint32_t *label_counts, uint32_t *n_representatives, int mem);
 
+/* The complete single-linkage hierarchy of the indexed genomes, and the spanning forest it is, in ONE self-join: what
+ * niqki_cluster answers at one threshold, for every threshold >= floor.
+ * Definitions.  count(a, b) is the co-occurrence count of the stored sketches (the cell niqki_matrix_range gives,
+ * before any u16 wrap; at S = 16 the exact sum of the two planes).  labels_t[g] is what niqki_cluster(ix, t) returns.
+ * Edge order: undirected pairs lo < hi are strictly ordered by (1) the larger count first, (2) among equal counts the
+ * smaller lo, (3) then the smaller hi.
+ * Forest: the unique maximum spanning forest, under that order, of the graph whose edges are the pairs with
+ * count >= max(floor, 1) -- what Kruskal keeps when it takes the edges in that order.  edge_lo / edge_hi /
+ * edge_count[0 .. n_edges) hold it in that order, n_edges = N - *n_roots; the arrays have N places each, the places
+ * from n_edges on are not written.
+ * Hierarchy: for every genome g, merge_count[g] is the largest t >= max(floor, 1) with labels_t[g] != g and
+ * merge_into[g] is labels_t[g] at that t.  If there is no such t (g is the smallest id of its component at the floor)
+ * merge_into[g] = g and merge_count[g] = 0.  merge_into[g] < g whenever it differs from g, and a child's merge_count
+ * is strictly larger than its parent's.  labels_t for every t >= max(floor, 1) is read off the two arrays: from g,
+ * follow merge_into while merge_count >= t (and merge_into differs).
+ * floor = 0: the result of floor = 1, and then every remaining root r > 0 joins genome 0 at count 0: edges (0, r, 0)
+ * in ascending r at the end of the list, merge_into[r] = 0, merge_count[r] = 0, *n_roots = 1 (canonical under the
+ * edge order: the count-0 pairs come last, and (0, r) is the first of them that joins r).
+ * The result is a function of the index and floor only: it does not depend on batch sizes, options, top_k (ignored),
+ * tile count, paging, a delta segment or the order in which the device links.  The handle's min_score and top_k are
+ * unchanged when the call returns, also when it fails.  Handles as niqki_cluster: whole-range single-GPU handles,
+ * resident or paged, any tile count, with or without a delta segment, S <= 16; NIQKI_E_STATE on a slot-range shard.
+ * More than 2^23 genomes: NIQKI_E_INVALID (an edge is one 64-bit key with 23 bits an id; niqki_last_error says so).
+ * No genomes: NIQKI_OK, *n_roots = 0.  merge_into and merge_count may both be NULL, the three edge arrays may all be
+ * NULL, n_roots (host memory whatever mem is) may be NULL.  mem as in niqki_cluster: with NIQKI_MEM_DEVICE the five
+ * arrays are device arrays, written in stream order; the call synchronises.
+ * One self-join: the batches, the hit buffers, their budget (option "cluster_ws_mib") and the halving rule are
+ * niqki_cluster's.  The device keeps a forest of fewer than N edges; per batch Boruvka rounds (offers with a 64-bit
+ * atomic maximum per component, hooks, pointer jumping) make the forest of the old forest and the batch's pairs; after
+ * the last batch the forest crosses to the host once, is sorted, and a union-find over its levels gives the hierarchy
+ * (DESIGN.md 4.6g).  Device state: 28 bytes a genome.
+ * niqki_get_stat, the last call: "linkage_rounds" (the most rounds in which a batch hooked components),
+ * "linkage_splits", "linkage_pairs" (hits the batches held); while profiling is on, with one synchronisation per
+ * batch: "linkage_us_read", "linkage_us_hits", "linkage_us_forest", "linkage_us_finish" (microseconds; the last one
+ * by the host's clock: copy, sort, hierarchy, results). */
+int niqki_linkage(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_t *merge_count,
+                  uint32_t *edge_lo, uint32_t *edge_hi, uint32_t *edge_count, uint32_t *n_roots, int mem);
+
 /* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
  * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
  * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses

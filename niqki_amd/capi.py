@@ -119,6 +119,7 @@ ABI = [
     ("niqki_cluster", _int, [_vp, _u32, _vp, C.POINTER(_u32), _int]),
     ("niqki_dereplicate", _int, [_vp, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_dereplicate_from", _int, [_vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), _int]),
+    ("niqki_linkage", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
@@ -184,6 +185,21 @@ def lib():
             f.argtypes = args
         _lib = L
     return _lib
+
+
+def cut_linkage(merge_into, merge_count, t):
+    """labels of Engine.cluster(t) from Engine.linkage(floor)'s hierarchy, t >= floor: from every genome follow
+    merge_into while merge_count >= t.  (merge_count descends strictly along a chain, so the walk stops at the first
+    genome below t, or at a root.)"""
+    into = np.asarray(merge_into, dtype=np.int64)
+    cnt = np.asarray(merge_count, dtype=np.int64)
+    ids = np.arange(into.size, dtype=np.int64)
+    up = np.where((cnt >= t) & (into != ids), into, ids)     # one step, or none
+    while True:
+        nxt = up[up]
+        if np.array_equal(nxt, up):
+            return up.astype(np.uint32)
+        up = nxt
 
 
 def row_stride(n):
@@ -571,6 +587,23 @@ class Engine:
         self._ck(self.L.niqki_dereplicate_from(self.h, int(first), int(threshold), _p(labels), _p(lc) if counts else None,
                                                C.byref(n), MEM_HOST))
         return (labels, lc, int(n.value)) if counts else (labels, int(n.value))
+
+    def linkage(self, floor, edges=True):
+        """The complete single-linkage hierarchy at co-occurrence counts >= floor, in one self-join:
+        (merge_into, merge_count, (edge_lo, edge_hi, edge_count) | None, n_roots).  merge_count[g] is the largest
+        threshold at which genome g is not the smallest id of its cluster, merge_into[g] its cluster's label there
+        (g and 0 for a genome that is one down to the floor): cut_linkage reads the labels of cluster(t) off the two
+        for any t >= floor.  The edges are the maximum spanning forest in edge order (larger count, then smaller lo,
+        then smaller hi), N - n_roots of them."""
+        n_g = self.n_genomes
+        into = np.empty(n_g, dtype=np.uint32)
+        cnt = np.empty(n_g, dtype=np.uint32)
+        e3 = [np.zeros(n_g, dtype=np.uint32) for _ in range(3)] if edges else None
+        n = _u32(0)
+        ep = [_p(a) for a in e3] if edges else [None, None, None]
+        self._ck(self.L.niqki_linkage(self.h, int(floor), _p(into), _p(cnt), ep[0], ep[1], ep[2], C.byref(n), MEM_HOST))
+        n_edges = n_g - int(n.value)
+        return into, cnt, (tuple(a[:n_edges].copy() for a in e3) if edges else None), int(n.value)
 
     def retain(self, keep):
         """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),

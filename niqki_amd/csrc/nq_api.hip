@@ -574,6 +574,14 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "derep_us_decide")) { *value = (uint64_t)(ix->derep_stats.ms[2] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "derep_us_assign")) { *value = (uint64_t)(ix->derep_stats.ms[3] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "derep_pairs")) { *value = ix->derep_stats.pairs; return NIQKI_OK; }
+  // the last niqki_linkage call; the phases and the hits while profiling was on
+  if (!std::strcmp(key, "linkage_rounds")) { *value = ix->linkage_stats.rounds; return NIQKI_OK; }
+  if (!std::strcmp(key, "linkage_splits")) { *value = ix->linkage_stats.splits; return NIQKI_OK; }
+  if (!std::strcmp(key, "linkage_us_read")) { *value = (uint64_t)(ix->linkage_stats.ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "linkage_us_hits")) { *value = (uint64_t)(ix->linkage_stats.ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "linkage_us_forest")) { *value = (uint64_t)(ix->linkage_stats.ms[2] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "linkage_us_finish")) { *value = (uint64_t)(ix->linkage_stats.ms[3] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "linkage_pairs")) { *value = ix->linkage_stats.pairs; return NIQKI_OK; }
   // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
   if (!std::strcmp(key, "retain_us_rank")) { *value = (uint64_t)(ix->retain_ms[0] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "retain_us_compact")) { *value = (uint64_t)(ix->retain_ms[1] * 1000.0); return NIQKI_OK; }

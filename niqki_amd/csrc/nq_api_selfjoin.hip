@@ -2,11 +2,15 @@
 // sketches, the sparse form of Index::query_range, src/niqki_index.cpp:570-610), niqki_cluster (single-linkage
 // clusters: the link and flatten kernels over the hit lists of the stored sketches) and niqki_dereplicate /
 // niqki_dereplicate_from (greedy representatives in index order, the genomes below `first` given: the decide, assign
-// and finish kernels over the same hit lists).  The kernels are in nq_cluster.hip, the hit lists come from the query
-// path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c, 4.6f.
+// and finish kernels over the same hit lists) and niqki_linkage (the single-linkage forest and hierarchy: the forest
+// kernels over the same hit lists, then a host pass over fewer than N edges).  The kernels are in nq_cluster.hip, the
+// hit lists come from the query path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c, 4.6f, 4.6g.
 #include "nq_handle.h"
+#include "nq_linkage_key.h"
 
 #include <algorithm>
+#include <chrono>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -47,6 +51,7 @@ struct SelfJoin {
   // Enqueues the consumer's kernels on the hits (off, hit_counts, hit_gids) of genomes [t0, t0 + n) and ends each of
   // its phases k = 2 .. phases - 1 with mark(k + 1).
   std::function<int(const unsigned long long *, const uint32_t *, const uint32_t *, uint32_t, uint32_t)> consume;
+  bool count_pairs = false;   // stats.pairs also without profiling (the total is read back per batch anyway)
   uint64_t stride = 0, room = 0;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // phase k lies between ev[k] and ev[k + 1]
 
@@ -99,8 +104,8 @@ int self_join_batch(SelfJoin &r, uint32_t t0, uint32_t n, uint32_t *fitted) {
       NQ_HIP(ix, hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
       r.stats.ms[k] += ms;
     }
-    r.stats.pairs += out.total;
   }
+  if (ix->prof || r.count_pairs) r.stats.pairs += out.total;
   *fitted = n;
   return NIQKI_OK;
 }
@@ -200,6 +205,125 @@ int derep_run(niqki_index *ix, uint32_t first, uint32_t threshold, uint32_t *lab
   return NIQKI_OK;
 }
 
+// smallest-id-root union-find on the host (the hierarchy of niqki_linkage); find() halves paths, no recursion
+struct HostForest {
+  std::vector<uint32_t> parent;
+  explicit HostForest(uint32_t n) : parent(n) {
+    for (uint32_t g = 0; g < n; ++g) parent[g] = g;
+  }
+  uint32_t find(uint32_t x) {
+    while (parent[x] != x) {
+      parent[x] = parent[parent[x]];
+      x = parent[x];
+    }
+    return x;
+  }
+};
+
+// One self-join at max(floor, 1); the consumer keeps the maximum spanning forest of everything seen so far (nq_cluster.hip).
+// After the last batch the forest, fewer than N keys, crosses to the host once, is sorted into the edge order and gives
+// the edge arrays and the hierarchy: a union-find with the smaller id as root, level by level (a level = the edges of
+// one count); merge_into is the root at the END of the level that took g's root status.
+int linkage_run(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_t *merge_count, uint32_t *edge_lo, uint32_t *edge_hi,
+                uint32_t *edge_count, uint32_t *n_roots, int mem) {
+  const uint32_t N = ix->n_genomes;
+  int rc = build_if_needed(ix);
+  if (rc) return rc;
+  // best[N], two forests [N] (8 bytes each), comp[N], info
+  const uint32_t info_words = nq::kLinkageInfoHead + nq::linkage_rounds(N);
+  if ((rc = ensure(ix, ix->ws_parent, (size_t)N * 28 + (size_t)info_words * 4))) return rc;
+  unsigned long long *best = (unsigned long long *)ix->ws_parent.p, *forest[2] = {best + N, best + 2 * (size_t)N};
+  uint32_t *comp = (uint32_t *)(best + 3 * (size_t)N), *info = comp + N;
+  int cur = 0;   // forest[cur] holds the forest so far
+  SelfJoin r(ix, "niqki_linkage", ix->linkage_stats, 3);
+  r.count_pairs = true;
+  r.consume = [&](const unsigned long long *off, const uint32_t *hc, const uint32_t *hg, uint32_t t0, uint32_t n) {
+    NQ_HIP(ix, nq::launch_linkage_batch(comp, best, forest[cur], forest[cur ^ 1], info, N, off, hc, hg, t0, n, ix->stream));
+    cur ^= 1;
+    return r.mark(3);
+  };
+  NQ_HIP(ix, hipMemsetAsync(info, 0, (size_t)info_words * 4, ix->stream));
+  if ((rc = self_join_batches(r, N))) return rc;
+  const auto t_finish = std::chrono::steady_clock::now();
+  uint32_t head[4] = {0, 0, 0, 0};
+  std::vector<unsigned long long> keys(N);
+  NQ_HIP(ix, hipMemcpyAsync(head, info, 16, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipMemcpyAsync(keys.data(), forest[cur], (size_t)N * 8, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  ix->linkage_stats.rounds = head[2];
+  if (head[3] || head[0] >= N) return fail(ix, NIQKI_E_STATE, "niqki_linkage: the forest rounds did not end (a bug)");
+  keys.resize(head[0]);
+  std::sort(keys.begin(), keys.end(), std::greater<unsigned long long>());
+  const uint32_t n_tree = (uint32_t)keys.size();
+  // floor 0: every remaining root r > 0 joins genome 0 at count 0, ascending r, behind the others
+  std::vector<uint32_t> into(N), cnt(N, 0u), losers;
+  HostForest uf(N);
+  for (uint32_t g = 0; g < N; ++g) into[g] = g;
+  for (uint32_t e = 0; e < n_tree;) {
+    const uint32_t c = nq::linkage_count(keys[e]);
+    losers.clear();
+    for (; e < n_tree && nq::linkage_count(keys[e]) == c; ++e) {
+      const uint32_t a = uf.find(nq::linkage_lo(keys[e])), b = uf.find(nq::linkage_hi(keys[e]));
+      if (a == b) return fail(ix, NIQKI_E_STATE, "niqki_linkage: the forest holds a cycle (a bug)");
+      uf.parent[std::max(a, b)] = std::min(a, b);
+      losers.push_back(std::max(a, b));
+    }
+    for (uint32_t g : losers) {
+      into[g] = uf.find(g);
+      cnt[g] = c;
+    }
+  }
+  std::vector<uint32_t> zero_roots;
+  if (floor == 0)
+    for (uint32_t g = 1; g < N; ++g)
+      if (into[g] == g) {
+        zero_roots.push_back(g);
+        into[g] = 0;
+      }
+  const uint32_t n_edges = n_tree + (uint32_t)zero_roots.size();
+  std::vector<uint32_t> el, eh, ec;
+  if (edge_lo) {
+    el.resize(n_edges);
+    eh.resize(n_edges);
+    ec.resize(n_edges);
+    for (uint32_t e = 0; e < n_tree; ++e) {
+      el[e] = nq::linkage_lo(keys[e]);
+      eh[e] = nq::linkage_hi(keys[e]);
+      ec[e] = nq::linkage_count(keys[e]);
+    }
+    for (uint32_t k = 0; k < zero_roots.size(); ++k) {
+      el[n_tree + k] = 0;
+      eh[n_tree + k] = zero_roots[k];
+      ec[n_tree + k] = 0;
+    }
+  }
+  if (mem == NIQKI_MEM_DEVICE) {
+    if (merge_into) {
+      NQ_HIP(ix, hipMemcpyAsync(merge_into, into.data(), (size_t)N * 4, hipMemcpyHostToDevice, ix->stream));
+      NQ_HIP(ix, hipMemcpyAsync(merge_count, cnt.data(), (size_t)N * 4, hipMemcpyHostToDevice, ix->stream));
+    }
+    if (edge_lo && n_edges) {
+      NQ_HIP(ix, hipMemcpyAsync(edge_lo, el.data(), (size_t)n_edges * 4, hipMemcpyHostToDevice, ix->stream));
+      NQ_HIP(ix, hipMemcpyAsync(edge_hi, eh.data(), (size_t)n_edges * 4, hipMemcpyHostToDevice, ix->stream));
+      NQ_HIP(ix, hipMemcpyAsync(edge_count, ec.data(), (size_t)n_edges * 4, hipMemcpyHostToDevice, ix->stream));
+    }
+    NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // (the vectors leave scope)
+  } else {
+    if (merge_into) {
+      std::copy(into.begin(), into.end(), merge_into);
+      std::copy(cnt.begin(), cnt.end(), merge_count);
+    }
+    if (edge_lo) {
+      std::copy(el.begin(), el.end(), edge_lo);
+      std::copy(eh.begin(), eh.end(), edge_hi);
+      std::copy(ec.begin(), ec.end(), edge_count);
+    }
+  }
+  if (ix->prof) ix->linkage_stats.ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_finish).count();
+  if (n_roots) *n_roots = N - n_edges;
+  return NIQKI_OK;
+}
+
 }  // namespace
 
 }  // namespace nqi
@@ -285,6 +409,24 @@ int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, 
 int niqki_dereplicate(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_t *label_counts, uint32_t *n_representatives,
                       int mem) {
   return niqki_dereplicate_from(ix, 0, threshold, labels, label_counts, n_representatives, mem);
+}
+
+int niqki_linkage(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_t *merge_count, uint32_t *edge_lo, uint32_t *edge_hi,
+                  uint32_t *edge_count, uint32_t *n_roots, int mem) {
+  if (!ix) return NIQKI_E_INVALID;
+  if (!merge_into != !merge_count) return fail(ix, NIQKI_E_INVALID, "niqki_linkage: merge_into and merge_count go together");
+  if (!edge_lo != !edge_hi || !edge_lo != !edge_count) return fail(ix, NIQKI_E_INVALID, "niqki_linkage: the three edge arrays go together");
+  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_linkage: a slot-range shard sees partial counts; the self-join needs a whole-range handle");
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  ix->linkage_stats = SelfJoinStats();
+  const uint32_t N = ix->n_genomes;
+  if (N == 0) {
+    if (n_roots) *n_roots = 0;
+    return NIQKI_OK;
+  }
+  if (!nq::linkage_fits(N)) return fail(ix, NIQKI_E_INVALID, "niqki_linkage: more than 2^23 genomes (the edge key holds 23 bits an id)");
+  CallThreshold guard(ix, std::max(floor, 1u));
+  return linkage_run(ix, floor, merge_into, merge_count, edge_lo, edge_hi, edge_count, n_roots, mem);
 }
 
 }  // extern "C"

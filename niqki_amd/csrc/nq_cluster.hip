@@ -1,8 +1,10 @@
 // nq_cluster.hip -- the self-join of an index: niqki_neighbors_range (the hits of the stored sketches, the sparse form
 // of Index::query_range, src/niqki_index.cpp:570-610) and niqki_cluster (single-linkage clusters: the link and flatten
 // kernels over the hit lists of the stored sketches) and niqki_dereplicate (greedy representatives in index order: the
-// decide, assign and finish kernels over the same hit lists).  DESIGN.md 4.6b, 4.6c.
+// decide, assign and finish kernels over the same hit lists) and niqki_linkage (the single-linkage forest: Boruvka
+// rounds over the same hit lists).  DESIGN.md 4.6b, 4.6c, 4.6g.
 #include "nq_handle.h"
+#include "nq_linkage_key.h"
 
 #include <algorithm>
 #include <string>
@@ -283,6 +285,161 @@ __global__ void derep_finish_kernel(const uint8_t *state, const unsigned long lo
   if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)m) - 1)) atomicAdd(n_reps, (uint32_t)__popcll(m));
 }
 
+// ---- single-linkage forest on the device (niqki_linkage) -------------------------------------------
+// The maximum spanning forest of the co-occurrence graph under the edge order of nq_linkage_key.h IS the complete
+// single-linkage hierarchy.  MST(A u B) = MST(MST(A) u B): an edge once dropped is the last of a cycle and stays
+// dropped.  So the device keeps a forest of at most n - 1 keys, and per batch of the self-join computes the forest of
+// (old forest u the batch's pairs g < t) into the other half of a double buffer, by Boruvka rounds:
+//   offer   every edge whose endpoints lie in different components offers its key to both components with a 64-bit
+//           atomic maximum on best[component].  Two launches: the old forest, one thread per edge; the hit lists, one
+//           wavefront per query t.
+//   hook    every component c with an offer takes the component at the other end of its best edge as its parent and
+//           records the edge into the new forest.  The order is strict, so the picks of a round can only cycle as a
+//           mutual pick of the SAME edge (a longer cycle would need strictly ascending keys all the way round; two
+//           components that pick each other through different edges would each hold both edges and pick the larger).
+//           In a mutual pick the smaller component id stays root and the other one records the edge: once.
+//   jump    comp[g] = the root of g's chain, best[g] = 0.
+// comp[g] names g's component by its root; between rounds every comp[g] is a root.  A round whose hook kernel found no
+// offer ends the batch: the `any` words (one per round, zeroed by the init kernel) carry that to the launches of the
+// following rounds, which return at once; the host enqueues ceil(log2 n) + 1 rounds -- the components with an offer at
+// least halve per round -- and never synchronises.
+//
+// Coherence.  The atomics on best[] execute at the memory side on the real value.  Everything else is read in a LATER
+// launch than it was written (stream order makes it visible), with three exceptions, all harmless:
+//   * the relaxed agent-scope load of best[] before an offer: best[] only grows within a round, so a stale value costs
+//     a needless atomic and never loses an offer;
+//   * the hook kernel reads comp[lo] / comp[hi] of its best edge while other threads of the same launch store new
+//     parents.  A new parent is stored with bit 31 set (ids have 23 bits), and only a ROOT x, comp[x] == x, is ever
+//     given one, so a flagged value decodes to x itself: fresh or stale, the reader gets the value of before the launch;
+//   * the jump kernel walks chains while other threads store roots.  A word holds its old value (a flagged parent, or
+//     the root of the round before, itself flagged or final) or the final root; every one of them leads to the final
+//     root of the chain, the only unflagged x with comp[x] == x on it.  These accesses are agent-scope relaxed atomics
+//     like those of the link kernel; nothing relies on their being fresh.
+
+constexpr uint32_t kHookFlag = 0x80000000u;
+// (info: [0] old forest size, [1] new forest size, [2] most rounds, [3] error; from kLinkageInfoHead on the `any` words)
+
+__device__ __forceinline__ unsigned long long best_load(const unsigned long long *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void best_offer(unsigned long long *best, uint32_t c, unsigned long long key) {
+  if (key > best_load(best + c)) __hip_atomic_fetch_max(best + c, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void linkage_init_kernel(uint32_t *comp, unsigned long long *best, uint32_t n, uint32_t *info, uint32_t rounds) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n) {
+    comp[g] = g;
+    best[g] = 0;
+  }
+  if (g == 0) info[1] = 0;
+  if (g < rounds) info[kLinkageInfoHead + g] = 0;   // (the launch has at least 256 threads)
+}
+
+// go: the `any` word of the round before (null in the first round)
+__global__ void linkage_offer_forest_kernel(const uint32_t *comp, unsigned long long *best, const unsigned long long *forest,
+                                            const uint32_t *info, uint32_t n, const uint32_t *go) {
+  if (go && !*go) return;
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= info[0] || e >= n) return;
+  const unsigned long long key = forest[e];
+  const uint32_t lo = linkage_lo(key), hi = linkage_hi(key);
+  if (lo >= n || hi >= n) return;
+  const uint32_t cl = comp[lo], ch = comp[hi];
+  if (cl == ch) return;
+  best_offer(best, cl, key);
+  best_offer(best, ch, key);
+}
+
+__global__ __launch_bounds__(kLinkBlock) void linkage_offer_hits_kernel(const uint32_t *comp, unsigned long long *best, uint32_t n,
+                                                                        const unsigned long long *hit_off, const uint32_t *hit_counts,
+                                                                        const uint32_t *hit_gids, uint32_t t0, uint32_t nq,
+                                                                        const uint32_t *go) {
+  if (go && !*go) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t q = blockIdx.x * (kLinkBlock / 64) + (threadIdx.x >> 6);   // wave-uniform
+  if (q >= nq) return;
+  const uint32_t t = t0 + q;
+  if (t >= n) return;
+  const unsigned long long lo = hit_off[q], hi = hit_off[q + 1];
+  const uint32_t ct = comp[t];
+  unsigned long long mine = 0;
+  for (unsigned long long i = lo + lane; i < hi; i += 64) {
+    // the pair (t, g) with g > t is query g's, g == t is no edge
+    const uint32_t g = hit_gids[i];
+    if (g >= t) continue;
+    const uint32_t cg = comp[g];
+    if (cg == ct) continue;
+    const unsigned long long key = linkage_pack(hit_counts[i], g, t);
+    mine = key > mine ? key : mine;
+    best_offer(best, cg, key);
+  }
+  for (int d = 32; d; d >>= 1) {
+    const unsigned long long o = (unsigned long long)__shfl_xor((long long)mine, d);
+    mine = o > mine ? o : mine;
+  }
+  if (lane == 0 && mine) best_offer(best, ct, mine);
+}
+
+// mine: the `any` word of this round
+__global__ void linkage_hook_kernel(uint32_t *comp, const unsigned long long *best, uint32_t n, unsigned long long *forest,
+                                    uint32_t *info, const uint32_t *go, uint32_t *mine) {
+  if (go && !*go) return;
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long key = 0;
+  bool hooks = false;
+  if (c < n) {
+    key = best[c];   // (nonzero only where c is a root: offers go to comp[] values)
+    if (key) {
+      const uint32_t lo = linkage_lo(key), hi = linkage_hi(key);
+      uint32_t cl = uf_load(comp + lo), ch = uf_load(comp + hi);
+      if (cl & kHookFlag) cl = lo;   // hooked in this launch: lo was its own root before it
+      if (ch & kHookFlag) ch = hi;
+      const uint32_t other = cl == c ? ch : cl;
+      hooks = !(best[other] == key && c < other);   // a mutual pick: the smaller id stays root
+      if (hooks) __hip_atomic_store(comp + c, other | kHookFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  if (__any(key != 0) && (threadIdx.x & 63u) == 0) *mine = 1;   // (every wave with an offer stores the same word)
+  // the recorded edges of a wavefront take consecutive places: one atomic a wavefront
+  const unsigned long long m = __ballot(hooks);
+  if (!m) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int leader = __ffsll((long long)m) - 1;
+  uint32_t base = 0;
+  if ((int)lane == leader) base = atomicAdd(info + 1, (uint32_t)__popcll(m));
+  base = (uint32_t)__shfl((int)base, leader);
+  if (hooks) {
+    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (at < n) forest[at] = key;
+    else info[3] = 1;   // (a forest has fewer than n edges)
+  }
+}
+
+__global__ void linkage_jump_kernel(uint32_t *comp, unsigned long long *best, uint32_t n, const uint32_t *go) {
+  if (go && !*go) return;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  best[g] = 0;
+  uint32_t r = g;
+  for (;;) {
+    const uint32_t v = uf_load(comp + r);
+    if (v == r) break;
+    r = v & ~kHookFlag;
+  }
+  if (r != g) __hip_atomic_store(comp + g, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the batch is through: the new forest becomes the old one (the host swaps the buffers), the rounds that hooked
+__global__ void linkage_end_kernel(uint32_t *info, uint32_t rounds) {
+  uint32_t r = 0;
+  for (uint32_t k = 0; k < rounds; ++k) r += info[kLinkageInfoHead + k] ? 1u : 0u;
+  if (rounds && info[kLinkageInfoHead + rounds - 1]) info[3] = 1;   // the last round still had offers
+  if (r > info[2]) info[2] = r;
+  info[0] = info[1];
+}
+
 hipError_t launch_cluster_init(uint32_t *parent, uint32_t n, hipStream_t stream) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(cluster_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, parent, n);
@@ -338,6 +495,32 @@ hipError_t launch_derep_finish(const uint8_t *state, const unsigned long long *b
   hipError_t e = hipMemsetAsync(n_reps, 0, 4, stream);
   if (e != hipSuccess || !n) return e;
   hipLaunchKernelGGL(derep_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, state, best, n, labels, label_counts, n_reps);
+  return hipGetLastError();
+}
+
+uint32_t linkage_rounds(uint32_t n) {
+  uint32_t lg = 0;
+  while ((1ull << lg) < n) lg += 1;
+  return lg + 1;
+}
+
+hipError_t launch_linkage_batch(uint32_t *comp, unsigned long long *best, const unsigned long long *forest_old,
+                                unsigned long long *forest_new, uint32_t *info, uint32_t n, const unsigned long long *hit_off,
+                                const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream) {
+  if (!n) return hipSuccess;
+  const uint32_t rounds = linkage_rounds(n), per = kLinkBlock / 64;
+  const dim3 over_n((n + 255) / 256), block(256);
+  hipLaunchKernelGGL(linkage_init_kernel, over_n, block, 0, stream, comp, best, n, info, rounds);
+  for (uint32_t r = 0; r < rounds; ++r) {
+    const uint32_t *go = r ? info + kLinkageInfoHead + r - 1 : nullptr;
+    hipLaunchKernelGGL(linkage_offer_forest_kernel, over_n, block, 0, stream, comp, best, forest_old, info, n, go);
+    if (nq)
+      hipLaunchKernelGGL(linkage_offer_hits_kernel, dim3((nq + per - 1) / per), dim3(kLinkBlock), 0, stream, comp, best, n, hit_off,
+                         hit_counts, hit_gids, t0, nq, go);
+    hipLaunchKernelGGL(linkage_hook_kernel, over_n, block, 0, stream, comp, best, n, forest_new, info, go, info + kLinkageInfoHead + r);
+    hipLaunchKernelGGL(linkage_jump_kernel, over_n, block, 0, stream, comp, best, n, go);
+  }
+  hipLaunchKernelGGL(linkage_end_kernel, dim3(1), dim3(1), 0, stream, info, rounds);
   return hipGetLastError();
 }
 

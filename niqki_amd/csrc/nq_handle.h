@@ -26,7 +26,7 @@ struct ProfSpan {
 struct SelfJoinStats {
   uint64_t splits = 0;   // batches the call had to halve
   uint64_t pairs = 0;    // the hits its kernels went through (while profiling is on)
-  uint64_t rounds = 0;   // niqki_dereplicate: most decide rounds of a batch
+  uint64_t rounds = 0;   // niqki_dereplicate: most decide rounds of a batch; niqki_linkage: most hooking rounds of a batch
   double ms[4] = {0, 0, 0, 0};
 };
 
@@ -123,7 +123,8 @@ struct niqki_index {
   uint32_t cluster_ws_mib = 1024;   // option "cluster_ws_mib": device hit buffers of a niqki_cluster batch (nq_api_selfjoin.hip)
   // the last niqki_cluster / niqki_dereplicate call (stats "cluster_*", "derep_*").  ms, while profiling is on: store
   // read, gather + hits, then link and flatten (cluster) or decide and assign (derep)
-  nqi::SelfJoinStats cluster_stats, derep_stats;
+  // niqki_linkage (stats "linkage_*"): store read, gather + hits, forest rounds, then sort + hierarchy + copies
+  nqi::SelfJoinStats cluster_stats, derep_stats, linkage_stats;
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
 

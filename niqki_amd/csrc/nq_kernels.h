@@ -287,6 +287,20 @@ hipError_t launch_derep_given(unsigned long long *best, uint32_t n, uint32_t fir
 hipError_t launch_derep_finish(const uint8_t *state, const unsigned long long *best, uint32_t n, uint32_t *labels, uint32_t *label_counts,
                                uint32_t *n_reps, hipStream_t stream);
 
+// ---- single-linkage forest (nq_cluster.hip; the edge key: nq_linkage_key.h) --------
+// One batch of the self-join: forest_new = the maximum spanning forest of forest_old (info[0] keys) and the pairs
+// (g, t0 + q), g < t0 + q, of the batch's hit lists; info[0] = its size.  comp[n], best[n] are scratch.  The caller
+// swaps the forests for the next batch.  linkage_rounds(n) = ceil(log2 n) + 1 rounds are enqueued; those after a round
+// without offers return at once.
+// info: kLinkageInfoHead + linkage_rounds(n) words, zeroed once per call.  info[0] = edges of forest_old (kept by the
+// launches themselves), info[2] = the most rounds in which a batch hooked, info[3] = nonzero: a bug;
+// info[kLinkageInfoHead + r] = nonzero: round r of this batch had offers.
+constexpr uint32_t kLinkageInfoHead = 4;
+uint32_t linkage_rounds(uint32_t n);
+hipError_t launch_linkage_batch(uint32_t *comp, unsigned long long *best, const unsigned long long *forest_old,
+                                unsigned long long *forest_new, uint32_t *info, uint32_t n, const unsigned long long *hit_off,
+                                const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream);
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

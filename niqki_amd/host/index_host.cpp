@@ -30,6 +30,7 @@
 
 #include "../csrc/nq_pack.h"
 #include "file_reader.h"
+#include "linkage_text.h"
 #include "seqio.h"
 
 namespace nqhost {
@@ -1009,10 +1010,13 @@ append_begin_fn engine_append_begin() { return (append_begin_fn)dlsym(RTLD_DEFAU
 append_slots_fn engine_append_slots() { return (append_slots_fn)dlsym(RTLD_DEFAULT, "niqki_append_slots"); }
 append_cancel_fn engine_append_cancel() { return (append_cancel_fn)dlsym(RTLD_DEFAULT, "niqki_append_cancel"); }
 retain_fn engine_retain() { return (retain_fn)dlsym(RTLD_DEFAULT, "niqki_retain"); }
+using linkage_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, int);
+linkage_fn engine_linkage() { return (linkage_fn)dlsym(RTLD_DEFAULT, "niqki_linkage"); }
 }  // namespace
 
 bool Index::has_self_join() { return engine_neighbors() != nullptr && engine_cluster() != nullptr; }
 bool Index::has_dereplication() { return engine_derep() != nullptr; }
+bool Index::has_linkage() { return engine_linkage() != nullptr; }
 bool Index::has_retain() { return engine_retain() != nullptr; }
 bool Index::has_dereplication_from() { return engine_derep_from() != nullptr; }
 bool Index::has_append() { return engine_append_begin() != nullptr && engine_append_slots() != nullptr && engine_append_cancel() != nullptr; }
@@ -1094,6 +1098,31 @@ void Index::dereplicate(const std::string &list_file, const std::string &dump_fi
   for (uint32_t g = 0; g < N; ++g) keep[g] = labels[g] == g;
   retain(keep);
   dump_index_disk(dump_file);
+}
+
+void Index::linkage_to_files(const std::string &mst_file, const std::string &linkage_file, const std::string &tree_file) {
+  const linkage_fn call = engine_linkage();
+  if (!call || grp_) throw std::runtime_error("this engine has no linkage");
+  const uint32_t N = (uint32_t)filenames.size();
+  niqki_params p{};
+  check(niqki_get_params(h_, &p), "niqki_get_params");
+  std::vector<uint32_t> into(N), count(N), lo(N), hi(N), ec(N);
+  uint32_t n_roots = 0;
+  const bool edges = !mst_file.empty();
+  check(call(h_, p.min_score, into.data(), count.data(), edges ? lo.data() : nullptr, edges ? hi.data() : nullptr,
+             edges ? ec.data() : nullptr, &n_roots, NIQKI_MEM_HOST), "niqki_linkage");
+  const auto to_file = [&](const std::string &filestr, auto &&writer) {
+    if (filestr.empty()) return;
+    ParallelTextWriter out(filestr, host_threads());
+    writer([&](const std::string &text) { out.write(text); });
+    out.close();
+  };
+  lo.resize(N - n_roots);
+  hi.resize(N - n_roots);
+  ec.resize(N - n_roots);
+  to_file(mst_file, [&](auto &&sink) { write_mst(lo, hi, ec, filenames, F, sink); });
+  to_file(linkage_file, [&](auto &&sink) { write_linkage(into, count, filenames, F, sink); });
+  to_file(tree_file, [&](auto &&sink) { write_tree(into, count, filenames, F, sink); });
 }
 
 // ---- merging dumps ------------------------------------------------------------------

@@ -95,6 +95,12 @@ class Index {
   static bool has_dereplication_from();
   void keep_novel(uint32_t first, uint32_t threshold, const std::string &list_file);
 
+  // The linkage phase (long options --mst / --linkage / --tree; single-GPU index; niqki_linkage, looked up at run time
+  // like the calls above): ONE engine call at min_score as the floor serves the three files (an empty name: not
+  // written); the texts are linkage_text.h's, gzip files like every output of the program.
+  static bool has_linkage();
+  void linkage_to_files(const std::string &mst_file, const std::string &linkage_file, const std::string &tree_file);
+
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
 

@@ -8,6 +8,8 @@
 //   --top <n>      report at most n best hits per query (-Q / -q; niqki_params.top_k), 0 = all
 //   --neighbors    the indexed genomes themselves as queries, in index order, written like -Q (niqki_neighbors_range)
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
+//   --mst <f> / --linkage <f> / --tree <f>   the complete single-linkage hierarchy down to the -J threshold from ONE
+//                  engine call (niqki_linkage): the maximum spanning forest, the merge table, Newick dendrograms
 //   --derep <f>    greedy representatives at the -J threshold, in index order, into f: representative<TAB>member
 //                  (niqki_dereplicate); the lines whose two names are equal are the dereplicated list
 //   --remove <f>   drop every indexed genome named in f (one name per line) before -D and the queries (niqki_retain)
@@ -44,7 +46,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -81,6 +83,9 @@ const Desc kDesc[] = {
     {DEREP_DUMP, "", "derep-dump", NONEMPTY, "  --derep-dump <filename>       Dereplicate at the -J threshold and dump the index of the representatives (as -D); the rest of the run is answered by that index."},
     {MERGE, "", "merge", NONEMPTY, "  --merge <filename>            Append the genomes of a dump to the index, after -L / -I / -i; may be repeated: every occurrence is taken, in order (of all other options only the last one counts)."},
     {NOVEL, "", "novel", NONEMPTY, "  --novel <filename>            After all index inputs and merges: of the genomes behind those of -L keep only the representatives at the -J threshold (the -L genomes are given); lines representative<TAB>member."},
+    {MST, "", "mst", NONEMPTY, "  --mst <filename>              Maximum spanning forest of the index down to the -J threshold: lines nameLo<TAB>nameHi<TAB>jaccard, best edge first."},
+    {LINKAGE, "", "linkage", NONEMPTY, "  --linkage <filename>          Single-linkage hierarchy down to the -J threshold: lines name<TAB>merges into<TAB>jaccard (cut it at any threshold for the --cluster groups)."},
+    {TREE, "", "tree", NONEMPTY, "  --tree <filename>             Single-linkage dendrograms down to the -J threshold in Newick, one tree per line."},
 };
 
 struct Parsed {
@@ -289,7 +294,8 @@ int main(int argc, char *argv[]) {
 
   // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts; and only a
   // single-GPU index can drop genomes or take the genomes of a dump
-  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL)) {
+  const bool linkage = o.has(MST) || o.has(LINKAGE) || o.has(TREE);
+  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL) || linkage) {
     if (n_gpus > 1) {
       cerr << "niqki: the self-join (--neighbors, --cluster, --derep), dropping genomes and merging dumps (--merge, --novel) need a single-GPU index (--gpus 1)" << endl;
       return EXIT_FAILURE;
@@ -316,6 +322,10 @@ int main(int argc, char *argv[]) {
     }
     if ((o.has(DEREP) || o.has(DEREP_DUMP)) && !nqhost::Index::has_dereplication()) {
       cerr << "niqki: this engine has no dereplication" << endl;
+      return EXIT_FAILURE;
+    }
+    if (linkage && !nqhost::Index::has_linkage()) {
+      cerr << "niqki: this engine has no linkage" << endl;
       return EXIT_FAILURE;
     }
   }
@@ -363,6 +373,13 @@ int main(int argc, char *argv[]) {
       ix->dereplicate(o.has(DEREP) ? o.last(DEREP) : string(), o.has(DEREP_DUMP) ? o.last(DEREP_DUMP) : string());
       const RunClock::tp now = system_clock::now();
       RunClock::row("| Dereplication lasted (s)          |", clk.index_end, now);
+      clk.index_end = now;
+    }
+    if (linkage) {   // ... and the linkage phase: one engine call for the three files; after --derep-dump of the dereplicated index
+      ix->linkage_to_files(o.has(MST) ? o.last(MST) : string(), o.has(LINKAGE) ? o.last(LINKAGE) : string(),
+                           o.has(TREE) ? o.last(TREE) : string());
+      const RunClock::tp now = system_clock::now();
+      RunClock::row("| Linkage lasted (s)                |", clk.index_end, now);
       clk.index_end = now;
     }
     run_matrix(*ix, o, clk);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The self-join (niqki_cluster, niqki_dereplicate) at the index shape of bench.py: 100 000 genomes, S = 15, W = 12, -J 0.1.  The index
+"""The self-join (niqki_cluster, niqki_dereplicate, niqki_linkage) at the index shape of bench.py: 100 000 genomes, S = 15, W = 12, -J 0.1.  The index
 is made of synthetic sketches (families of related genomes, made and inserted on the device, as tools/bench_topk.py
 does).  Every case runs in a child process of its own under its own time limit, one after the other; the first that
 fails ends the run.  One JSON line per case:
@@ -17,6 +17,11 @@ fails ends the run.  One JSON line per case:
               phases stand beside the link + flatten phases
   derep_path  the decide rounds' worst case: --path genomes, each linked to its two index neighbours only, inside
               one batch; microseconds per round
+  linkage, linkage_one, linkage_singletons
+              niqki_linkage(floor) on the indexes of cluster / one / singletons, floor = the cluster case's threshold,
+              and niqki_cluster(floor) on the SAME handle in the same process as the yardstick: the read and hits
+              phases are the same work, the forest + finish phases stand beside the link + flatten phases; a cut of
+              the hierarchy at the floor is compared with the cluster labels
 
     python tools/bench_selfjoin.py [--genomes 100000] [--slice 4096] [--extreme 20000] [--path 1024] [--out FILE]
 """
@@ -144,6 +149,41 @@ def case_derep(args, kind):
     return res
 
 
+def case_linkage(args, kind):
+    import numpy as np
+    import torch
+    import niqki_amd
+    e, N = make_index(args, kind)
+    thr = e.min_score if kind != "singletons" else F // 2
+    e.linkage(thr)                                     # warm-up: workspace allocations
+    t = time.time()
+    into, cnt, edges, roots = e.linkage(thr)
+    wall = time.time() - t
+    e.cluster(thr)
+    t = time.time()
+    labels, n_cl = e.cluster(thr)
+    wall_cl = time.time() - t
+    same = bool(np.array_equal(niqki_amd.cut_linkage(into, cnt, thr), labels)) and roots == n_cl
+    e.profile(True)
+    e.linkage(thr)
+    us = {k: e.stat("linkage_us_" + k) for k in ("read", "hits", "forest", "finish")}
+    pairs, rounds, splits = e.stat("linkage_pairs"), e.stat("linkage_rounds"), e.stat("linkage_splits")
+    e.cluster(thr)
+    e.profile(False)
+    cl = {k: e.stat("cluster_us_" + k) for k in ("read", "hits", "link", "flatten")}
+    res = {"case": "linkage" if kind == "families" else "linkage_" + kind, "genomes": N, "floor": int(thr),
+           "roots": roots, "clusters": n_cl, "cut_at_floor_equals_cluster": same, "wall_s": round(wall, 3),
+           "cluster_wall_s": round(wall_cl, 3), "wall_over_cluster_wall": round(wall / max(wall_cl, 1e-9), 3),
+           "phases_ms": {k: round(v / 1e3, 3) for k, v in us.items()},
+           "cluster_phases_ms": {k: round(v / 1e3, 3) for k, v in cl.items()}, "hits": pairs, "rounds": rounds,
+           "splits": splits,
+           "forest_plus_finish_over_gather_plus_hits": round((us["forest"] + us["finish"]) / max(us["hits"], 1), 4),
+           "link_plus_flatten_over_gather_plus_hits": round((cl["link"] + cl["flatten"]) / max(cl["hits"], 1), 4)}
+    e.close()
+    torch.cuda.synchronize()
+    return res
+
+
 def case_host(args):
     import numpy as np
     e, N = make_index(args, "families")
@@ -188,12 +228,15 @@ def main():
     if args.case:
         if args.case.startswith("derep"):
             res = case_derep(args, args.case[6:] or "families")
+        elif args.case.startswith("linkage"):
+            res = case_linkage(args, args.case[8:] or "families")
         else:
             res = case_host(args) if args.case == "host" else case_cluster(args, args.case)
         print(json.dumps(res), flush=True)
         return 0
     lines = []
-    for case in ("families", "host", "one", "singletons", "derep", "derep_one", "derep_singletons", "derep_path"):
+    for case in ("families", "host", "one", "singletons", "derep", "derep_one", "derep_singletons", "derep_path",
+                 "linkage", "linkage_one", "linkage_singletons"):
         if args.only and case not in args.only.split(","):
             continue
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case,
