@@ -537,6 +537,50 @@ int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, 
 int niqki_linkage(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_t *merge_count,
                   uint32_t *edge_lo, uint32_t *edge_hi, uint32_t *edge_count, uint32_t *n_roots, int mem);
 
+/* Greedy cover of a query: the non-redundant form of niqki_query's answer.  A sample that holds several genomes, or an
+ * index with many close relatives of one genome, makes niqki_query list every relative; the cover lists, pick after
+ * pick, the genome that explains the most query slots nothing picked before it explains.
+ * Let Q be a query sketch and G_g the stored sketch of genome g, as niqki_get_sketches returns it.  A cell v is valid
+ * when 0 <= v < 2^W (the rule of Index::query_sketch, src/niqki_index.cpp:639).
+ *   R_0 = {s : Q[s] valid};  total(g) = |{s in R_0 : G_g[s] == Q[s]}|, the count niqki_query reports.
+ *   Round r = 1, 2, ...:  c_r(g) = |{s in R_(r-1) : G_g[s] == Q[s]}|;  g_r = the genome with the largest c_r, among
+ *   equal counts the LARGEST id -- by definition the first hit niqki_query returns for Q with every cell outside
+ *   R_(r-1) set to -1.  The cover ends before round r when c_r(g_r) < max(min_score, 1) (the handle's min_score) or
+ *   when r > max_picks (max_picks = 0: no limit).  Otherwise pick r is (count c_r(g_r), gid g_r, total(g_r)) and
+ *   R_r = R_(r-1) minus the slots where G_(g_r) matches.
+ * Consequences: counts never increase from pick to pick; no genome is picked twice; the counts of a query's picks sum
+ * to at most |R_0|; a query has at most min(N, |R_0| / max(min_score, 1)) picks.  The result is a function of the
+ * index, Q, min_score and max_picks only: batch sizes, options, tile count, a delta segment and the handle's top_k
+ * (ignored here) do not change it.  min_score and top_k are the handle's own again when the call returns, also when
+ * it fails.
+ * Outputs as niqki_query's: hit_off holds nq + 1 offsets, a query's picks appear in pick order in hit_counts (the
+ * slots the pick newly explains), hit_gids and hit_totals (total(g); may be NULL).  In BOTH memory spaces a total
+ * above `capacity` returns NIQKI_E_CAPACITY with the true total in hit_off[nq] and nothing written to the other
+ * arrays; capacity = nq x max_picks never fails when max_picks > 0.  NIQKI_MEM_HOST works in batches of option
+ * "query_batch"; NIQKI_MEM_DEVICE takes the nq sketches as one batch and writes in stream order.
+ * niqki_staged_cover works on the sketches of the staged batch (niqki_stage_raw) and leaves it usable: a
+ * niqki_staged_query after it answers as if it had not run.
+ * Handles: whole-range, single-GPU, resident handles; any tile count, hit lists or counter rows, with or without a
+ * delta segment, S <= 16.  A slot-range shard gets NIQKI_E_STATE, and so does a paged handle (resident_bytes /
+ * resident_mib; niqki_last_error says so): its store is host memory, and a column read per pick across the bus is not
+ * a form worth having -- refused, never answered differently.  Groups have no cover.  No genomes, nq = 0 or a sketch
+ * without a valid cell: NIQKI_OK and no picks.
+ * How: per batch the device keeps the sketches as given, a working copy and the list of active queries.  A round runs
+ * the query path itself (threshold max(min_score, 1), top_k = 1) on the active queries' working rows, so every count
+ * and every tie is niqki_query's; then one workgroup per active query walks the winner's column of the sketch store,
+ * counts total against the sketch as given, sets the matching cells of the working row to -1 and logs the pick; the
+ * rows of the queries that go on are moved together, in query order, so later rounds cost less.  The host reads the
+ * active count back once per round -- the round's only synchronisation -- and ends the call with NIQKI_E_STATE (never
+ * a spin) if a pick masked no cell or the rounds pass min(N, F / max(min_score, 1), max_picks if nonzero) + 1.
+ * niqki_get_stat, the last call: "cover_rounds" (the most rounds a batch ran), "cover_picks",
+ * "cover_recount_mismatches" (the sum over picks of |cells masked - count reported|: 0 unless there is a bug); while
+ * profiling is on: "cover_us_hits", "cover_us_pick", "cover_us_compact", "cover_us_finish" (microseconds).
+ * DESIGN.md 4.5c. */
+int niqki_cover(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint32_t max_picks, uint64_t *hit_off,
+                uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
+int niqki_staged_cover(niqki_index *ix, uint32_t max_picks, uint64_t *hit_off, uint32_t *hit_counts,
+                       uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
+
 /* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
  * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
  * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses

@@ -120,6 +120,8 @@ ABI = [
     ("niqki_dereplicate", _int, [_vp, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_dereplicate_from", _int, [_vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_linkage", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32), _int]),
+    ("niqki_cover", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_staged_cover", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
@@ -605,6 +607,34 @@ class Engine:
         n_edges = n_g - int(n.value)
         return into, cnt, (tuple(a[:n_edges].copy() for a in e3) if edges else None), int(n.value)
 
+    def _cover(self, call, nq, capacity, totals):
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        while True:
+            hc, hg, ht = (np.empty(max(capacity, 1), dtype=np.uint32) for _ in range(3))
+            rc = call(off, hc, hg, ht if totals else None, capacity)
+            self._ck(rc, allow=(E_CAPACITY,))
+            if rc == 0:
+                tot = int(off[nq])
+                return (off, hc[:tot], hg[:tot], ht[:tot]) if totals else (off, hc[:tot], hg[:tot])
+            capacity = int(off[nq])
+
+    def cover(self, sketches, max_picks=0, capacity=None, totals=False):
+        """niqki_cover: the greedy cover of each query sketch, (off, counts, gids[, totals]) shaped like query's
+        result.  A query's picks are in pick order; counts = the slots a pick newly explains, totals = the genome's
+        plain count.  max_picks = 0: no limit."""
+        sk = np.ascontiguousarray(sketches, dtype=np.int32).reshape(-1, self.F)
+        nq = sk.shape[0]
+        cap = capacity if capacity is not None else (nq * max_picks if max_picks else max(1024, nq * 8))
+        return self._cover(lambda off, hc, hg, ht, c: self.L.niqki_cover(
+            self.h, _p(sk), nq, int(max_picks), _p(off), _p(hc), _p(hg), _p(ht), c, MEM_HOST), nq, cap, totals)
+
+    def staged_cover(self, max_picks=0, capacity=None, totals=False):
+        """niqki_staged_cover: cover of the staged batch's sketches; the staged batch stays usable."""
+        nq = self._staged.n_entry
+        cap = capacity if capacity is not None else (nq * max_picks if max_picks else max(1024, nq * 8))
+        return self._cover(lambda off, hc, hg, ht, c: self.L.niqki_staged_cover(
+            self.h, int(max_picks), _p(off), _p(hc), _p(hg), _p(ht), c, MEM_HOST), nq, cap, totals)
+
     def retain(self, keep):
         """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),
         new_ids[g] = the new id of old genome g (the kept genomes below it), 0xFFFFFFFF for a dropped one.  The handle
@@ -754,6 +784,12 @@ class Engine:
     def query_dev(self, sketches, nq, hit_off, hc, hg, capacity):
         self._ck(self.L.niqki_query(self.h, _p(sketches), nq, _p(hit_off), _p(hc), _p(hg), capacity,
                                     MEM_DEVICE))
+
+    def cover_dev(self, sketches, nq, max_picks, hit_off, hc, hg, ht, capacity):
+        """niqki_cover on device arrays (ht may be None); returns the status: 0, or E_CAPACITY with the true total in
+        hit_off[nq] and nothing else written."""
+        return self._ck(self.L.niqki_cover(self.h, _p(sketches), nq, int(max_picks), _p(hit_off), _p(hc), _p(hg), _p(ht),
+                                           capacity, MEM_DEVICE), allow=(E_CAPACITY,))
 
     def query_sequences_dev(self, seqs, rec_off, n, hit_off, hc, hg, capacity):
         self._ck(self.L.niqki_query_sequences(self.h, _p(seqs), _p(rec_off), n, None, n, _p(hit_off),

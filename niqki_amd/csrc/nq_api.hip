@@ -380,7 +380,8 @@ void niqki_destroy(niqki_index *ix) {
   for (Buf *b : {&ix->ws_seq, &ix->ws_recoff, &ix->ws_entry, &ix->ws_sk, &ix->ws_counts, &ix->ws_blk,
                  &ix->ws_hitoff, &ix->ws_hc, &ix->ws_hg, &ix->ws_tc, &ix->ws_tg, &ix->ws_misc, &ix->ws_stash,
                  &ix->ws_raw, &ix->ws_wire[0], &ix->ws_wire[1], &ix->ws_redo[0], &ix->ws_redo[1], &ix->ws_fmeta, &ix->ws_summ, &ix->ws_chunk, &ix->ws_fkept, &ix->ws_fnrec,
-                 &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab})
+                 &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
+                 &ix->ws_cv_orig, &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -582,6 +583,14 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "linkage_us_forest")) { *value = (uint64_t)(ix->linkage_stats.ms[2] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "linkage_us_finish")) { *value = (uint64_t)(ix->linkage_stats.ms[3] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "linkage_pairs")) { *value = ix->linkage_stats.pairs; return NIQKI_OK; }
+  // the last niqki_cover / niqki_staged_cover call; the phases while profiling was on
+  if (!std::strcmp(key, "cover_rounds")) { *value = ix->cover_stats.rounds; return NIQKI_OK; }
+  if (!std::strcmp(key, "cover_picks")) { *value = ix->cover_stats.picks; return NIQKI_OK; }
+  if (!std::strcmp(key, "cover_recount_mismatches")) { *value = ix->cover_stats.mismatches; return NIQKI_OK; }
+  if (!std::strcmp(key, "cover_us_hits")) { *value = (uint64_t)(ix->cover_stats.ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cover_us_pick")) { *value = (uint64_t)(ix->cover_stats.ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cover_us_compact")) { *value = (uint64_t)(ix->cover_stats.ms[2] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "cover_us_finish")) { *value = (uint64_t)(ix->cover_stats.ms[3] * 1000.0); return NIQKI_OK; }
   // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
   if (!std::strcmp(key, "retain_us_rank")) { *value = (uint64_t)(ix->retain_ms[0] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "retain_us_compact")) { *value = (uint64_t)(ix->retain_ms[1] * 1000.0); return NIQKI_OK; }

@@ -30,6 +30,14 @@ struct SelfJoinStats {
   double ms[4] = {0, 0, 0, 0};
 };
 
+// what niqki_get_stat reports of the last niqki_cover / niqki_staged_cover call (nq_api_cover.hip)
+struct CoverStats {
+  uint64_t rounds = 0;       // the most rounds a batch ran
+  uint64_t picks = 0;
+  uint64_t mismatches = 0;   // cells masked against counts reported, summed: 0 unless there is a bug
+  double ms[4] = {0, 0, 0, 0};   // while profiling is on: hits, pick, compact, finish
+};
+
 void shared_free(struct ::niqki_index *ix);   // nq_shared.hip
 
 }  // namespace nqi
@@ -125,6 +133,10 @@ struct niqki_index {
   // read, gather + hits, then link and flatten (cluster) or decide and assign (derep)
   // niqki_linkage (stats "linkage_*"): store read, gather + hits, forest rounds, then sort + hierarchy + copies
   nqi::SelfJoinStats cluster_stats, derep_stats, linkage_stats;
+  nqi::CoverStats cover_stats;
+  // niqki_cover: the batch's sketches as given (host calls), two buffers of masked rows with their query numbers, the
+  // per-row and per-query words, the pick log, a batch's picks on their way to the host
+  nqi::Buf ws_cv_orig, ws_cv_sk[2], ws_cv_idx, ws_cv_log, ws_cv_out;
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
 
@@ -248,6 +260,10 @@ SketchSource stored_rows(niqki_index *ix, uint32_t begin);             // genome
 uint32_t query_rows_per_batch(const niqki_index *ix);   // option "query_batch", or more where no counter rows are written
 int query_to_host(niqki_index *ix, const SketchSource &src, uint32_t nq, uint32_t qb, uint64_t *hit_off, uint32_t *hit_counts,
                   uint32_t *hit_gids, uint64_t capacity);
+// ---- nq_api_cover.hip ----
+// the greedy cover of nq device-resident whole sketches (niqki_hip.h); the outputs in host or device memory
+int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint32_t max_picks, uint64_t *hit_off,
+              uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);

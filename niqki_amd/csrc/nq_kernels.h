@@ -301,6 +301,45 @@ hipError_t launch_linkage_batch(uint32_t *comp, unsigned long long *best, const 
                                 unsigned long long *forest_new, uint32_t *info, uint32_t n, const unsigned long long *hit_off,
                                 const uint32_t *hit_counts, const uint32_t *hit_gids, uint32_t t0, uint32_t nq, hipStream_t stream);
 
+// ---- greedy cover of a query (nq_cover.hip; the rounds: nq_api_cover.hip) -----------
+// One entry of the pick log: a round writes one per active row, in row order.  pos = the pick's place in its query's
+// list, kCoverNoPick for a query that had no hit in the round (it leaves the active set).
+constexpr uint32_t kCoverNoPick = 0xFFFFFFFFu;
+struct CoverPick {
+  uint32_t q, pos, count, gid, total;
+};
+// info words of a batch (zeroed per batch, kCoverInfoActive and kCoverInfoPicks rewritten per round)
+enum : uint32_t { kCoverInfoActive = 0, kCoverInfoPicks = 1, kCoverInfoStuck = 2, kCoverInfoMismatch = 3, kCoverInfoWords = 4 };
+struct CoverPickArgs {
+  const unsigned long long *hit_off;   // n_active + 1: the round's hits at top_k = 1, at most one a row
+  const uint32_t *hit_counts, *hit_gids;
+  const uint32_t *qidx;                // n_active: the batch's query each row belongs to
+  const int32_t *orig;                 // the batch's sketches as given, F apart
+  int32_t *masked;                     // n_active working rows, F apart
+  const uint16_t *store;               // slot-major u16 store of a whole-range handle: store[s * cap + g]
+  uint64_t cap;
+  uint32_t n_genomes, F, R, max_picks;
+  uint32_t *n_picks;                   // per query of the batch
+  uint32_t *flag;                      // n_active: out, the row goes on
+  CoverPick *log;                      // n_active entries of this round
+  uint32_t *info;                      // kCoverInfoWords
+};
+hipError_t launch_cover_init(uint32_t *qidx, uint32_t *n_picks, uint32_t n, hipStream_t stream);   // qidx[i] = i, n_picks[i] = 0
+// Every row with a hit: total = its winner's matches against the original row, the matching cells of the masked row
+// become -1; info[kCoverInfoMismatch] += |cells masked - count|, info[kCoverInfoStuck] += 1 where none was masked or
+// the winner lies outside the index, info[kCoverInfoPicks] += 1.  One workgroup per row; right for any F >= 1.
+hipError_t launch_cover_pick(const CoverPickArgs &a, uint32_t n_active, hipStream_t stream);
+// pos[i] = the number of flagged rows before row i, info[kCoverInfoActive] = the number of flagged rows (pos: n + 1 words)
+hipError_t launch_cover_compact_scan(const uint32_t *flag, uint32_t n_active, uint32_t *pos, uint32_t *info, hipStream_t stream);
+// the flagged rows of src / qidx_src, in order, to the front of dst / qidx_dst
+hipError_t launch_cover_compact(const uint32_t *flag, const uint32_t *pos, const int32_t *src, const uint32_t *qidx_src, int32_t *dst,
+                                uint32_t *qidx_dst, uint32_t F, uint32_t n_active, hipStream_t stream);
+// hit_off[0 .. n] = exclusive scan of n_picks
+hipError_t launch_cover_finish(const uint32_t *n_picks, uint32_t n, unsigned long long *hit_off, hipStream_t stream);
+// every pick of the log to place hit_off[q] + pos of the output arrays (hit_totals may be null)
+hipError_t launch_cover_scatter(const CoverPick *log, uint64_t n_log, const unsigned long long *hit_off, uint32_t *hit_counts,
+                                uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, hipStream_t stream);
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

@@ -390,10 +390,32 @@ void Index::group_query_staged(uint32_t per, const std::vector<uint32_t> &n_entr
     }
 }
 
+namespace {
+using cover_fn = int (*)(niqki_index *, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint32_t *, uint64_t, int);
+cover_fn engine_cover() { return (cover_fn)dlsym(RTLD_DEFAULT, "niqki_staged_cover"); }
+}  // namespace
+
+bool Index::has_cover() { return engine_cover() != nullptr; }
+
 // hits of the staged entries, written in entry order
 // hits of the staged entries
 void Index::query_staged(size_t n, Hits &h) {
   const uint64_t N = niqki_genome_count(h_);
+  if (cover) {   // --cover: each entry's greedy cover in the place of its hits, at most top_k picks (n x k never overflows)
+    const cover_fn call = engine_cover();
+    if (!call) throw std::runtime_error("this engine has no cover");
+    uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1) : std::max<uint64_t>(uint64_t(1) << 16, n * 8);
+    h.off.resize(n + 1);
+    for (;;) {
+      h.hc.resize(cap);
+      h.hg.resize(cap);
+      const int rc = call(h_, top_k, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST);
+      if (rc == NIQKI_E_CAPACITY && cap < n * N) { cap = std::max(h.off[n], cap * 2); continue; }
+      check(rc, "niqki_staged_cover");
+      break;
+    }
+    return;
+  }
   // top-k: at most n x k hits, never NIQKI_E_CAPACITY
   uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1)
                        : std::max<uint64_t>(uint64_t(1) << 20, n * 64);

@@ -101,6 +101,12 @@ class Index {
   static bool has_linkage();
   void linkage_to_files(const std::string &mst_file, const std::string &linkage_file, const std::string &tree_file);
 
+  // The greedy cover (long option --cover; single-GPU resident index; niqki_staged_cover, looked up at run time like
+  // the calls above).  With `cover` set the list of every -Q / -l query is its cover instead of its hits: per pick the
+  // genome and the slots it newly explains, at most top_k picks where top_k > 0; --neighbors and -M are not affected.
+  static bool has_cover();
+  bool cover = false;
+
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
 

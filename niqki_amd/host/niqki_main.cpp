@@ -7,6 +7,8 @@
 //   --resident-mib <n>  paged index: sketch store in host memory, n MiB of device memory for one page of slots
 //   --top <n>      report at most n best hits per query (-Q / -q; niqki_params.top_k), 0 = all
 //   --neighbors    the indexed genomes themselves as queries, in index order, written like -Q (niqki_neighbors_range)
+//   --cover        the list of every -Q / -q query is its greedy cover (niqki_staged_cover): the genome that explains
+//                  the most query slots, then the one that explains the most of the rest, ...; --top bounds the picks
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
 //   --mst <f> / --linkage <f> / --tree <f>   the complete single-linkage hierarchy down to the -J threshold from ONE
 //                  engine call (niqki_linkage): the maximum spanning forest, the merge table, Newick dendrograms
@@ -46,7 +48,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -86,6 +88,7 @@ const Desc kDesc[] = {
     {MST, "", "mst", NONEMPTY, "  --mst <filename>              Maximum spanning forest of the index down to the -J threshold: lines nameLo<TAB>nameHi<TAB>jaccard, best edge first."},
     {LINKAGE, "", "linkage", NONEMPTY, "  --linkage <filename>          Single-linkage hierarchy down to the -J threshold: lines name<TAB>merges into<TAB>jaccard (cut it at any threshold for the --cluster groups)."},
     {TREE, "", "tree", NONEMPTY, "  --tree <filename>             Single-linkage dendrograms down to the -J threshold in Newick, one tree per line."},
+    {COVER, "", "cover", NONE, "  --cover                       Report each -Q / -q query's greedy cover instead of all its hits: per genome the slots no earlier line explains (--top bounds the picks)."},
 };
 
 struct Parsed {
@@ -330,6 +333,22 @@ int main(int argc, char *argv[]) {
     }
   }
 
+  // the cover reads whole counts and the winner's column of a device-resident sketch store
+  if (o.has(COVER)) {
+    if (n_gpus > 1) {
+      cerr << "niqki: --cover needs a single-GPU index (--gpus 1)" << endl;
+      return EXIT_FAILURE;
+    }
+    if (resident_mib > 0) {
+      cerr << "niqki: --cover needs a resident index (--resident-mib 0): a paged index keeps its sketch store in host memory" << endl;
+      return EXIT_FAILURE;
+    }
+    if (!nqhost::Index::has_cover()) {
+      cerr << "niqki: this engine has no cover" << endl;
+      return EXIT_FAILURE;
+    }
+  }
+
   const char *rule = "+-----------------------------------+-------------------------------+";
   cout << "+-------------------------------------------------------------------+" << endl
        << "|                            Informations                           |" << endl
@@ -338,6 +357,7 @@ int main(int argc, char *argv[]) {
   try {
     if (o.has(LOAD)) ix.reset(new nqhost::Index(o.last(LOAD), true, out_file, device, n_gpus, resident_mib, top_k));
     else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib, top_k));
+    ix->cover = o.has(COVER);
     if (const unsigned expect = (unsigned)int_opt(o, GENOME_SIZE, 0)) ix->select_best_H(expect);   // src/niqki.cpp:303-305
 
     const uint32_t n_loaded = (uint32_t)ix->getNbGenomes();   // --novel: the genomes of -L are given (none without -L)
