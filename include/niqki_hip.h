@@ -581,6 +581,59 @@ int niqki_cover(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint32_t 
 int niqki_staged_cover(niqki_index *ix, uint32_t max_picks, uint64_t *hit_off, uint32_t *hit_counts,
                        uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
 
+/* Collapsed hits: per query the best hit of every LABEL.  A collection with a species label per genome (from a
+ * taxonomy table, or the labels niqki_cluster / niqki_dereplicate return) answers "which species, and how close is its
+ * best member" without the full lists (nq x relatives entries) ever leaving the device.
+ * niqki_set_labels gives every indexed genome g a label[g], any uint32_t: values are arbitrary and need not be dense, 0
+ * and 0xFFFFFFFF are ordinary labels.  n must equal niqki_genome_count (else NIQKI_E_INVALID, the labelling the handle
+ * had stays); labels == NULL or n == 0 removes the labelling.  mem as in niqki_cluster: a device array is taken in
+ * stream order; the call may synchronise once.  The call prepares what the kernel needs -- dense label ids, a rank
+ * among the distinct values -- and stat "labels" = the number of distinct labels (0 when none is set); this is one-off
+ * work and runs on the host.  The labelling belongs to a genome set: every call that adds or drops genomes removes it
+ * (niqki_insert, niqki_insert_shared, niqki_staged_insert of at least one genome; a committed niqki_append_*;
+ * niqki_retain, whatever its flags).  Without a labelling the collapsed calls return NIQKI_E_STATE and
+ * niqki_last_error says to set labels again.  Plain queries and every other call never look at the labelling.
+ * Definition.  For a query sketch Q let H(Q) be the list niqki_query returns for Q with top_k = 0 at the handle's
+ * min_score: ordered by count descending, then gid descending (min_score 0: every genome is a hit).  The collapsed
+ * list of Q is the subsequence of H(Q) made of the entries that are the first of their label in H(Q), in H(Q)'s order.
+ * Each carries count and gid of that entry (the label's best member, ties to the larger gid because that is H's order)
+ * and members, the number of entries of H(Q) with that label; members never depends on top_k.  With the handle's
+ * top_k = k > 0 the result is the first min(k, n) entries of the collapsed list: top_k bounds LABELS.
+ * Consequences: every genome its own label gives H(Q) itself, with members 1; one label for all gives at most one
+ * entry per query, with members = |H(Q)|; a query's members sum to |H(Q)| when top_k = 0.  The result is a function
+ * of the index, the labels, Q, min_score and top_k only: batch size, options, tile count, paging, a delta segment and
+ * the hit-list versus counter-row form do not change it.  The handle's min_score and top_k are its own again when the
+ * call returns, also when it fails.
+ * Outputs as niqki_cover's: hit_off holds nq + 1 offsets; hit_counts, hit_gids and hit_members (may be NULL) hold the
+ * entries in list order.  In BOTH memory spaces a total above `capacity` returns NIQKI_E_CAPACITY with the true total
+ * in hit_off[nq] and nothing written to the other arrays; capacity = nq x min(top_k or "labels", "labels") never
+ * fails.  NIQKI_MEM_HOST works in batches of option "query_batch"; NIQKI_MEM_DEVICE takes the nq sketches in one call
+ * and writes in stream order.  niqki_staged_query_collapsed works on the staged batch (niqki_stage_raw) and leaves it
+ * usable: a niqki_staged_query after it answers as if it had not run.
+ * Handles: whole-range single-GPU handles, resident or paged, any tile count, hit lists or counter rows, with or
+ * without a delta segment, S <= 16 (at S = 16 counts reach 65 536; the outputs are u32).  A slot-range shard gets
+ * NIQKI_E_STATE.  Out of scope: multi-GPU groups, the _shared calls and the _ahead calls have no collapsed form.  No
+ * genomes, nq = 0 or a query without a hit: NIQKI_OK and empty lists (no genomes: also without a labelling, which an
+ * empty index cannot have).
+ * How: per batch the query path itself runs at top_k = 0 into the handle's device hit buffers, whose budget is option
+ * "cluster_ws_mib" with the halving rule of niqki_cluster (a batch whose full lists do not fit is split in halves,
+ * down to one query, whose list always fits; stat "collapse_splits").  collapse_first_kernel then takes a query per
+ * workgroup: a list of at most L entries (option "collapse_lds_cap", 1..4096, default 1024: a 24 KiB table, six
+ * workgroups a compute unit) goes through an open-addressing table in LDS keyed by the dense label id -- per entry an
+ * atomic minimum on the label's first position and an atomic add on its member count, at least 2 L slots, linear
+ * probing bounded by the table size -- and a longer list through a direct-indexed table in global memory, one per
+ * resident workgroup (labels x 8 bytes each, as many as a quarter of the budget holds, 1 .. 1024), which is cleared by
+ * walking the list again; stat "collapse_long_lists" counts the queries of the last call on that route.  An entry is
+ * kept iff its position is its label's first; a scan of the kept counts, cut to top_k, and a scatter in list order
+ * finish the batch.  Nothing is sorted, nothing spins, and the kept total is read back once per batch (4 more bytes a
+ * hit than the hit buffers for the flags).  While profiling is on: "collapse_us_hits", "collapse_us_first",
+ * "collapse_us_emit" (microseconds, the last call).  DESIGN.md 4.5d. */
+int niqki_set_labels(niqki_index *ix, const uint32_t *labels, uint32_t n, int mem);
+int niqki_query_collapsed(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint64_t *hit_off,
+                          uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_members, uint64_t capacity, int mem);
+int niqki_staged_query_collapsed(niqki_index *ix, uint64_t *hit_off, uint32_t *hit_counts, uint32_t *hit_gids,
+                                 uint32_t *hit_members, uint64_t capacity, int mem);
+
 /* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
  * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
  * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses

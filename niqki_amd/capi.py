@@ -122,6 +122,9 @@ ABI = [
     ("niqki_linkage", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_cover", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_staged_cover", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_set_labels", _int, [_vp, _vp, _u32, _int]),
+    ("niqki_query_collapsed", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_staged_query_collapsed", _int, [_vp, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
@@ -635,6 +638,37 @@ class Engine:
         return self._cover(lambda off, hc, hg, ht, c: self.L.niqki_staged_cover(
             self.h, int(max_picks), _p(off), _p(hc), _p(hg), _p(ht), c, MEM_HOST), nq, cap, totals)
 
+    def set_labels(self, labels):
+        """niqki_set_labels: a uint32 label per indexed genome (a numpy array, or a device tensor of dtype int32 /
+        uint32 holding the same bits), None to remove the labelling.  Labels need not be dense; the labelling lasts
+        until genomes are added or dropped."""
+        if labels is None:
+            self._ck(self.L.niqki_set_labels(self.h, None, 0, MEM_HOST))
+        elif hasattr(labels, "data_ptr"):
+            if labels.element_size() != 4 or not labels.is_contiguous():
+                raise ValueError("set_labels: a device tensor must be contiguous and hold 32-bit labels")
+            self._ck(self.L.niqki_set_labels(self.h, _p(labels), int(labels.numel()), MEM_DEVICE))
+        else:
+            lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+            self._ck(self.L.niqki_set_labels(self.h, _p(lab) if lab.size else None, lab.size, MEM_HOST))
+
+    def query_collapsed(self, sketches, capacity=None, members=False):
+        """niqki_query_collapsed: per query the best hit of every label, (off, counts, gids[, members]) shaped like
+        query's result.  A query's entries are the first of their label in its full ordered hit list, in that order;
+        members = the label's entries in the full list.  The handle's top_k bounds the labels."""
+        sk = np.ascontiguousarray(sketches, dtype=np.int32).reshape(-1, self.F)
+        nq = sk.shape[0]
+        cap = capacity if capacity is not None else max(1024, nq * 8)
+        return self._cover(lambda off, hc, hg, hm, c: self.L.niqki_query_collapsed(
+            self.h, _p(sk), nq, _p(off), _p(hc), _p(hg), _p(hm), c, MEM_HOST), nq, cap, members)
+
+    def staged_query_collapsed(self, capacity=None, members=False):
+        """niqki_staged_query_collapsed: query_collapsed of the staged batch's sketches; the staged batch stays usable."""
+        nq = self._staged.n_entry
+        cap = capacity if capacity is not None else max(1024, nq * 8)
+        return self._cover(lambda off, hc, hg, hm, c: self.L.niqki_staged_query_collapsed(
+            self.h, _p(off), _p(hc), _p(hg), _p(hm), c, MEM_HOST), nq, cap, members)
+
     def retain(self, keep):
         """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),
         new_ids[g] = the new id of old genome g (the kept genomes below it), 0xFFFFFFFF for a dropped one.  The handle
@@ -790,6 +824,12 @@ class Engine:
         hit_off[nq] and nothing else written."""
         return self._ck(self.L.niqki_cover(self.h, _p(sketches), nq, int(max_picks), _p(hit_off), _p(hc), _p(hg), _p(ht),
                                            capacity, MEM_DEVICE), allow=(E_CAPACITY,))
+
+    def query_collapsed_dev(self, sketches, nq, hit_off, hc, hg, hm, capacity):
+        """niqki_query_collapsed on device arrays (hm may be None); returns the status: 0, or E_CAPACITY with the true
+        total in hit_off[nq] and nothing else written."""
+        return self._ck(self.L.niqki_query_collapsed(self.h, _p(sketches), nq, _p(hit_off), _p(hc), _p(hg), _p(hm),
+                                                     capacity, MEM_DEVICE), allow=(E_CAPACITY,))
 
     def query_sequences_dev(self, seqs, rec_off, n, hit_off, hc, hg, capacity):
         self._ck(self.L.niqki_query_sequences(self.h, _p(seqs), _p(rec_off), n, None, n, _p(hit_off),

@@ -381,7 +381,8 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_hitoff, &ix->ws_hc, &ix->ws_hg, &ix->ws_tc, &ix->ws_tg, &ix->ws_misc, &ix->ws_stash,
                  &ix->ws_raw, &ix->ws_wire[0], &ix->ws_wire[1], &ix->ws_redo[0], &ix->ws_redo[1], &ix->ws_fmeta, &ix->ws_summ, &ix->ws_chunk, &ix->ws_fkept, &ix->ws_fnrec,
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
-                 &ix->ws_cv_orig, &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out})
+                 &ix->ws_cv_orig, &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
+                 &ix->lab_dense, &ix->ws_cl_sk, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -473,6 +474,11 @@ int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
   if (!std::strcmp(key, "cluster_ws_mib")) {
     if (value < 1 || value > (1 << 20)) return fail(ix, NIQKI_E_INVALID, "cluster_ws_mib must be in 1..1048576");
     ix->cluster_ws_mib = (uint32_t)value;
+    return NIQKI_OK;
+  }
+  if (!std::strcmp(key, "collapse_lds_cap")) {
+    if (value < 1 || value > (int64_t)nq::kCollapseMaxLdsCap) return fail(ix, NIQKI_E_INVALID, "collapse_lds_cap must be in 1..4096");
+    ix->collapse_lds_cap = (uint32_t)value;
     return NIQKI_OK;
   }
   if (!std::strcmp(key, "query_batch")) { if (value < 1) return NIQKI_E_INVALID; ix->query_batch = (uint32_t)value; return NIQKI_OK; }
@@ -591,6 +597,13 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "cover_us_pick")) { *value = (uint64_t)(ix->cover_stats.ms[1] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "cover_us_compact")) { *value = (uint64_t)(ix->cover_stats.ms[2] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "cover_us_finish")) { *value = (uint64_t)(ix->cover_stats.ms[3] * 1000.0); return NIQKI_OK; }
+  // niqki_set_labels; the last niqki_query_collapsed / niqki_staged_query_collapsed call; its phases while profiling was on
+  if (!std::strcmp(key, "labels")) { *value = ix->labels_set ? ix->n_labels : 0; return NIQKI_OK; }
+  if (!std::strcmp(key, "collapse_splits")) { *value = ix->collapse_stats.splits; return NIQKI_OK; }
+  if (!std::strcmp(key, "collapse_long_lists")) { *value = ix->collapse_stats.long_lists; return NIQKI_OK; }
+  if (!std::strcmp(key, "collapse_us_hits")) { *value = (uint64_t)(ix->collapse_stats.ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "collapse_us_first")) { *value = (uint64_t)(ix->collapse_stats.ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "collapse_us_emit")) { *value = (uint64_t)(ix->collapse_stats.ms[2] * 1000.0); return NIQKI_OK; }
   // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
   if (!std::strcmp(key, "retain_us_rank")) { *value = (uint64_t)(ix->retain_ms[0] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "retain_us_compact")) { *value = (uint64_t)(ix->retain_ms[1] * 1000.0); return NIQKI_OK; }

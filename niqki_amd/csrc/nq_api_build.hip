@@ -171,6 +171,7 @@ int insert_dev(niqki_index *ix, const int32_t *sketches, uint32_t sk_stride, uin
   if ((uint64_t)ix->n_genomes + n > 0xFFFFFFFFull) return fail(ix, NIQKI_E_INVALID, "too many genomes");
   int rc = reserve_store(ix, (uint64_t)ix->n_genomes + n);
   if (rc) return rc;
+  drop_labels(ix);   // (niqki_set_labels: a labelling belongs to a genome set)
   if (ix->resident_bytes) {
     // paged: transpose into a device staging block of all the handle's slots, then rows to the host store
     const uint32_t f_all = ix->full_end - ix->full_begin;

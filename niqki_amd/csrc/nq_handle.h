@@ -38,6 +38,13 @@ struct CoverStats {
   double ms[4] = {0, 0, 0, 0};   // while profiling is on: hits, pick, compact, finish
 };
 
+// what niqki_get_stat reports of the last niqki_query_collapsed / niqki_staged_query_collapsed call (nq_api_collapse.hip)
+struct CollapseStats {
+  uint64_t splits = 0;       // batches the call had to halve
+  uint64_t long_lists = 0;   // queries whose list took the global-table route
+  double ms[3] = {0, 0, 0};  // while profiling is on: hits, first, emit
+};
+
 void shared_free(struct ::niqki_index *ix);   // nq_shared.hip
 
 }  // namespace nqi
@@ -137,6 +144,17 @@ struct niqki_index {
   // niqki_cover: the batch's sketches as given (host calls), two buffers of masked rows with their query numbers, the
   // per-row and per-query words, the pick log, a batch's picks on their way to the host
   nqi::Buf ws_cv_orig, ws_cv_sk[2], ws_cv_idx, ws_cv_log, ws_cv_out;
+  // niqki_set_labels: the genomes' labels as dense ids (device, n_genomes words) and how many there are; every call that
+  // changes the genome set drops them (drop_labels)
+  nqi::Buf lab_dense;
+  uint32_t n_labels = 0;
+  bool labels_set = false;
+  uint32_t collapse_lds_cap = 1024;   // option "collapse_lds_cap": the longest list the LDS table of collapse_first_kernel takes
+  nqi::CollapseStats collapse_stats;
+  // niqki_query_collapsed: a host call's sketches, a flag word per hit, the kept counts per query, a leaf's offsets and
+  // info words, the global tables, a batch's collapsed entries, its offsets on their way to the host
+  nqi::Buf ws_cl_sk, ws_cl_keep, ws_cl_nk, ws_cl_off, ws_cl_tab, ws_cl_stage;
+  bool cl_tab_clean = false;   // every entry of ws_cl_tab is cleared (false after growth and while a call is under way)
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
 
@@ -264,6 +282,8 @@ int query_to_host(niqki_index *ix, const SketchSource &src, uint32_t nq, uint32_
 // the greedy cover of nq device-resident whole sketches (niqki_hip.h); the outputs in host or device memory
 int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint32_t max_picks, uint64_t *hit_off,
               uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
+// ---- nq_api_collapse.hip ----
+void drop_labels(niqki_index *ix);   // the genome set changes: the labelling of niqki_set_labels goes
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);

@@ -340,6 +340,39 @@ hipError_t launch_cover_finish(const uint32_t *n_picks, uint32_t n, unsigned lon
 hipError_t launch_cover_scatter(const CoverPick *log, uint64_t n_log, const unsigned long long *hit_off, uint32_t *hit_counts,
                                 uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, hipStream_t stream);
 
+// ---- collapsed hits: the best hit per label (nq_collapse.hip; the batches: nq_api_collapse.hip) -----------
+// One entry of a collapsed list on its way out: the label's best member and how many members the full list holds.
+struct CollapsedHit {
+  uint32_t count, gid, members;
+};
+// info words of a batch: queries that took the global-table route; entries no table could take (a bug: the host ends the call)
+enum : uint32_t { kCollapseInfoLong = 0, kCollapseInfoBad = 1, kCollapseInfoWords = 2 };
+constexpr uint32_t kCollapseMaxLdsCap = 4096;
+struct CollapseArgs {
+  const unsigned long long *hit_off;   // nq + 1: the full ordered lists (top_k = 0) of the batch
+  const uint32_t *hit_gids;
+  const uint32_t *dense;               // per genome: its label as a dense id below n_labels
+  uint32_t n_genomes, n_labels, nq;
+  uint32_t lds_cap;                    // the longest list the LDS table takes
+  uint32_t lds_slots;                  // collapse_lds_slots(lds_cap)
+  uint32_t top_k;                      // 0 = no cut
+  unsigned long long *tables;          // one cleared table of n_labels entries per workgroup of the launch, or null (no list is long)
+  uint32_t *kept;                      // out, per hit: the label's members where the hit is its label's first, else 0
+  uint32_t *n_kept;                    // out, per query: its kept hits, at most top_k
+  uint32_t *info;                      // kCollapseInfoWords, zeroed by the caller
+};
+uint32_t collapse_lds_slots(uint32_t lds_cap);   // slots of the LDS table: a power of two >= 2 x lds_cap (12 bytes a slot)
+// n_blocks workgroups share the nq queries; with tables, n_blocks of them.  Leaves every table cleared.
+hipError_t launch_collapse_first(const CollapseArgs &a, uint32_t n_blocks, hipStream_t stream);
+hipError_t launch_collapse_table_init(unsigned long long *tables, uint64_t n_entries, hipStream_t stream);   // every entry cleared
+// off[0 .. n] = exclusive scan of n_kept
+hipError_t launch_collapse_scan(const uint32_t *n_kept, uint32_t n, unsigned long long *off, hipStream_t stream);
+// query q's first n_kept[q] kept hits, in list order, to out[off[q] ...)
+hipError_t launch_collapse_emit(const unsigned long long *hit_off, const uint32_t *hit_counts, const uint32_t *hit_gids, const uint32_t *kept,
+                                const uint32_t *n_kept, const unsigned long long *off, uint32_t n, CollapsedHit *out, hipStream_t stream);
+hipError_t launch_collapse_unpack(const CollapsedHit *in, uint64_t n, uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_members,
+                                  hipStream_t stream);   // (hit_members may be null)
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

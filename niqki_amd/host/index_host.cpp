@@ -30,6 +30,7 @@
 
 #include "../csrc/nq_pack.h"
 #include "file_reader.h"
+#include "label_file.h"
 #include "linkage_text.h"
 #include "seqio.h"
 
@@ -397,10 +398,60 @@ cover_fn engine_cover() { return (cover_fn)dlsym(RTLD_DEFAULT, "niqki_staged_cov
 
 bool Index::has_cover() { return engine_cover() != nullptr; }
 
+namespace {
+using set_labels_fn = int (*)(niqki_index *, const uint32_t *, uint32_t, int);
+using collapsed_fn = int (*)(niqki_index *, uint64_t *, uint32_t *, uint32_t *, uint32_t *, uint64_t, int);
+set_labels_fn engine_set_labels() { return (set_labels_fn)dlsym(RTLD_DEFAULT, "niqki_set_labels"); }
+collapsed_fn engine_collapsed() { return (collapsed_fn)dlsym(RTLD_DEFAULT, "niqki_staged_query_collapsed"); }
+}  // namespace
+
+bool Index::has_collapse() { return engine_set_labels() != nullptr && engine_collapsed() != nullptr; }
+
+void Index::set_collapse(const std::string &filestr) {
+  const set_labels_fn call = engine_set_labels();
+  if (!call || !engine_collapsed() || grp_) throw std::runtime_error("this engine has no collapsed query");
+  LabelFile lf;
+  std::string err;
+  try {
+    PinnedBuf bytes;
+    read_file_bytes(filestr, bytes);
+    lf = parse_label_file((const char *)bytes.p, bytes.size, filenames);
+    err = lf.error;
+  } catch (const std::exception &e) { err = e.what(); }
+  if (!err.empty()) {
+    // refused before anything is written: the output file the constructor made goes away again
+    outfile->close();
+    (void)::unlink(out_path_.c_str());
+    throw std::runtime_error("--collapse '" + filestr + "': " + err);
+  }
+  label_of_ = std::move(lf.label_of);
+  label_text_ = std::move(lf.texts);
+  check(call(h_, label_of_.empty() ? nullptr : label_of_.data(), (uint32_t)label_of_.size(), NIQKI_MEM_HOST), "niqki_set_labels");
+  collapse_ = true;
+}
+
 // hits of the staged entries, written in entry order
 // hits of the staged entries
 void Index::query_staged(size_t n, Hits &h) {
   const uint64_t N = niqki_genome_count(h_);
+  h.collapsed = false;
+  if (collapse_) {   // --collapse: each entry's best hit per label in the place of its hits, at most top_k labels
+    const collapsed_fn call = engine_collapsed();
+    if (!call) throw std::runtime_error("this engine has no collapsed query");
+    const uint64_t L = label_text_.size();
+    uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, L), 1) : std::max<uint64_t>(uint64_t(1) << 16, n * 8);
+    h.off.resize(n + 1);
+    for (;;) {
+      h.hc.resize(cap);
+      h.hg.resize(cap);
+      const int rc = call(h_, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST);
+      if (rc == NIQKI_E_CAPACITY && cap < n * L) { cap = std::max(h.off[n], cap * 2); continue; }
+      check(rc, "niqki_staged_query_collapsed");
+      break;
+    }
+    h.collapsed = N != 0;
+    return;
+  }
   if (cover) {   // --cover: each entry's greedy cover in the place of its hits, at most top_k picks (n x k never overflows)
     const cover_fn call = engine_cover();
     if (!call) throw std::runtime_error("this engine has no cover");
@@ -450,7 +501,7 @@ void Index::write_hits(const Hits &h) {
     text += h.names[i];
     text += ' ';
     for (uint64_t j = h.off[i]; j < h.off[i + 1]; ++j) {
-      text += filenames[h.hg[j]];
+      text += h.collapsed ? label_text_[label_of_[h.hg[j]]] : filenames[h.hg[j]];
       text += ':';
       const int n = snprintf(num, sizeof num, "%g", (double)h.hc[j] / F);
       text.append(num, (size_t)n);

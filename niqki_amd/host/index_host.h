@@ -106,6 +106,14 @@ class Index {
   // genome and the slots it newly explains, at most top_k picks where top_k > 0; --neighbors and -M are not affected.
   static bool has_cover();
   bool cover = false;
+  // Collapsed hits (long option --collapse <file>; single-GPU index; niqki_set_labels + niqki_staged_query_collapsed,
+  // looked up at run time like the calls above).  set_collapse reads the label file (label_file.h; plain or gzip) against
+  // `filenames` as they are at that moment and hands the labels to the engine; from then on the list of every -Q / -l
+  // query holds one entry per label -- the label's text and the jaccard of its best member -- at most top_k labels
+  // where top_k > 0; --neighbors and -M are not affected.  A file error is an error of the run, and then nothing is
+  // written, the -O file included.
+  static bool has_collapse();
+  void set_collapse(const std::string &filestr);
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
@@ -121,6 +129,7 @@ class Index {
     std::vector<std::string> names;
     std::vector<uint64_t> off;
     std::vector<uint32_t> hc, hg;
+    bool collapsed = false;   // hg names each label's best member: the line prints the label's text (--collapse)
     // lines mode: the names are header lines of a piece of the input that stays alive until the WRITER thread has
     // taken them (name e = the line at name_base + name_at[e]); `keep` is that piece
     const uint8_t *name_base = nullptr;
@@ -130,6 +139,9 @@ class Index {
   };
   void query_staged(size_t n, Hits &h);
   void write_hits(const Hits &h);
+  bool collapse_ = false;                // --collapse: set_collapse has run
+  std::vector<uint32_t> label_of_;      // ... per genome its label, per label its text (label_file.h)
+  std::vector<std::string> label_text_;
   std::string out_text_;                // write_hits' lines before they go to the writer
   std::string out_path_;                // the -O file (remove_listed takes it away again when it refuses)
   void stream_lines(const std::string &filestr, bool insert);

@@ -9,6 +9,9 @@
 //   --neighbors    the indexed genomes themselves as queries, in index order, written like -Q (niqki_neighbors_range)
 //   --cover        the list of every -Q / -q query is its greedy cover (niqki_staged_cover): the genome that explains
 //                  the most query slots, then the one that explains the most of the rest, ...; --top bounds the picks
+//   --collapse <f> f holds lines label<TAB>member (what --cluster / --derep write, or a taxonomy table): the list of
+//                  every -Q / -q query holds one entry per label, label:jaccard of the label's best member
+//                  (niqki_set_labels + niqki_staged_query_collapsed); --top bounds the labels
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
 //   --mst <f> / --linkage <f> / --tree <f>   the complete single-linkage hierarchy down to the -J threshold from ONE
 //                  engine call (niqki_linkage): the maximum spanning forest, the merge table, Newick dendrograms
@@ -48,7 +51,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -89,6 +92,7 @@ const Desc kDesc[] = {
     {LINKAGE, "", "linkage", NONEMPTY, "  --linkage <filename>          Single-linkage hierarchy down to the -J threshold: lines name<TAB>merges into<TAB>jaccard (cut it at any threshold for the --cluster groups)."},
     {TREE, "", "tree", NONEMPTY, "  --tree <filename>             Single-linkage dendrograms down to the -J threshold in Newick, one tree per line."},
     {COVER, "", "cover", NONE, "  --cover                       Report each -Q / -q query's greedy cover instead of all its hits: per genome the slots no earlier line explains (--top bounds the picks)."},
+    {COLLAPSE, "", "collapse", NONEMPTY, "  --collapse <filename>         Report each -Q / -q query's best hit per label instead of all its hits: the file holds lines label<TAB>member (as --cluster / --derep write them; plain or gzip), a genome no line names is its own label (--top bounds the labels)."},
 };
 
 struct Parsed {
@@ -333,6 +337,10 @@ int main(int argc, char *argv[]) {
     }
   }
 
+  if (o.has(COLLAPSE) && o.has(COVER)) {
+    cerr << "niqki: --collapse and --cover both replace a query's list: choose one" << endl;
+    return EXIT_FAILURE;
+  }
   // the cover reads whole counts and the winner's column of a device-resident sketch store
   if (o.has(COVER)) {
     if (n_gpus > 1) {
@@ -345,6 +353,18 @@ int main(int argc, char *argv[]) {
     }
     if (!nqhost::Index::has_cover()) {
       cerr << "niqki: this engine has no cover" << endl;
+      return EXIT_FAILURE;
+    }
+  }
+
+  // the collapsed list is selected on one device from whole counts
+  if (o.has(COLLAPSE)) {
+    if (n_gpus > 1) {
+      cerr << "niqki: --collapse needs a single-GPU index (--gpus 1)" << endl;
+      return EXIT_FAILURE;
+    }
+    if (!nqhost::Index::has_collapse()) {
+      cerr << "niqki: this engine has no collapsed query" << endl;
       return EXIT_FAILURE;
     }
   }
@@ -403,6 +423,8 @@ int main(int argc, char *argv[]) {
       clk.index_end = now;
     }
     run_matrix(*ix, o, clk);
+    // after everything that changes the index in memory (-M may index its list): the names are those of the final index
+    if (o.has(COLLAPSE)) ix->set_collapse(o.last(COLLAPSE));
     if (o.has(NEIGHBORS)) ix->query_neighbors();
     for (const Phase &ph : kQueryPhases) run_phase(*ix, o, ph);
     ix->outfile->close();
