@@ -824,7 +824,13 @@ int niqki_group_staged_query(niqki_group *g, uint32_t per, const uint32_t *n_ent
  * slots per page; 1 / all slots unless the index is paged), "delta_genomes" (genomes indexed by
  * the delta segment, see option "incremental_build"), "last_gather_form" (launch form the last
  * counter call used: bit 0 look-up pre-pass, bit 1 its streamed-rows kernel, bit 2 locality
- * order), "last_hits_form" (1 = the last niqki_query* call took the hit-list form, option "hit_lists"), "class_mask" (1 = the built index carries its per-slot class mask: single-tile
+ * order), "last_gather_kernel" (the gather kernel instantiation the last counter call launched:
+ * BLOCK | UNROLL << 12 | (NT + 1) << 20 | PAD << 24 -- threads per workgroup, bucket lines per round trip,
+ * NT = -1 look-ups from the pre-pass, 2..4 the stash form of that many tiles, 1 one look-up per tile; PAD = 1
+ * the padded walk was launched, which takes "bucket_align_log2" 6 and a 1024-thread shape; option
+ * "gather_variant" 1..5 = BLOCK, UNROLL 1024, 8 / 1024, 32 / 512, 16 / 256, 16 / 128, 16),
+ * "bucket_align_log2" (the built index's bucket alignment, as set by the option or chosen from the tile size),
+ * "last_hits_form" (1 =the last niqki_query* call took the hit-list form, option "hit_lists"), "class_mask" (1 = the built index carries its per-slot class mask: single-tile
  * indexes; the gather kernel then looks up only fingerprints whose sixteenth of the
  * fingerprint range holds a bucket in their slot -- a short read against a genome index
  * skips nearly all of its 2^S table look-ups; results are unaffected; NIQKI_HMASK=0 in the

@@ -166,6 +166,7 @@ int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride,
   }
   if (ordered && (rc = ensure(ix, ix->ws_order, (size_t)chunk * 8))) return rc;
   ix->last_form = (pre ? 1u : 0u) | (pre && nq::lookup_wants_packed(v) ? 2u : 0u) | (ordered ? 4u : 0u);
+  ix->last_kernel = nq::gather_shape_code(nq::gather_shape(v, ix->gather_variant, pre));   // what launch_gather launches below
   for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t n = std::min(chunk, nq - q0);
     Span sp(ix, NIQKI_KC_GATHER);

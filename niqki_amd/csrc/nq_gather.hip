@@ -785,7 +785,7 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
     g_gclk[(uint64_t)blockIdx.x * 64 + 15] = ((uint64_t)xcc << 32) | hw;
   }
 #endif
-  // (PAD: the padded walk addresses the counters from LDS address 0 -- launch_gather checks that this
+  // (PAD: the padded walk addresses the counters from LDS address 0 -- gather_shape checks that this
   // instantiation has no static LDS in front of its dynamic block and otherwise launches the form without PAD)
   const int32_t *sk = NT < 0 ? nullptr : sketches + (uint64_t)q * v.q_stride + v.q_off;
   Item *queue = (Item *)(cnt + (v.tile + 1) / 2 + (PAD ? kPadWords : 0u));  // behind the counters: kQueue items per wave
@@ -1087,6 +1087,34 @@ bool gather_variant_valid(int variant) {
   return variant >= 0 && variant <= 5;
 }
 
+GatherShape gather_shape(const IndexView &v, int variant, bool pre) {
+  // The padded walk (PAD = true) takes a counter's LDS address from the genome id alone: the kernel's dynamic
+  // LDS must start at LDS address 0, i.e. the instantiation must have no static LDS in front of it.  Asked of
+  // the runtime once per process; if a toolchain ever puts something there, the form with explicit lengths
+  // (any LDS base, any index layout) is launched instead.
+  static const bool pad_at_zero = [] {
+    hipFuncAttributes fa{};
+    return hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 32, -1, true>) == hipSuccess && fa.sharedSizeBytes == 0 &&
+           hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 16, 2, true>) == hipSuccess && fa.sharedSizeBytes == 0;
+  }();
+  const bool padded = v.padded && pad_at_zero;
+  // look-ups from the pre-pass: one form for any tile count; else the stash forms for 2..4 tiles
+  const int nt = pre ? -1 : (v.n_tiles >= 2 && v.n_tiles <= 4 ? (int)v.n_tiles : 1);
+  switch (variant) {
+    case 1: return GatherShape{1024, 8, nt, padded};
+    case 2: return GatherShape{1024, 32, nt, padded};
+    case 3: return GatherShape{512, 16, nt, false};
+    case 4: return GatherShape{256, 16, nt, false};
+    case 5: return GatherShape{128, 16, nt, false};
+    default: break;
+  }
+  // small tiles (short-read indexes): counters of <= 24 KB leave room for several
+  // workgroups per CU, and 4 waves per query then beat 16 (tools/bench_reads.py)
+  if (v.tile <= 12288) return GatherShape{256, 16, nt, false};
+  if (padded && pre) return GatherShape{1024, 32, nt, true};   // without look-ups of its own the walk gains from 32 lines per round trip (8.42 against 8.6 ms)
+  return GatherShape{1024, 16, nt, padded};   // padded index: mask-free bucket walk
+}
+
 hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t nq, uint16_t *counts, uint16_t *counts2,
                          uint64_t stride, Entry *stash, const uint32_t *order, int variant, bool pre,
                          hipStream_t stream, const CandOut &co) {
@@ -1111,39 +1139,27 @@ hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t n
     if (e != hipSuccess) return e;                                                               \
     hipLaunchKernelGGL(k, grid, dim3(B), lds, stream, v, sketches, counts, counts2, stride, stash, order, nq, co); \
   } while (0)
-  // The padded walk (PAD = true) takes a counter's LDS address from the genome id alone: the kernel's dynamic
-  // LDS must start at LDS address 0, i.e. the instantiation must have no static LDS in front of it.  Asked of
-  // the runtime once per process; if a toolchain ever puts something there, the form with explicit lengths
-  // (any LDS base, any index layout) is launched instead.
-  static const bool pad_at_zero = [] {
-    hipFuncAttributes fa{};
-    return hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 32, -1, true>) == hipSuccess && fa.sharedSizeBytes == 0 &&
-           hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 16, 2, true>) == hipSuccess && fa.sharedSizeBytes == 0;
-  }();
-  const bool padded = v.padded && pad_at_zero;
+  const GatherShape sh = gather_shape(v, variant, pre);
 #define NQ_BY_TILES(B, U, ...)                                                                   \
   do {                                                                                           \
-    if (pre) NQ_LAUNCH_GATHER(B, U, -1, ##__VA_ARGS__);                                           \
-    else if (v.n_tiles == 2) NQ_LAUNCH_GATHER(B, U, 2, ##__VA_ARGS__);                           \
-    else if (v.n_tiles == 3) NQ_LAUNCH_GATHER(B, U, 3, ##__VA_ARGS__);                           \
-    else if (v.n_tiles == 4) NQ_LAUNCH_GATHER(B, U, 4, ##__VA_ARGS__);                           \
+    if (sh.nt < 0) NQ_LAUNCH_GATHER(B, U, -1, ##__VA_ARGS__);                                     \
+    else if (sh.nt == 2) NQ_LAUNCH_GATHER(B, U, 2, ##__VA_ARGS__);                               \
+    else if (sh.nt == 3) NQ_LAUNCH_GATHER(B, U, 3, ##__VA_ARGS__);                               \
+    else if (sh.nt == 4) NQ_LAUNCH_GATHER(B, U, 4, ##__VA_ARGS__);                               \
     else NQ_LAUNCH_GATHER(B, U, 1, ##__VA_ARGS__);                                               \
   } while (0)
-  switch (variant) {
-    case 1: if (padded) NQ_BY_TILES(1024, 8, true); else NQ_BY_TILES(1024, 8); break;
-    case 2: if (padded) NQ_BY_TILES(1024, 32, true); else NQ_BY_TILES(1024, 32); break;
-    case 3: NQ_BY_TILES(512, 16); break;
-    case 4: NQ_BY_TILES(256, 16); break;
-    case 5: NQ_BY_TILES(128, 16); break;
-    default:
-      // small tiles (short-read indexes): counters of <= 24 KB leave room for several
-      // workgroups per CU, and 4 waves per query then beat 16 (tools/bench_reads.py)
-      if (v.tile <= 12288) NQ_BY_TILES(256, 16);
-      else if (padded && pre) NQ_BY_TILES(1024, 32, true);   // without look-ups of its own the walk gains from 32 lines per round trip (8.42 against 8.6 ms)
-      else if (padded) NQ_BY_TILES(1024, 16, true);   // padded index: mask-free bucket walk
-      else NQ_BY_TILES(1024, 16);
-      break;
-  }
+#define NQ_BY_PAD(B, U)                                                                          \
+  do {                                                                                           \
+    if (sh.pad) NQ_BY_TILES(B, U, true); else NQ_BY_TILES(B, U);                                 \
+  } while (0)
+  if (sh.block == 1024 && sh.unroll == 8) NQ_BY_PAD(1024, 8);
+  else if (sh.block == 1024 && sh.unroll == 16) NQ_BY_PAD(1024, 16);
+  else if (sh.block == 1024 && sh.unroll == 32) NQ_BY_PAD(1024, 32);
+  else if (sh.block == 512 && sh.unroll == 16 && !sh.pad) NQ_BY_TILES(512, 16);
+  else if (sh.block == 256 && sh.unroll == 16 && !sh.pad) NQ_BY_TILES(256, 16);
+  else if (sh.block == 128 && sh.unroll == 16 && !sh.pad) NQ_BY_TILES(128, 16);
+  else return hipErrorInvalidValue;   // (gather_shape names an instantiation this file does not have)
+#undef NQ_BY_PAD
 #undef NQ_BY_TILES
 #undef NQ_GATHER_LDS
 #undef NQ_LAUNCH_GATHER

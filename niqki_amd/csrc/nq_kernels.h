@@ -210,6 +210,17 @@ size_t lookup_pre_bytes(const IndexView &v, uint32_t nq);
 hipError_t launch_lookup(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *pre, hipStream_t stream);
 // launch shapes selectable through the "gather_variant" option (0 = choose)
 bool gather_variant_valid(int variant);
+// The gather_kernel<BLOCK, UNROLL, NT, PAD> instantiation launch_gather launches for (view, variant, pre): the one place
+// where the shape is chosen.  pad is the form actually launched (the padded walk needs its dynamic LDS at address 0).
+struct GatherShape {
+  int block, unroll, nt;
+  bool pad;
+};
+GatherShape gather_shape(const IndexView &v, int variant, bool pre);
+// stat "last_gather_kernel": BLOCK | UNROLL << 12 | (NT + 1) << 20 | PAD << 24
+constexpr uint32_t gather_shape_code(const GatherShape &s) {
+  return (uint32_t)s.block | (uint32_t)s.unroll << 12 | (uint32_t)(s.nt + 1) << 20 | (s.pad ? 1u : 0u) << 24;
+}
 // keys / order: nq words of scratch each
 hipError_t launch_order(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *keys,
                         uint32_t *order, hipStream_t stream);

@@ -745,7 +745,7 @@ def test_more_than_four_tiles(native, po, n, tile):
     e.close()
 
 
-@pytest.mark.parametrize("W,tile", [(12, 0), (12, 256), (11, 256), (12, 128), (12, 64), (11, 64)])
+@pytest.mark.parametrize("W,tile", [(12, 0), (12, 256), (11, 256), (12, 128), (12, 64), (11, 64), (13, 0)])
 def test_prepass_with_table_rows_staged_in_lds(native, po, W, tile):
     """The pre-pass form that streams whole table rows through LDS (a slot's packed row of TWO tiles copied into
     LDS, 1024 queries per workgroup; a last workgroup with idle threads) for W <= 12 indexes and real batches:
