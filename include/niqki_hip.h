@@ -634,6 +634,59 @@ int niqki_query_collapsed(niqki_index *ix, const int32_t *sketches, uint32_t nq,
 int niqki_staged_query_collapsed(niqki_index *ix, uint64_t *hit_off, uint32_t *hit_counts, uint32_t *hit_gids,
                                  uint32_t *hit_members, uint64_t capacity, int mem);
 
+/* Taxon of a query: the lowest common ancestor (LCA) of its near-best hits, the rule of Kraken and MEGAN.  Labels are
+ * flat; a collection also says that species X lies in genus Y and Y in family Z, and what a read classifier asks of
+ * the index is ONE taxon per query: the species when the best hits all lie in it, the genus when several of its
+ * species are hit equally well.  The result is one fixed-size row per query; nothing per hit leaves the device.
+ * niqki_set_taxonomy.  Taxa are the dense ids 0 .. n_taxa - 1.  parent[t] is t's parent; parent[t] == t makes t a root,
+ * and several roots form a forest.  genome_taxon[g] is the taxon of indexed genome g; interior taxa may carry genomes,
+ * and a taxon nothing refers to is fine.  n_genomes must equal niqki_genome_count; every genome_taxon[g] and parent[t]
+ * must be below n_taxa; n_taxa < 0xFFFFFFFE; following parent from any taxon must reach a root (no cycle other than a
+ * root's self-loop).  Any breach returns NIQKI_E_INVALID, niqki_last_error names the offending genome or taxon, and
+ * the taxonomy the handle had stays.  genome_taxon == NULL, parent == NULL or n_taxa == 0 removes the taxonomy.  mem as
+ * in niqki_set_labels: both arrays live in that space; the call may synchronise once.  Validation and the depth of
+ * every taxon (a root has depth 0) are one-off work on the host; the device keeps one 8-byte node {parent, depth} per
+ * taxon and genome_taxon.  Stat "taxa" = n_taxa (0 when no taxonomy is set), stat "taxonomy_depth" = the largest
+ * depth.  The taxonomy is independent of niqki_set_labels -- neither call disturbs the other -- and belongs to a
+ * genome set in the same way: every call that drops the labelling drops the taxonomy.  Without one the two query
+ * calls return NIQKI_E_STATE and niqki_last_error says to set it again (no genomes: NIQKI_OK also without one).
+ * Definition.  H(Q) is the list niqki_query returns for Q with top_k = 0 at the handle's min_score: count descending,
+ * then gid descending (min_score 0: every genome is a hit).  H(Q) empty: taxon = NIQKI_TAXON_NONE, best_count = 0,
+ * best_gid = 0xFFFFFFFF, considered = 0.  Otherwise best_count and best_gid are H(Q)'s first entry, and the CONSIDERED
+ * hits are the entries with count * 1000 >= best_count * (1000 - top_permille), in 64-bit arithmetic, equality
+ * included.  H is ordered, so they are a prefix of H(Q) and `considered` is its length.  top_permille = 0: only the
+ * ties with the best hit; 1000: every hit; above 1000: NIQKI_E_INVALID.  taxon is the deepest taxon that is an
+ * ancestor-or-self of genome_taxon[g] for every considered g, and NIQKI_TAXON_NONE when the considered hits lie in
+ * more than one tree (told from "no hit" by considered >= 2).  The handle's top_k is ignored; min_score and top_k are
+ * the handle's own again when the call returns, also when it fails.  The result is a function of the index, the
+ * taxonomy, Q, min_score and top_permille only: batch size, options, tile count, paging, a delta segment and hit
+ * lists versus counter rows do not change it.
+ * Outputs: four arrays of nq entries in `mem`; taxon is required, each of the other three may be NULL.
+ * NIQKI_MEM_HOST works in batches of option "query_batch"; NIQKI_MEM_DEVICE takes the nq sketches in one call and
+ * writes in stream order.  There is no capacity argument and NIQKI_E_CAPACITY never occurs.
+ * niqki_staged_query_lca works on the staged batch (niqki_stage_raw) and leaves it usable, as
+ * niqki_staged_query_collapsed does.
+ * Handles as niqki_query_collapsed: whole-range single-GPU handles, resident or paged, any tile count, with or without
+ * a delta segment, S <= 16; a slot-range shard gets NIQKI_E_STATE.  Groups, the _shared calls and the _ahead calls
+ * have no LCA form.
+ * How: per batch the query path itself runs at top_k = 0 into the handle's device hit buffers (budget: option
+ * "cluster_ws_mib"; a batch whose lists do not fit is halved down to one query, first half first; stat "lca_splits"),
+ * then one launch of lca_kernel per leaf.  A 256-thread workgroup takes four queries at a time, a wavefront each.  The
+ * wavefront finds the considered prefix by a 64-way search of the ordered counts (64 evenly spaced probes and a ballot
+ * a step, at most 6 steps), each lane folds its strided share of the prefix with a pairwise LCA -- lift the deeper
+ * node to the other's depth, then both until they meet or both are roots, at most "taxonomy_depth" steps each -- and
+ * six __shfl_xor steps combine the lanes.  A prefix longer than option "lca_wave_cap" (64 .. 65536, default 1024) is
+ * folded by the whole workgroup after the four waves' own queries; stat "lca_long_lists" counts those queries of the
+ * last call, stat "lca_no_common" its queries with considered >= 2 and no common taxon.  Nothing spins and no loop is
+ * unbounded.  While profiling is on: "lca_us_hits", "lca_us_fold" (microseconds, the last call).  DESIGN.md 4.5e. */
+#define NIQKI_TAXON_NONE 0xFFFFFFFFu
+int niqki_set_taxonomy(niqki_index *ix, const uint32_t *genome_taxon, uint32_t n_genomes, const uint32_t *parent,
+                       uint32_t n_taxa, int mem);
+int niqki_query_lca(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint32_t top_permille, uint32_t *taxon,
+                    uint32_t *best_count, uint32_t *best_gid, uint32_t *considered, int mem);
+int niqki_staged_query_lca(niqki_index *ix, uint32_t top_permille, uint32_t *taxon, uint32_t *best_count,
+                           uint32_t *best_gid, uint32_t *considered, int mem);
+
 /* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
  * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
  * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses

@@ -19,6 +19,7 @@ E_GZIP = 7
 FILE_GZIP = 0x80
 GROUP_ID_BYTES = 128
 E_CAPACITY = 4
+TAXON_NONE = 0xFFFFFFFF
 
 
 class NiqkiError(RuntimeError):
@@ -125,6 +126,9 @@ ABI = [
     ("niqki_set_labels", _int, [_vp, _vp, _u32, _int]),
     ("niqki_query_collapsed", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_staged_query_collapsed", _int, [_vp, _vp, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_set_taxonomy", _int, [_vp, _vp, _u32, _vp, _u32, _int]),
+    ("niqki_query_lca", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _int]),
+    ("niqki_staged_query_lca", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _int]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
@@ -669,6 +673,47 @@ class Engine:
         return self._cover(lambda off, hc, hg, hm, c: self.L.niqki_staged_query_collapsed(
             self.h, _p(off), _p(hc), _p(hg), _p(hm), c, MEM_HOST), nq, cap, members)
 
+    def set_taxonomy(self, genome_taxon, parent):
+        """niqki_set_taxonomy: genome_taxon[g] = the taxon of indexed genome g, parent[t] = the parent of taxon t (a
+        root is its own parent); numpy arrays, or two device tensors of 32-bit elements.  None for either removes the
+        taxonomy.  It lasts until genomes are added or dropped."""
+        if genome_taxon is None or parent is None:
+            self._ck(self.L.niqki_set_taxonomy(self.h, None, 0, None, 0, MEM_HOST))
+        elif hasattr(genome_taxon, "data_ptr") or hasattr(parent, "data_ptr"):
+            for t in (genome_taxon, parent):
+                if not hasattr(t, "data_ptr") or t.element_size() != 4 or not t.is_contiguous():
+                    raise ValueError("set_taxonomy: device tensors must both be contiguous and hold 32-bit ids")
+            self._ck(self.L.niqki_set_taxonomy(self.h, _p(genome_taxon), int(genome_taxon.numel()), _p(parent),
+                                               int(parent.numel()), MEM_DEVICE))
+        else:
+            gt = np.ascontiguousarray(genome_taxon, dtype=np.uint32).reshape(-1)
+            par = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+            spare = np.zeros(1, dtype=np.uint32)   # (an empty index has no genome taxa, and NULL would remove the taxonomy)
+            self._ck(self.L.niqki_set_taxonomy(self.h, _p(gt) if gt.size else _p(spare), gt.size,
+                                               _p(par) if par.size else None, par.size, MEM_HOST))
+
+    def _lca(self, call, nq, details):
+        outs = [np.empty(nq, dtype=np.uint32) for _ in range(4 if details else 1)]
+        ptrs = [_p(a) if nq else None for a in outs] + [None] * (4 - len(outs))
+        if nq == 0:
+            ptrs[0] = _p(np.empty(1, dtype=np.uint32))
+        self._ck(call(*ptrs))
+        return tuple(outs) if details else outs[0]
+
+    def query_lca(self, sketches, top_permille=0, details=False):
+        """niqki_query_lca: per query the deepest taxon that holds every hit within top_permille of its best hit
+        (TAXON_NONE: no hit, or hits in two trees), as a uint32 array; with details (taxon, best_count, best_gid,
+        considered)."""
+        sk = np.ascontiguousarray(sketches, dtype=np.int32).reshape(-1, self.F)
+        nq = sk.shape[0]
+        return self._lca(lambda t, bc, bg, co: self.L.niqki_query_lca(
+            self.h, _p(sk) if nq else None, nq, int(top_permille), t, bc, bg, co, MEM_HOST), nq, details)
+
+    def staged_query_lca(self, top_permille=0, details=False):
+        """niqki_staged_query_lca: query_lca of the staged batch's sketches; the staged batch stays usable."""
+        return self._lca(lambda t, bc, bg, co: self.L.niqki_staged_query_lca(
+            self.h, int(top_permille), t, bc, bg, co, MEM_HOST), self._staged.n_entry, details)
+
     def retain(self, keep):
         """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),
         new_ids[g] = the new id of old genome g (the kept genomes below it), 0xFFFFFFFF for a dropped one.  The handle
@@ -830,6 +875,11 @@ class Engine:
         total in hit_off[nq] and nothing else written."""
         return self._ck(self.L.niqki_query_collapsed(self.h, _p(sketches), nq, _p(hit_off), _p(hc), _p(hg), _p(hm),
                                                      capacity, MEM_DEVICE), allow=(E_CAPACITY,))
+
+    def query_lca_dev(self, sketches, nq, top_permille, taxon, best_count=None, best_gid=None, considered=None):
+        """niqki_query_lca on device arrays (each of the last three may be None), written in stream order."""
+        self._ck(self.L.niqki_query_lca(self.h, _p(sketches), nq, int(top_permille), _p(taxon), _p(best_count), _p(best_gid),
+                                        _p(considered), MEM_DEVICE))
 
     def query_sequences_dev(self, seqs, rec_off, n, hit_off, hc, hg, capacity):
         self._ck(self.L.niqki_query_sequences(self.h, _p(seqs), _p(rec_off), n, None, n, _p(hit_off),

@@ -382,6 +382,7 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_raw, &ix->ws_wire[0], &ix->ws_wire[1], &ix->ws_redo[0], &ix->ws_redo[1], &ix->ws_fmeta, &ix->ws_summ, &ix->ws_chunk, &ix->ws_fkept, &ix->ws_fnrec,
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
                  &ix->ws_cv_orig, &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
+                 &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info,
                  &ix->lab_dense, &ix->ws_cl_sk, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
@@ -479,6 +480,11 @@ int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
   if (!std::strcmp(key, "collapse_lds_cap")) {
     if (value < 1 || value > (int64_t)nq::kCollapseMaxLdsCap) return fail(ix, NIQKI_E_INVALID, "collapse_lds_cap must be in 1..4096");
     ix->collapse_lds_cap = (uint32_t)value;
+    return NIQKI_OK;
+  }
+  if (!std::strcmp(key, "lca_wave_cap")) {
+    if (value < (int64_t)nq::kLcaMinWaveCap || value > (int64_t)nq::kLcaMaxWaveCap) return fail(ix, NIQKI_E_INVALID, "lca_wave_cap must be in 64..65536");
+    ix->lca_wave_cap = (uint32_t)value;
     return NIQKI_OK;
   }
   if (!std::strcmp(key, "query_batch")) { if (value < 1) return NIQKI_E_INVALID; ix->query_batch = (uint32_t)value; return NIQKI_OK; }
@@ -606,6 +612,14 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "collapse_us_hits")) { *value = (uint64_t)(ix->collapse_stats.ms[0] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "collapse_us_first")) { *value = (uint64_t)(ix->collapse_stats.ms[1] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "collapse_us_emit")) { *value = (uint64_t)(ix->collapse_stats.ms[2] * 1000.0); return NIQKI_OK; }
+  // niqki_set_taxonomy; the last niqki_query_lca / niqki_staged_query_lca call; its phases while profiling was on
+  if (!std::strcmp(key, "taxa")) { *value = ix->tax_set ? ix->n_taxa : 0; return NIQKI_OK; }
+  if (!std::strcmp(key, "taxonomy_depth")) { *value = ix->tax_set ? ix->tax_depth : 0; return NIQKI_OK; }
+  if (!std::strcmp(key, "lca_splits")) { *value = ix->lca_stats.splits; return NIQKI_OK; }
+  if (!std::strcmp(key, "lca_long_lists")) { *value = ix->lca_stats.long_lists; return NIQKI_OK; }
+  if (!std::strcmp(key, "lca_no_common")) { *value = ix->lca_stats.no_common; return NIQKI_OK; }
+  if (!std::strcmp(key, "lca_us_hits")) { *value = (uint64_t)(ix->lca_stats.ms[0] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "lca_us_fold")) { *value = (uint64_t)(ix->lca_stats.ms[1] * 1000.0); return NIQKI_OK; }
   // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
   if (!std::strcmp(key, "retain_us_rank")) { *value = (uint64_t)(ix->retain_ms[0] * 1000.0); return NIQKI_OK; }
   if (!std::strcmp(key, "retain_us_compact")) { *value = (uint64_t)(ix->retain_ms[1] * 1000.0); return NIQKI_OK; }

@@ -172,6 +172,7 @@ int insert_dev(niqki_index *ix, const int32_t *sketches, uint32_t sk_stride, uin
   int rc = reserve_store(ix, (uint64_t)ix->n_genomes + n);
   if (rc) return rc;
   drop_labels(ix);   // (niqki_set_labels: a labelling belongs to a genome set)
+  drop_taxonomy(ix);   // (niqki_set_taxonomy: so does a taxonomy)
   if (ix->resident_bytes) {
     // paged: transpose into a device staging block of all the handle's slots, then rows to the host store
     const uint32_t f_all = ix->full_end - ix->full_begin;

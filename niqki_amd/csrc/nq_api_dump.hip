@@ -364,6 +364,7 @@ int niqki_append_slots(niqki_index *ix, uint32_t slot_begin, uint32_t slot_end, 
   if (slot_end == ix->d.F) {   // commit, as insert_dev ends
     ix->n_genomes += ix->append.n_new;
     drop_labels(ix);
+    drop_taxonomy(ix);
     ix->built = false;
     ix->pg_layout_n = 0xFFFFFFFFu;
     append_drop(ix);

@@ -1,0 +1,293 @@
+// nq_api_lca.hip -- niqki_set_taxonomy, niqki_query_lca and niqki_staged_query_lca behind the C ABI: per query the
+// lowest taxon that holds all its near-best hits (niqki_hip.h).  A batch's full lists are the query path's own
+// (query_hits_dev at top_k = 0 into the handle's hit buffers, within the budget of the self-join calls), so every count,
+// the threshold, the order and the ties are the pinned path's; the kernel of nq_lca.hip only folds a prefix of them.
+// The lists never leave the device: four words a query do.  DESIGN.md 4.5e.
+#include "nq_handle.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace nqi {
+
+void drop_taxonomy(niqki_index *ix) {
+  ix->tax_set = false;
+  ix->n_taxa = 0;
+  ix->tax_depth = 0;
+}
+
+namespace {
+
+// The query path at the handle's threshold and no top-k; the handle's own values come back whatever happens.
+struct LcaCall {
+  niqki_index *ix;
+  const uint32_t ms, pms, k;
+  explicit LcaCall(niqki_index *ix_) : ix(ix_), ms(ix_->d.min_score), pms(ix_->p.min_score), k(ix_->p.top_k) { ix->p.top_k = 0; }
+  ~LcaCall() {
+    ix->d.min_score = ms;
+    ix->p.min_score = pms;
+    ix->p.top_k = k;
+  }
+};
+
+// events of a leaf while the handle is profiling: 0-1 hits, 1-2 fold
+struct LcaEvents {
+  niqki_index *ix;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  explicit LcaEvents(niqki_index *ix_) : ix(ix_) {}
+  ~LcaEvents() {
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  int create() {
+    if (ix->prof) for (auto &e : ev) NQ_HIP(ix, hipEventCreate(&e));
+    return NIQKI_OK;
+  }
+  int mark(int k) {
+    if (ix->prof) NQ_HIP(ix, hipEventRecord(ev[k], ix->stream));
+    return NIQKI_OK;
+  }
+  int add(int a, int b, int to) {
+    if (!ix->prof) return NIQKI_OK;
+    float ms = 0;
+    NQ_HIP(ix, hipEventSynchronize(ev[b]));
+    NQ_HIP(ix, hipEventElapsedTime(&ms, ev[a], ev[b]));
+    ix->lca_stats.ms[to] += ms;
+    return NIQKI_OK;
+  }
+};
+
+struct Lca {
+  niqki_index *ix;
+  LcaEvents ev;
+  const char *who = "";
+  uint32_t top_permille = 0;
+  uint64_t stride = 0, room = 0;
+  uint32_t *out[4] = {nullptr, nullptr, nullptr, nullptr};   // device rows of the batch: taxon, best_count, best_gid, considered
+  explicit Lca(niqki_index *ix_) : ix(ix_), ev(ix_) {}
+};
+
+// Queries [q_at, q_at + n) of the batch, their sketches at d_sk: full lists into the fixed hit buffers, then one launch
+// that writes the leaf's result rows at q_at.  A leaf whose full lists exceed the room is halved (the rule of
+// self_join_batch), the first half before the second.
+int lca_leaf(Lca &c, const int32_t *d_sk, uint32_t q_at, uint32_t n) {
+  niqki_index *ix = c.ix;
+  int rc;
+  Planes pl;
+  HitOut out;
+  if ((rc = counter_planes(ix, n, c.stride, pl))) return rc;
+  if ((rc = hit_out_ws(ix, n, c.room, out))) return rc;
+  if ((rc = c.ev.mark(0))) return rc;
+  rc = query_hits_dev(ix, d_sk, n, pl, c.stride, out);
+  if (rc == NIQKI_E_CAPACITY) {
+    if (n == 1) return fail(ix, NIQKI_E_STATE, std::string(c.who) + ": one query's hits exceed the genome count");   // (room >= N)
+    ix->lca_stats.splits += 1;
+    const uint32_t h = n / 2;
+    if ((rc = lca_leaf(c, d_sk, q_at, h))) return rc;
+    return lca_leaf(c, d_sk + (size_t)h * ix->d.F, q_at + h, n - h);
+  }
+  if (rc) return rc;
+  if ((rc = c.ev.mark(1))) return rc;
+  nq::LcaArgs a{};
+  a.hit_off = out.off;
+  a.hit_counts = out.counts;
+  a.hit_gids = out.gids;
+  a.nodes = (const nq::TaxNode *)ix->tax_nodes.p;
+  a.genome_taxon = (const uint32_t *)ix->tax_genome.p;
+  a.n_genomes = ix->n_genomes;
+  a.n_taxa = ix->n_taxa;
+  a.max_depth = ix->tax_depth;
+  a.nq = n;
+  a.top_permille = c.top_permille;
+  a.wave_cap = ix->lca_wave_cap;
+  a.taxon = c.out[0] + q_at;
+  a.best_count = c.out[1] ? c.out[1] + q_at : nullptr;
+  a.best_gid = c.out[2] ? c.out[2] + q_at : nullptr;
+  a.considered = c.out[3] ? c.out[3] + q_at : nullptr;
+  a.info = (uint32_t *)ix->ws_lca_info.p;
+  NQ_HIP(ix, nq::launch_lca(a, ix->stream));
+  if ((rc = c.ev.mark(2))) return rc;
+  if ((rc = c.ev.add(0, 1, 0)) || (rc = c.ev.add(1, 2, 1))) return rc;
+  return NIQKI_OK;
+}
+
+// rows [0, n) of a query without a hit
+int lca_no_hit(niqki_index *ix, uint32_t *const out[4], uint32_t n, bool dev) {
+  static const int fill[4] = {0xFF, 0, 0xFF, 0};   // NIQKI_TAXON_NONE, 0, 0xFFFFFFFF, 0
+  for (int j = 0; j < 4; ++j) {
+    if (!out[j] || !n) continue;
+    if (dev) NQ_HIP(ix, hipMemsetAsync(out[j], fill[j], (size_t)n * 4, ix->stream));
+    else std::fill(out[j], out[j] + n, fill[j] ? 0xFFFFFFFFu : 0u);
+  }
+  return NIQKI_OK;
+}
+
+int lca_run(niqki_index *ix, const char *who, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint32_t top_permille,
+            uint32_t *taxon, uint32_t *best_count, uint32_t *best_gid, uint32_t *considered, int mem) {
+  ix->lca_stats = LcaStats();
+  if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, std::string(who) + ": a slot-range shard sees partial counts; the LCA query needs a whole-range handle");
+  if (top_permille > 1000) return fail(ix, NIQKI_E_INVALID, std::string(who) + ": top_permille " + std::to_string(top_permille) + " is above 1000");
+  const bool dev = mem == NIQKI_MEM_DEVICE;
+  const uint32_t N = ix->n_genomes, F = ix->d.F;
+  if (N && !ix->tax_set)
+    return fail(ix, NIQKI_E_STATE, std::string(who) + ": no taxonomy on this genome set: call niqki_set_taxonomy (again, after genomes were added or dropped)");
+  uint32_t *const user[4] = {taxon, best_count, best_gid, considered};
+  if (nq == 0 || N == 0) return lca_no_hit(ix, user, nq, dev);
+  LcaCall guard(ix);
+  int rc = build_if_needed(ix);
+  if (rc) return rc;
+  Lca c(ix);
+  c.who = who;
+  c.top_permille = top_permille;
+  c.stride = NIQKI_ROW_STRIDE(N);
+  // the hit buffers of the self-join calls: 16 bytes a hit, never below N, the hits of one query
+  c.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
+  if ((rc = c.ev.create())) return rc;
+  const uint32_t qb = dev ? nq : std::max<uint32_t>(ix->query_batch, 1);
+  const uint32_t rows = std::min(qb, nq);
+  if ((rc = ensure(ix, ix->ws_lca_info, nq::kLcaInfoWords * 4))) return rc;
+  NQ_HIP(ix, hipMemsetAsync(ix->ws_lca_info.p, 0, nq::kLcaInfoWords * 4, ix->stream));
+  if (dev) {
+    for (int j = 0; j < 4; ++j) c.out[j] = user[j];
+  } else {   // a batch's rows: four arrays of `rows` words, the ones nobody asked for left out
+    if ((rc = ensure(ix, ix->ws_lca_out, (size_t)rows * 16))) return rc;
+    for (int j = 0; j < 4; ++j) c.out[j] = user[j] ? (uint32_t *)ix->ws_lca_out.p + (size_t)j * rows : nullptr;
+  }
+  for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+    const uint32_t n = std::min(qb, nq - q0);
+    const int32_t *d_orig = d_sketches ? d_sketches + (size_t)q0 * F : nullptr;
+    if (!d_orig) {
+      if ((rc = ensure(ix, ix->ws_cl_sk, (size_t)n * F * 4))) return rc;
+      NQ_HIP(ix, hipMemcpyAsync(ix->ws_cl_sk.p, h_sketches + (size_t)q0 * F, (size_t)n * F * 4, hipMemcpyHostToDevice, ix->stream));
+      d_orig = (const int32_t *)ix->ws_cl_sk.p;
+    }
+    if ((rc = lca_leaf(c, d_orig, 0, n))) return rc;
+    if (dev) break;   // (one batch)
+    for (int j = 0; j < 4; ++j)
+      if (user[j]) NQ_HIP(ix, hipMemcpyAsync(user[j] + q0, c.out[j], (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
+    NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // (the next batch writes the same rows)
+  }
+  uint32_t info[nq::kLcaInfoWords] = {0, 0, 0};
+  NQ_HIP(ix, hipMemcpyAsync(info, ix->ws_lca_info.p, sizeof info, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  if (info[nq::kLcaInfoBad]) return fail(ix, NIQKI_E_STATE, std::string(who) + ": a hit outside the index or a taxon outside the taxonomy (a bug)");
+  ix->lca_stats.long_lists = info[nq::kLcaInfoLong];
+  ix->lca_stats.no_common = info[nq::kLcaInfoNoCommon];
+  return NIQKI_OK;
+}
+
+}  // namespace
+
+}  // namespace nqi
+
+using namespace nqi;
+
+extern "C" {
+
+int niqki_set_taxonomy(niqki_index *ix, const uint32_t *genome_taxon, uint32_t n_genomes, const uint32_t *parent, uint32_t n_taxa, int mem) {
+  if (!ix) return NIQKI_E_INVALID;
+  if (!genome_taxon || !parent || n_taxa == 0) {
+    drop_taxonomy(ix);
+    return NIQKI_OK;
+  }
+  const char *who = "niqki_set_taxonomy: ";
+  if (n_genomes != ix->n_genomes)
+    return fail(ix, NIQKI_E_INVALID, who + std::to_string(n_genomes) + " genome taxa for " + std::to_string(ix->n_genomes) + " genomes");
+  if (n_taxa >= 0xFFFFFFFEu) return fail(ix, NIQKI_E_INVALID, who + std::to_string(n_taxa) + " taxa: the count must be below 4294967294");
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  std::vector<uint32_t> gt(n_genomes), par(n_taxa);
+  if (mem == NIQKI_MEM_DEVICE) {
+    if (n_genomes) NQ_HIP(ix, hipMemcpyAsync(gt.data(), genome_taxon, (size_t)n_genomes * 4, hipMemcpyDeviceToHost, ix->stream));
+    NQ_HIP(ix, hipMemcpyAsync(par.data(), parent, (size_t)n_taxa * 4, hipMemcpyDeviceToHost, ix->stream));
+    NQ_HIP(ix, hipStreamSynchronize(ix->stream));
+  } else {
+    std::copy(genome_taxon, genome_taxon + n_genomes, gt.begin());
+    std::copy(parent, parent + n_taxa, par.begin());
+  }
+  // validation and depths: one-off work on the host
+  for (uint32_t g = 0; g < n_genomes; ++g)
+    if (gt[g] >= n_taxa)
+      return fail(ix, NIQKI_E_INVALID, who + std::string("genome ") + std::to_string(g) + " has taxon " + std::to_string(gt[g]) + ", not below " + std::to_string(n_taxa));
+  for (uint32_t t = 0; t < n_taxa; ++t)
+    if (par[t] >= n_taxa)
+      return fail(ix, NIQKI_E_INVALID, who + std::string("taxon ") + std::to_string(t) + " has parent " + std::to_string(par[t]) + ", not below " + std::to_string(n_taxa));
+  // every taxon's depth from the first settled ancestor above it; a walk that meets its own trail has found a cycle
+  std::vector<nq::TaxNode> nodes(n_taxa);
+  std::vector<uint8_t> state(n_taxa, 0);   // 0 = untouched, 1 = on the trail of the walk under way, 2 = settled
+  std::vector<uint32_t> trail;
+  uint32_t deepest = 0;
+  for (uint32_t t0 = 0; t0 < n_taxa; ++t0) {
+    if (state[t0]) continue;
+    trail.clear();
+    uint32_t t = t0, d = 0;
+    for (;;) {
+      if (state[t] == 2) {
+        d = nodes[t].depth + 1;
+        break;
+      }
+      if (state[t] == 1) return fail(ix, NIQKI_E_INVALID, who + std::string("taxon ") + std::to_string(t) + " lies on a cycle of parents");
+      if (par[t] == t) {   // a root
+        nodes[t] = nq::TaxNode{t, 0};
+        state[t] = 2;
+        d = 1;
+        break;
+      }
+      state[t] = 1;
+      trail.push_back(t);
+      t = par[t];
+    }
+    for (size_t j = trail.size(); j-- > 0;) {
+      const uint32_t u = trail[j];
+      nodes[u] = nq::TaxNode{par[u], d};
+      state[u] = 2;
+      deepest = std::max(deepest, d);
+      d += 1;
+    }
+  }
+  Buf nb, gb;   // the new arrays first: the taxonomy the handle had stays when memory runs out
+  int rc = ensure(ix, nb, (size_t)n_taxa * sizeof(nq::TaxNode));
+  if (!rc) rc = ensure(ix, gb, std::max<size_t>((size_t)n_genomes * 4, 4));
+  if (rc) {
+    if (nb.p) (void)hipFree(nb.p);
+    return rc;
+  }
+  hipError_t e = hipMemcpyAsync(nb.p, nodes.data(), (size_t)n_taxa * sizeof(nq::TaxNode), hipMemcpyHostToDevice, ix->stream);
+  if (e == hipSuccess && n_genomes) e = hipMemcpyAsync(gb.p, gt.data(), (size_t)n_genomes * 4, hipMemcpyHostToDevice, ix->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);   // (the vectors leave scope; earlier launches are through with the old arrays)
+  if (e != hipSuccess) {
+    (void)hipFree(nb.p);
+    (void)hipFree(gb.p);
+    NQ_HIP(ix, e);
+  }
+  if (ix->tax_nodes.p) (void)hipFree(ix->tax_nodes.p);
+  if (ix->tax_genome.p) (void)hipFree(ix->tax_genome.p);
+  ix->tax_nodes = nb;
+  ix->tax_genome = gb;
+  ix->n_taxa = n_taxa;
+  ix->tax_depth = deepest;
+  ix->tax_set = true;
+  return NIQKI_OK;
+}
+
+int niqki_query_lca(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint32_t top_permille, uint32_t *taxon, uint32_t *best_count,
+                    uint32_t *best_gid, uint32_t *considered, int mem) {
+  if (!ix || ((!sketches || !taxon) && nq)) return NIQKI_E_INVALID;
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  const bool dev = mem == NIQKI_MEM_DEVICE;
+  return lca_run(ix, "niqki_query_lca", dev ? sketches : nullptr, dev ? nullptr : sketches, nq, top_permille, taxon, best_count, best_gid,
+                 considered, mem);
+}
+
+int niqki_staged_query_lca(niqki_index *ix, uint32_t top_permille, uint32_t *taxon, uint32_t *best_count, uint32_t *best_gid,
+                           uint32_t *considered, int mem) {
+  if (!ix) return NIQKI_E_INVALID;
+  NQ_HIP(ix, hipSetDevice(ix->device));
+  int rc = staged_sketch_ws(ix);
+  if (rc) return rc;
+  if (!taxon && ix->staged.n_entry) return NIQKI_E_INVALID;
+  // (the staged sketches are only read, so niqki_staged_query answers as before)
+  return lca_run(ix, "niqki_staged_query_lca", (const int32_t *)ix->ws_stsk.p, nullptr, ix->staged.n_entry, top_permille, taxon, best_count,
+                 best_gid, considered, mem);
+}
+
+}  // extern "C"

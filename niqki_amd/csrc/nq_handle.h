@@ -45,6 +45,14 @@ struct CollapseStats {
   double ms[3] = {0, 0, 0};  // while profiling is on: hits, first, emit
 };
 
+// what niqki_get_stat reports of the last niqki_query_lca / niqki_staged_query_lca call (nq_api_lca.hip)
+struct LcaStats {
+  uint64_t splits = 0;       // batches the call had to halve
+  uint64_t long_lists = 0;   // queries whose considered prefix the whole workgroup folded
+  uint64_t no_common = 0;    // queries with two or more considered hits and no common taxon
+  double ms[2] = {0, 0};     // while profiling is on: hits, fold
+};
+
 void shared_free(struct ::niqki_index *ix);   // nq_shared.hip
 
 }  // namespace nqi
@@ -156,6 +164,15 @@ struct niqki_index {
   // info words, the global tables, a batch's collapsed entries, its offsets on their way to the host
   nqi::Buf ws_cl_sk, ws_cl_keep, ws_cl_nk, ws_cl_off, ws_cl_tab, ws_cl_stage;
   bool cl_tab_clean = false;   // every entry of ws_cl_tab is cleared (false after growth and while a call is under way)
+  // niqki_set_taxonomy: a node {parent, depth} per taxon and every genome's taxon (device), how many taxa there are and
+  // the largest depth; every call that changes the genome set drops them (drop_taxonomy).  Independent of the labels.
+  nqi::Buf tax_nodes, tax_genome;
+  uint32_t n_taxa = 0, tax_depth = 0;
+  bool tax_set = false;
+  uint32_t lca_wave_cap = 1024;   // option "lca_wave_cap": the longest considered prefix one wavefront of lca_kernel folds
+  nqi::LcaStats lca_stats;
+  // niqki_query_lca: a host call's result rows of a batch, the info words of a call (a host call's sketches: ws_cl_sk)
+  nqi::Buf ws_lca_out, ws_lca_info;
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
 
@@ -285,6 +302,8 @@ int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketc
               uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
 // ---- nq_api_collapse.hip ----
 void drop_labels(niqki_index *ix);   // the genome set changes: the labelling of niqki_set_labels goes
+// ---- nq_api_lca.hip ----
+void drop_taxonomy(niqki_index *ix);   // the genome set changes: the taxonomy of niqki_set_taxonomy goes
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);

@@ -384,6 +384,30 @@ hipError_t launch_collapse_emit(const unsigned long long *hit_off, const uint32_
 hipError_t launch_collapse_unpack(const CollapsedHit *in, uint64_t n, uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_members,
                                   hipStream_t stream);   // (hit_members may be null)
 
+// ---- taxon of a query: the LCA of its near-best hits (nq_lca.hip; the batches: nq_api_lca.hip) ------------
+// One taxon of the device taxonomy: a step up the tree is one 8-byte load.  A root is its own parent at depth 0.
+struct TaxNode {
+  uint32_t parent, depth;
+};
+constexpr uint32_t kTaxonNone = 0xFFFFFFFFu;   // NIQKI_TAXON_NONE: absorbing in the fold
+// info words of a call: queries folded by the whole workgroup; gids or nodes out of range (a bug: the host ends the
+// call); queries with two or more considered hits and no common taxon
+enum : uint32_t { kLcaInfoLong = 0, kLcaInfoBad = 1, kLcaInfoNoCommon = 2, kLcaInfoWords = 3 };
+constexpr uint32_t kLcaMinWaveCap = 64, kLcaMaxWaveCap = 65536;
+struct LcaArgs {
+  const unsigned long long *hit_off;   // nq + 1: the full ordered lists (top_k = 0) of the leaf
+  const uint32_t *hit_counts, *hit_gids;
+  const TaxNode *nodes;                // n_taxa
+  const uint32_t *genome_taxon;        // n_genomes, each below n_taxa
+  uint32_t n_genomes, n_taxa, max_depth, nq;
+  uint32_t top_permille;               // 0 .. 1000
+  uint32_t wave_cap;                   // the longest considered prefix one wavefront folds
+  uint32_t *taxon;                     // out, nq rows each; the three below may be null
+  uint32_t *best_count, *best_gid, *considered;
+  uint32_t *info;                      // kLcaInfoWords, zeroed by the caller; the launch adds to them
+};
+hipError_t launch_lca(const LcaArgs &a, hipStream_t stream);
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

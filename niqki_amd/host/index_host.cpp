@@ -31,6 +31,7 @@
 #include "../csrc/nq_pack.h"
 #include "file_reader.h"
 #include "label_file.h"
+#include "taxonomy_file.h"
 #include "linkage_text.h"
 #include "seqio.h"
 
@@ -430,11 +431,75 @@ void Index::set_collapse(const std::string &filestr) {
   collapse_ = true;
 }
 
+namespace {
+using set_taxonomy_fn = int (*)(niqki_index *, const uint32_t *, uint32_t, const uint32_t *, uint32_t, int);
+using lca_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, int);
+set_taxonomy_fn engine_set_taxonomy() { return (set_taxonomy_fn)dlsym(RTLD_DEFAULT, "niqki_set_taxonomy"); }
+lca_fn engine_lca() { return (lca_fn)dlsym(RTLD_DEFAULT, "niqki_staged_query_lca"); }
+}  // namespace
+
+bool Index::has_lca() { return engine_set_taxonomy() != nullptr && engine_lca() != nullptr; }
+
+void Index::set_lca(const std::string &filestr, uint32_t top_permille, const std::string &label_file) {
+  const set_taxonomy_fn call = engine_set_taxonomy();
+  if (!call || !engine_lca() || grp_) throw std::runtime_error("this engine has no LCA query");
+  LabelFile lf;
+  TaxonomyFile tf;
+  std::string err, which = "--lca '" + filestr + "'";
+  try {
+    if (!label_file.empty()) {   // --collapse beside --lca: its labels are the leaves
+      PinnedBuf bytes;
+      read_file_bytes(label_file, bytes);
+      lf = parse_label_file((const char *)bytes.p, bytes.size, filenames);
+      if (!lf.error.empty()) which = "--collapse '" + label_file + "'";
+    } else {
+      lf = parse_label_file(nullptr, 0, filenames);   // every genome its own label under its own name
+    }
+    err = lf.error;
+    if (err.empty()) {
+      PinnedBuf bytes;
+      read_file_bytes(filestr, bytes);
+      tf = parse_taxonomy_file((const char *)bytes.p, bytes.size, lf.texts);
+      err = tf.error;
+    }
+  } catch (const std::exception &e) { err = e.what(); }
+  if (!err.empty()) {
+    // refused before anything is written: the output file the constructor made goes away again
+    outfile->close();
+    (void)::unlink(out_path_.c_str());
+    throw std::runtime_error(which + ": " + err);
+  }
+  taxon_text_ = std::move(tf.texts);
+  if (!lf.label_of.empty())
+    check(call(h_, lf.label_of.data(), (uint32_t)lf.label_of.size(), tf.parent.data(), (uint32_t)tf.parent.size(), NIQKI_MEM_HOST), "niqki_set_taxonomy");
+  lca_permille_ = top_permille;
+  lca_ = true;
+}
+
 // hits of the staged entries, written in entry order
 // hits of the staged entries
 void Index::query_staged(size_t n, Hits &h) {
   const uint64_t N = niqki_genome_count(h_);
   h.collapsed = false;
+  h.lca = false;
+  if (lca_) {   // --lca: each entry's taxon in the place of its hits, with the count of its best hit; no entry without a hit
+    const lca_fn call = engine_lca();
+    if (!call) throw std::runtime_error("this engine has no LCA query");
+    std::vector<uint32_t> taxon(std::max<size_t>(n, 1)), best(std::max<size_t>(n, 1)), considered(std::max<size_t>(n, 1));
+    check(call(h_, lca_permille_, taxon.data(), best.data(), nullptr, considered.data(), NIQKI_MEM_HOST), "niqki_staged_query_lca");
+    h.off.assign(n + 1, 0);
+    h.hc.clear();
+    h.hg.clear();
+    for (size_t i = 0; i < n; ++i) {
+      if (considered[i]) {
+        h.hc.push_back(best[i]);
+        h.hg.push_back(taxon[i]);
+      }
+      h.off[i + 1] = h.hc.size();
+    }
+    h.lca = true;
+    return;
+  }
   if (collapse_) {   // --collapse: each entry's best hit per label in the place of its hits, at most top_k labels
     const collapsed_fn call = engine_collapsed();
     if (!call) throw std::runtime_error("this engine has no collapsed query");
@@ -501,7 +566,8 @@ void Index::write_hits(const Hits &h) {
     text += h.names[i];
     text += ' ';
     for (uint64_t j = h.off[i]; j < h.off[i + 1]; ++j) {
-      text += h.collapsed ? label_text_[label_of_[h.hg[j]]] : filenames[h.hg[j]];
+      if (h.lca) text += h.hg[j] < taxon_text_.size() ? taxon_text_[h.hg[j]] : std::string("no_common_taxon");
+      else text += h.collapsed ? label_text_[label_of_[h.hg[j]]] : filenames[h.hg[j]];
       text += ':';
       const int n = snprintf(num, sizeof num, "%g", (double)h.hc[j] / F);
       text.append(num, (size_t)n);

@@ -114,6 +114,15 @@ class Index {
   // written, the -O file included.
   static bool has_collapse();
   void set_collapse(const std::string &filestr);
+  // Taxon of a query (long options --lca <file>, --lca-top <permille>; single-GPU index; niqki_set_taxonomy +
+  // niqki_staged_query_lca, looked up at run time like the calls above).  set_lca reads the taxonomy file
+  // (taxonomy_file.h; plain or gzip) over the label texts of the run -- those of label_file (the --collapse file)
+  // where it is not empty, else every genome under its own name -- and hands genome taxa and parents to the engine;
+  // from then on the list of every -Q / -l query holds at most one entry, taxonText:jaccard of the best hit
+  // ("no_common_taxon" where the considered hits lie in two trees); --neighbors and -M are not affected.  A file error
+  // is an error of the run, and then nothing is written, the -O file included.
+  static bool has_lca();
+  void set_lca(const std::string &filestr, uint32_t top_permille, const std::string &label_file);
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
@@ -130,6 +139,7 @@ class Index {
     std::vector<uint64_t> off;
     std::vector<uint32_t> hc, hg;
     bool collapsed = false;   // hg names each label's best member: the line prints the label's text (--collapse)
+    bool lca = false;         // hg holds a taxon (NIQKI_TAXON_NONE: no common one): the line prints the taxon's text (--lca)
     // lines mode: the names are header lines of a piece of the input that stays alive until the WRITER thread has
     // taken them (name e = the line at name_base + name_at[e]); `keep` is that piece
     const uint8_t *name_base = nullptr;
@@ -142,6 +152,9 @@ class Index {
   bool collapse_ = false;                // --collapse: set_collapse has run
   std::vector<uint32_t> label_of_;      // ... per genome its label, per label its text (label_file.h)
   std::vector<std::string> label_text_;
+  bool lca_ = false;                     // --lca: set_lca has run
+  uint32_t lca_permille_ = 0;
+  std::vector<std::string> taxon_text_;  // ... per taxon its text (taxonomy_file.h)
   std::string out_text_;                // write_hits' lines before they go to the writer
   std::string out_path_;                // the -O file (remove_listed takes it away again when it refuses)
   void stream_lines(const std::string &filestr, bool insert);

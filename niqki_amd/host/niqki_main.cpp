@@ -12,6 +12,10 @@
 //   --collapse <f> f holds lines label<TAB>member (what --cluster / --derep write, or a taxonomy table): the list of
 //                  every -Q / -q query holds one entry per label, label:jaccard of the label's best member
 //                  (niqki_set_labels + niqki_staged_query_collapsed); --top bounds the labels
+//   --lca <f>      f holds lines parent<TAB>child over taxon texts whose leaves are the labels of --collapse or, without
+//                  it, the genome names: the list of every -Q / -q query holds one entry, taxon:jaccard, the lowest taxon
+//                  that contains every hit within --lca-top permille (default 100) of the best hit, and the best hit's
+//                  jaccard (niqki_set_taxonomy + niqki_staged_query_lca); "no_common_taxon" where there is none
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
 //   --mst <f> / --linkage <f> / --tree <f>   the complete single-linkage hierarchy down to the -J threshold from ONE
 //                  engine call (niqki_linkage): the maximum spanning forest, the merge table, Newick dendrograms
@@ -51,7 +55,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -93,6 +97,8 @@ const Desc kDesc[] = {
     {TREE, "", "tree", NONEMPTY, "  --tree <filename>             Single-linkage dendrograms down to the -J threshold in Newick, one tree per line."},
     {COVER, "", "cover", NONE, "  --cover                       Report each -Q / -q query's greedy cover instead of all its hits: per genome the slots no earlier line explains (--top bounds the picks)."},
     {COLLAPSE, "", "collapse", NONEMPTY, "  --collapse <filename>         Report each -Q / -q query's best hit per label instead of all its hits: the file holds lines label<TAB>member (as --cluster / --derep write them; plain or gzip), a genome no line names is its own label (--top bounds the labels)."},
+    {LCA, "", "lca", NONEMPTY, "  --lca <filename>              Report each -Q / -q query's taxon instead of all its hits: the lowest common ancestor of its near-best hits in the taxonomy of the file, lines parent<TAB>child (plain or gzip) over the labels of --collapse or, without it, the genome names; no_common_taxon where the hits share none."},
+    {LCA_TOP, "", "lca-top", NONEMPTY, "  --lca-top <permille>          With --lca: consider the hits within <permille> thousandths of the best hit's count, 0..1000 (100); 0: only ties with the best hit."},
 };
 
 struct Parsed {
@@ -337,6 +343,36 @@ int main(int argc, char *argv[]) {
     }
   }
 
+  // --lca-top: thousandths of the best count, a plain integer
+  uint32_t lca_permille = 100;
+  if (o.has(LCA_TOP)) {
+    const string &a = o.last(LCA_TOP);
+    char *end = nullptr;
+    errno = 0;
+    const long long v = strtoll(a.c_str(), &end, 10);
+    if (a.empty() || a[0] == '+' || a[0] == ' ' || end == a.c_str() || *end != 0 || errno || v < 0 || v > 1000) {
+      fprintf(stderr, "Option 'lca-top' requires an integer in 0..1000\n");
+      cout << "Bad usage!!!" << endl;
+      return EXIT_FAILURE;
+    }
+    lca_permille = (uint32_t)v;
+  }
+  // the taxon is folded on one device from whole counts
+  if (o.has(LCA)) {
+    if (n_gpus > 1) {
+      cerr << "niqki: --lca needs a single-GPU index (--gpus 1)" << endl;
+      return EXIT_FAILURE;
+    }
+    if (o.has(COVER)) {
+      cerr << "niqki: --lca and --cover both replace a query's list: choose one" << endl;
+      return EXIT_FAILURE;
+    }
+    if (!nqhost::Index::has_lca()) {
+      cerr << "niqki: this engine has no LCA query" << endl;
+      return EXIT_FAILURE;
+    }
+  }
+
   if (o.has(COLLAPSE) && o.has(COVER)) {
     cerr << "niqki: --collapse and --cover both replace a query's list: choose one" << endl;
     return EXIT_FAILURE;
@@ -358,7 +394,7 @@ int main(int argc, char *argv[]) {
   }
 
   // the collapsed list is selected on one device from whole counts
-  if (o.has(COLLAPSE)) {
+  if (o.has(COLLAPSE) && !o.has(LCA)) {   // (beside --lca the file supplies the labels only: no collapsed query runs)
     if (n_gpus > 1) {
       cerr << "niqki: --collapse needs a single-GPU index (--gpus 1)" << endl;
       return EXIT_FAILURE;
@@ -424,7 +460,8 @@ int main(int argc, char *argv[]) {
     }
     run_matrix(*ix, o, clk);
     // after everything that changes the index in memory (-M may index its list): the names are those of the final index
-    if (o.has(COLLAPSE)) ix->set_collapse(o.last(COLLAPSE));
+    if (o.has(LCA)) ix->set_lca(o.last(LCA), lca_permille, o.has(COLLAPSE) ? o.last(COLLAPSE) : string());
+    else if (o.has(COLLAPSE)) ix->set_collapse(o.last(COLLAPSE));
     if (o.has(NEIGHBORS)) ix->query_neighbors();
     for (const Phase &ph : kQueryPhases) run_phase(*ix, o, ph);
     ix->outfile->close();
