@@ -381,9 +381,9 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_hitoff, &ix->ws_hc, &ix->ws_hg, &ix->ws_tc, &ix->ws_tg, &ix->ws_misc, &ix->ws_stash,
                  &ix->ws_raw, &ix->ws_wire[0], &ix->ws_wire[1], &ix->ws_redo[0], &ix->ws_redo[1], &ix->ws_fmeta, &ix->ws_summ, &ix->ws_chunk, &ix->ws_fkept, &ix->ws_fnrec,
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
-                 &ix->ws_cv_orig, &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
+                 &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
                  &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info,
-                 &ix->lab_dense, &ix->ws_cl_sk, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
+                 &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -562,6 +562,67 @@ int niqki_reserve(niqki_index *ix, uint32_t n_genomes) {
   return reserve_store(ix, n_genomes);
 }
 
+namespace {
+uint64_t us(double ms) { return (uint64_t)(ms * 1000.0); }   // a phase time, kept in milliseconds, as microseconds
+
+// The stats of the last call of each kind that consumes full hit lists.  The *_us_* phases and the *_pairs of cluster and
+// derep are those of a call made while profiling was on (niqki_profile_enable).
+struct StatKey {
+  const char *key;
+  uint64_t (*get)(const niqki_index *ix);
+};
+#define NQ_STAT(key, expr) {key, [](const niqki_index *ix) -> uint64_t { return expr; }}
+const StatKey kCallStats[] = {
+    // niqki_cluster
+    NQ_STAT("cluster_splits", ix->cluster_stats.splits),
+    NQ_STAT("cluster_us_read", us(ix->cluster_stats.ms[0])),
+    NQ_STAT("cluster_us_hits", us(ix->cluster_stats.ms[1])),
+    NQ_STAT("cluster_us_link", us(ix->cluster_stats.ms[2])),
+    NQ_STAT("cluster_us_flatten", us(ix->cluster_stats.ms[3])),
+    NQ_STAT("cluster_pairs", ix->cluster_stats.pairs),
+    // niqki_dereplicate
+    NQ_STAT("derep_rounds", ix->derep_stats.rounds),
+    NQ_STAT("derep_splits", ix->derep_stats.splits),
+    NQ_STAT("derep_us_read", us(ix->derep_stats.ms[0])),
+    NQ_STAT("derep_us_hits", us(ix->derep_stats.ms[1])),
+    NQ_STAT("derep_us_decide", us(ix->derep_stats.ms[2])),
+    NQ_STAT("derep_us_assign", us(ix->derep_stats.ms[3])),
+    NQ_STAT("derep_pairs", ix->derep_stats.pairs),
+    // niqki_linkage
+    NQ_STAT("linkage_rounds", ix->linkage_stats.rounds),
+    NQ_STAT("linkage_splits", ix->linkage_stats.splits),
+    NQ_STAT("linkage_us_read", us(ix->linkage_stats.ms[0])),
+    NQ_STAT("linkage_us_hits", us(ix->linkage_stats.ms[1])),
+    NQ_STAT("linkage_us_forest", us(ix->linkage_stats.ms[2])),
+    NQ_STAT("linkage_us_finish", us(ix->linkage_stats.ms[3])),
+    NQ_STAT("linkage_pairs", ix->linkage_stats.pairs),
+    // niqki_cover / niqki_staged_cover
+    NQ_STAT("cover_rounds", ix->cover_stats.rounds),
+    NQ_STAT("cover_picks", ix->cover_stats.picks),
+    NQ_STAT("cover_recount_mismatches", ix->cover_stats.mismatches),
+    NQ_STAT("cover_us_hits", us(ix->cover_stats.ms[0])),
+    NQ_STAT("cover_us_pick", us(ix->cover_stats.ms[1])),
+    NQ_STAT("cover_us_compact", us(ix->cover_stats.ms[2])),
+    NQ_STAT("cover_us_finish", us(ix->cover_stats.ms[3])),
+    // niqki_set_labels; niqki_query_collapsed / niqki_staged_query_collapsed
+    NQ_STAT("labels", ix->labels_set ? ix->n_labels : 0),
+    NQ_STAT("collapse_splits", ix->collapse_stats.splits),
+    NQ_STAT("collapse_long_lists", ix->collapse_stats.long_lists),
+    NQ_STAT("collapse_us_hits", us(ix->collapse_stats.ms[0])),
+    NQ_STAT("collapse_us_first", us(ix->collapse_stats.ms[1])),
+    NQ_STAT("collapse_us_emit", us(ix->collapse_stats.ms[2])),
+    // niqki_set_taxonomy; niqki_query_lca / niqki_staged_query_lca
+    NQ_STAT("taxa", ix->tax_set ? ix->n_taxa : 0),
+    NQ_STAT("taxonomy_depth", ix->tax_set ? ix->tax_depth : 0),
+    NQ_STAT("lca_splits", ix->lca_stats.splits),
+    NQ_STAT("lca_long_lists", ix->lca_stats.long_lists),
+    NQ_STAT("lca_no_common", ix->lca_stats.no_common),
+    NQ_STAT("lca_us_hits", us(ix->lca_stats.ms[0])),
+    NQ_STAT("lca_us_fold", us(ix->lca_stats.ms[1])),
+};
+#undef NQ_STAT
+}  // namespace
+
 int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!ix || !key || !value) return NIQKI_E_INVALID;
   const uint32_t f_all = ix->resident_bytes ? ix->full_end - ix->full_begin : ix->d.slot_end - ix->d.slot_begin;
@@ -574,55 +635,11 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "last_gather_kernel")) { *value = ix->last_kernel; return NIQKI_OK; }
   if (!std::strcmp(key, "bucket_align_log2")) { *value = ix->align_log2; return NIQKI_OK; }
   if (!std::strcmp(key, "last_hits_form")) { *value = ix->last_hits_form; return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_splits")) { *value = ix->cluster_stats.splits; return NIQKI_OK; }
-  // the last niqki_cluster call while profiling was on (niqki_profile_enable): microseconds per phase, hits linked
-  if (!std::strcmp(key, "cluster_us_read")) { *value = (uint64_t)(ix->cluster_stats.ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_us_hits")) { *value = (uint64_t)(ix->cluster_stats.ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_us_link")) { *value = (uint64_t)(ix->cluster_stats.ms[2] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_us_flatten")) { *value = (uint64_t)(ix->cluster_stats.ms[3] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cluster_pairs")) { *value = ix->cluster_stats.pairs; return NIQKI_OK; }
-  // the last niqki_dereplicate call; the phases and the hits while profiling was on
-  if (!std::strcmp(key, "derep_rounds")) { *value = ix->derep_stats.rounds; return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_splits")) { *value = ix->derep_stats.splits; return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_read")) { *value = (uint64_t)(ix->derep_stats.ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_hits")) { *value = (uint64_t)(ix->derep_stats.ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_decide")) { *value = (uint64_t)(ix->derep_stats.ms[2] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_us_assign")) { *value = (uint64_t)(ix->derep_stats.ms[3] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "derep_pairs")) { *value = ix->derep_stats.pairs; return NIQKI_OK; }
-  // the last niqki_linkage call; the phases and the hits while profiling was on
-  if (!std::strcmp(key, "linkage_rounds")) { *value = ix->linkage_stats.rounds; return NIQKI_OK; }
-  if (!std::strcmp(key, "linkage_splits")) { *value = ix->linkage_stats.splits; return NIQKI_OK; }
-  if (!std::strcmp(key, "linkage_us_read")) { *value = (uint64_t)(ix->linkage_stats.ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "linkage_us_hits")) { *value = (uint64_t)(ix->linkage_stats.ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "linkage_us_forest")) { *value = (uint64_t)(ix->linkage_stats.ms[2] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "linkage_us_finish")) { *value = (uint64_t)(ix->linkage_stats.ms[3] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "linkage_pairs")) { *value = ix->linkage_stats.pairs; return NIQKI_OK; }
-  // the last niqki_cover / niqki_staged_cover call; the phases while profiling was on
-  if (!std::strcmp(key, "cover_rounds")) { *value = ix->cover_stats.rounds; return NIQKI_OK; }
-  if (!std::strcmp(key, "cover_picks")) { *value = ix->cover_stats.picks; return NIQKI_OK; }
-  if (!std::strcmp(key, "cover_recount_mismatches")) { *value = ix->cover_stats.mismatches; return NIQKI_OK; }
-  if (!std::strcmp(key, "cover_us_hits")) { *value = (uint64_t)(ix->cover_stats.ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cover_us_pick")) { *value = (uint64_t)(ix->cover_stats.ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cover_us_compact")) { *value = (uint64_t)(ix->cover_stats.ms[2] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "cover_us_finish")) { *value = (uint64_t)(ix->cover_stats.ms[3] * 1000.0); return NIQKI_OK; }
-  // niqki_set_labels; the last niqki_query_collapsed / niqki_staged_query_collapsed call; its phases while profiling was on
-  if (!std::strcmp(key, "labels")) { *value = ix->labels_set ? ix->n_labels : 0; return NIQKI_OK; }
-  if (!std::strcmp(key, "collapse_splits")) { *value = ix->collapse_stats.splits; return NIQKI_OK; }
-  if (!std::strcmp(key, "collapse_long_lists")) { *value = ix->collapse_stats.long_lists; return NIQKI_OK; }
-  if (!std::strcmp(key, "collapse_us_hits")) { *value = (uint64_t)(ix->collapse_stats.ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "collapse_us_first")) { *value = (uint64_t)(ix->collapse_stats.ms[1] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "collapse_us_emit")) { *value = (uint64_t)(ix->collapse_stats.ms[2] * 1000.0); return NIQKI_OK; }
-  // niqki_set_taxonomy; the last niqki_query_lca / niqki_staged_query_lca call; its phases while profiling was on
-  if (!std::strcmp(key, "taxa")) { *value = ix->tax_set ? ix->n_taxa : 0; return NIQKI_OK; }
-  if (!std::strcmp(key, "taxonomy_depth")) { *value = ix->tax_set ? ix->tax_depth : 0; return NIQKI_OK; }
-  if (!std::strcmp(key, "lca_splits")) { *value = ix->lca_stats.splits; return NIQKI_OK; }
-  if (!std::strcmp(key, "lca_long_lists")) { *value = ix->lca_stats.long_lists; return NIQKI_OK; }
-  if (!std::strcmp(key, "lca_no_common")) { *value = ix->lca_stats.no_common; return NIQKI_OK; }
-  if (!std::strcmp(key, "lca_us_hits")) { *value = (uint64_t)(ix->lca_stats.ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "lca_us_fold")) { *value = (uint64_t)(ix->lca_stats.ms[1] * 1000.0); return NIQKI_OK; }
+  for (const StatKey &s : kCallStats)
+    if (!std::strcmp(key, s.key)) { *value = s.get(ix); return NIQKI_OK; }
   // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
-  if (!std::strcmp(key, "retain_us_rank")) { *value = (uint64_t)(ix->retain_ms[0] * 1000.0); return NIQKI_OK; }
-  if (!std::strcmp(key, "retain_us_compact")) { *value = (uint64_t)(ix->retain_ms[1] * 1000.0); return NIQKI_OK; }
+  if (!std::strcmp(key, "retain_us_rank")) { *value = us(ix->retain_ms[0]); return NIQKI_OK; }
+  if (!std::strcmp(key, "retain_us_compact")) { *value = us(ix->retain_ms[1]); return NIQKI_OK; }
   if (!std::strcmp(key, "inflate_files_in_flight") || !std::strcmp(key, "inflate_files_in_flight_8k")) {
     // how many files a launch of the device inflate runs at once (workgroups the device keeps resident), by kernel form
     (void)hipSetDevice(ix->device);

@@ -18,91 +18,21 @@ void drop_labels(niqki_index *ix) {
 
 namespace {
 
-// The query path at the handle's threshold and no top-k; the handle's own values come back whatever happens.
-struct CollapseCall {
-  niqki_index *ix;
-  const uint32_t ms, pms, k;
-  explicit CollapseCall(niqki_index *ix_) : ix(ix_), ms(ix_->d.min_score), pms(ix_->p.min_score), k(ix_->p.top_k) { ix->p.top_k = 0; }
-  ~CollapseCall() {
-    ix->d.min_score = ms;
-    ix->p.min_score = pms;
-    ix->p.top_k = k;
-  }
-};
-
-// events of a leaf while the handle is profiling: 0-1 hits, 1-2 first, 2-3 scan + emit
-struct CollapseEvents {
-  niqki_index *ix;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  explicit CollapseEvents(niqki_index *ix_) : ix(ix_) {}
-  ~CollapseEvents() {
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  int create() {
-    if (ix->prof) for (auto &e : ev) NQ_HIP(ix, hipEventCreate(&e));
-    return NIQKI_OK;
-  }
-  int mark(int k) {
-    if (ix->prof) NQ_HIP(ix, hipEventRecord(ev[k], ix->stream));
-    return NIQKI_OK;
-  }
-  int add(int a, int b, int to) {
-    if (!ix->prof) return NIQKI_OK;
-    float ms = 0;
-    NQ_HIP(ix, hipEventSynchronize(ev[b]));
-    NQ_HIP(ix, hipEventElapsedTime(&ms, ev[a], ev[b]));
-    ix->collapse_stats.ms[to] += ms;
-    return NIQKI_OK;
-  }
-};
-
 struct Collapse {
   niqki_index *ix;
-  CollapseEvents ev;
+  PhaseTimer ev;            // events of a leaf: 0-1 hits, 1-2 first, 2-3 scan + emit
   uint32_t k = 0;           // the handle's top_k: the cut of every list
-  uint64_t stride = 0, room = 0;
   uint32_t n_tables = 0;    // global tables in ws_cl_tab (0: no list can be long)
   uint64_t staged = 0;      // entries of the current batch in ws_cl_stage
-  explicit Collapse(niqki_index *ix_) : ix(ix_), ev(ix_) {}
+  explicit Collapse(niqki_index *ix_) : ix(ix_), ev(ix_, 4, ix_->collapse_stats.ms) {}
 };
 
-// room for `entries` collapsed entries, the first `keep` of them kept
-int grow_stage(niqki_index *ix, uint64_t keep, uint64_t entries) {
-  Buf &b = ix->ws_cl_stage;
-  const size_t need = (size_t)std::max<uint64_t>(entries, 1) * sizeof(nq::CollapsedHit);
-  if (need <= b.n && b.p) return NIQKI_OK;
-  if (!keep) return ensure(ix, b, need);
-  Buf nb;
-  int rc = ensure(ix, nb, need * 2);
-  if (rc) return rc;
-  NQ_HIP(ix, hipMemcpyAsync(nb.p, b.p, (size_t)keep * sizeof(nq::CollapsedHit), hipMemcpyDeviceToDevice, ix->stream));
-  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
-  NQ_HIP(ix, hipFree(b.p));
-  b = nb;
-  return NIQKI_OK;
-}
-
-// Queries [q_at, q_at + n) of the batch, their sketches at d_sk: full lists into the fixed hit buffers, the first-of-
-// label flags, the kept counts into ws_cl_nk[q_at ...), the kept entries behind the batch's earlier ones in ws_cl_stage.
-// A leaf whose full lists exceed the room is halved (the rule of self_join_batch), the first half before the second:
-// the stage fills in query order.
-int collapse_leaf(Collapse &c, const int32_t *d_sk, uint32_t q_at, uint32_t n) {
+// The consumer of a leaf (HitLists): the full lists `out` of queries [q_at, q_at + n) of the batch; the first-of-label
+// flags, the kept counts into ws_cl_nk[q_at ...), the kept entries behind the batch's earlier ones in ws_cl_stage.  A
+// halved leaf finishes its first half before its second, so the stage fills in query order.
+int collapse_consume(Collapse &c, const HitOut &out, uint32_t q_at, uint32_t n) {
   niqki_index *ix = c.ix;
   int rc;
-  Planes pl;
-  HitOut out;
-  if ((rc = counter_planes(ix, n, c.stride, pl))) return rc;
-  if ((rc = hit_out_ws(ix, n, c.room, out))) return rc;
-  if ((rc = c.ev.mark(0))) return rc;
-  rc = query_hits_dev(ix, d_sk, n, pl, c.stride, out);
-  if (rc == NIQKI_E_CAPACITY) {
-    if (n == 1) return fail(ix, NIQKI_E_STATE, "niqki_query_collapsed: one query's hits exceed the genome count");   // (room >= N)
-    ix->collapse_stats.splits += 1;
-    const uint32_t h = n / 2;
-    if ((rc = collapse_leaf(c, d_sk, q_at, h))) return rc;
-    return collapse_leaf(c, d_sk + (size_t)h * ix->d.F, q_at + h, n - h);
-  }
-  if (rc) return rc;
   if ((rc = c.ev.mark(1))) return rc;
   // off[n + 1] of the leaf's kept entries, then the info words: one copy brings the total and the words back
   const size_t off_bytes = ((size_t)n + 1) * 8;
@@ -138,7 +68,8 @@ int collapse_leaf(Collapse &c, const int32_t *d_sk, uint32_t q_at, uint32_t n) {
   if (h.info[nq::kCollapseInfoBad] || h.total > out.total)
     return fail(ix, NIQKI_E_STATE, "niqki_query_collapsed: a hit no label table could take (a bug)");
   ix->collapse_stats.long_lists += h.info[nq::kCollapseInfoLong];
-  if ((rc = grow_stage(ix, c.staged, c.staged + h.total))) return rc;
+  const size_t entry = sizeof(nq::CollapsedHit);
+  if ((rc = ensure_keep(ix, ix->ws_cl_stage, (size_t)c.staged * entry, (size_t)std::max<uint64_t>(c.staged + h.total, 1) * entry))) return rc;
   NQ_HIP(ix, nq::launch_collapse_emit(out.off, out.counts, out.gids, a.kept, nk, d_off, n, (nq::CollapsedHit *)ix->ws_cl_stage.p + c.staged,
                                       ix->stream));
   if ((rc = c.ev.mark(3))) return rc;
@@ -166,12 +97,12 @@ int collapse_tables(Collapse &c, uint32_t batch) {
   return NIQKI_OK;
 }
 
-int collapse_run(niqki_index *ix, const char *who, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint64_t *hit_off,
-                 uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_members, uint64_t capacity, int mem) {
+int collapse_run(niqki_index *ix, const char *who, const SketchSource &src, uint32_t nq, uint64_t *hit_off, uint32_t *hit_counts,
+                 uint32_t *hit_gids, uint32_t *hit_members, uint64_t capacity, int mem) {
   ix->collapse_stats = CollapseStats();
   if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, std::string(who) + ": a slot-range shard sees partial counts; the collapsed query needs a whole-range handle");
   const bool dev = mem == NIQKI_MEM_DEVICE;
-  const uint32_t N = ix->n_genomes, F = ix->d.F;
+  const uint32_t N = ix->n_genomes;
   if (N && !ix->labels_set)
     return fail(ix, NIQKI_E_STATE, std::string(who) + ": no labels on this genome set: call niqki_set_labels (again, after genomes were added or dropped)");
   if (nq == 0 || N == 0) {
@@ -179,14 +110,11 @@ int collapse_run(niqki_index *ix, const char *who, const int32_t *d_sketches, co
     else std::fill(hit_off, hit_off + nq + 1, (uint64_t)0);
     return NIQKI_OK;
   }
-  CollapseCall guard(ix);
+  CallParams guard(ix, ix->d.min_score, 0);   // the query path at the handle's threshold and no top-k
   int rc = build_if_needed(ix);
   if (rc) return rc;
   Collapse c(ix);
   c.k = guard.k;
-  c.stride = NIQKI_ROW_STRIDE(N);
-  // the hit buffers of the self-join calls: 16 bytes a hit, never below N, the hits of one query
-  c.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
   if ((rc = c.ev.create())) return rc;
   const uint32_t qb = dev ? nq : std::max<uint32_t>(ix->query_batch, 1);
   if ((rc = collapse_tables(c, std::min(qb, nq)))) return rc;
@@ -195,23 +123,16 @@ int collapse_run(niqki_index *ix, const char *who, const int32_t *d_sketches, co
   std::vector<uint32_t> h_nk;
   if (!dev) h_nk.resize(nq);
   uint64_t base = 0;
-  for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
-    const uint32_t n = std::min(qb, nq - q0);
-    const int32_t *d_orig = d_sketches ? d_sketches + (size_t)q0 * F : nullptr;
-    if (!d_orig) {
-      if ((rc = ensure(ix, ix->ws_cl_sk, (size_t)n * F * 4))) return rc;
-      NQ_HIP(ix, hipMemcpyAsync(ix->ws_cl_sk.p, h_sketches + (size_t)q0 * F, (size_t)n * F * 4, hipMemcpyHostToDevice, ix->stream));
-      d_orig = (const int32_t *)ix->ws_cl_sk.p;
-    }
-    c.staged = 0;
-    if ((rc = collapse_leaf(c, d_orig, 0, n))) return rc;
+  HitLists hl{ix, "niqki_query_collapsed", c.ev, 0, ix->collapse_stats.splits, false};
+  hl.consume = [&](const HitOut &out, const int32_t *, uint32_t q_at, uint32_t n) { return collapse_consume(c, out, q_at, n); };
+  hl.after = [&](uint32_t q0, uint32_t n) {
     const nq::CollapsedHit *stage = (const nq::CollapsedHit *)ix->ws_cl_stage.p;
     if (dev) {   // one batch: the offsets in any case, the entries where the caller's arrays hold them
       NQ_HIP(ix, nq::launch_collapse_scan((const uint32_t *)ix->ws_cl_nk.p, n, (unsigned long long *)hit_off, ix->stream));
       if (c.n_tables) ix->cl_tab_clean = true;   // (every launch left them cleared)
-      if (c.staged > capacity) return NIQKI_E_CAPACITY;
+      if (c.staged > capacity) return (int)NIQKI_E_CAPACITY;
       NQ_HIP(ix, nq::launch_collapse_unpack(stage, c.staged, hit_counts, hit_gids, hit_members, ix->stream));
-      return NIQKI_OK;
+      return (int)NIQKI_OK;
     }
     // host arrays: nothing reaches the caller's arrays before the total is known
     h_hits.resize(base + c.staged);
@@ -220,7 +141,10 @@ int collapse_run(niqki_index *ix, const char *who, const int32_t *d_sketches, co
       NQ_HIP(ix, hipMemcpyAsync(h_hits.data() + base, stage, (size_t)c.staged * sizeof(nq::CollapsedHit), hipMemcpyDeviceToHost, ix->stream));
     NQ_HIP(ix, hipStreamSynchronize(ix->stream));
     base += c.staged;
-  }
+    c.staged = 0;   // (the next batch fills the stage from its start)
+    return (int)NIQKI_OK;
+  };
+  if ((rc = hl.run(src, nq, qb)) || dev) return rc;
   if (c.n_tables) ix->cl_tab_clean = true;   // (every launch left them cleared)
   hit_off[0] = 0;
   for (uint32_t q = 0; q < nq; ++q) hit_off[q + 1] = hit_off[q] + h_nk[q];
@@ -233,6 +157,7 @@ int collapse_run(niqki_index *ix, const char *who, const int32_t *d_sketches, co
   }
   return NIQKI_OK;
 }
+
 
 }  // namespace
 
@@ -276,9 +201,8 @@ int niqki_query_collapsed(niqki_index *ix, const int32_t *sketches, uint32_t nq,
                           uint32_t *hit_members, uint64_t capacity, int mem) {
   if (!ix || !hit_off || (!sketches && nq) || (capacity && (!hit_counts || !hit_gids))) return NIQKI_E_INVALID;
   NQ_HIP(ix, hipSetDevice(ix->device));
-  const bool dev = mem == NIQKI_MEM_DEVICE;
-  return collapse_run(ix, "niqki_query_collapsed", dev ? sketches : nullptr, dev ? nullptr : sketches, nq, hit_off, hit_counts, hit_gids,
-                      hit_members, capacity, mem);
+  return collapse_run(ix, "niqki_query_collapsed", mem == NIQKI_MEM_DEVICE ? device_rows(ix, sketches) : host_rows(ix, sketches), nq, hit_off,
+                      hit_counts, hit_gids, hit_members, capacity, mem);
 }
 
 int niqki_staged_query_collapsed(niqki_index *ix, uint64_t *hit_off, uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_members,
@@ -288,8 +212,8 @@ int niqki_staged_query_collapsed(niqki_index *ix, uint64_t *hit_off, uint32_t *h
   int rc = staged_sketch_ws(ix);
   if (rc) return rc;
   // (the staged sketches are only read, so niqki_staged_query answers as before)
-  return collapse_run(ix, "niqki_staged_query_collapsed", (const int32_t *)ix->ws_stsk.p, nullptr, ix->staged.n_entry, hit_off, hit_counts,
-                      hit_gids, hit_members, capacity, mem);
+  return collapse_run(ix, "niqki_staged_query_collapsed", device_rows(ix, (const int32_t *)ix->ws_stsk.p), ix->staged.n_entry, hit_off,
+                      hit_counts, hit_gids, hit_members, capacity, mem);
 }
 
 }  // extern "C"

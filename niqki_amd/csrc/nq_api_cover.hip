@@ -13,69 +13,9 @@ namespace nqi {
 
 namespace {
 
-// The query path at the handle's threshold raised to at least 1 and top_k = 1; the handle's own values come back
-// whatever happens.
-struct CoverCall {
-  niqki_index *ix;
-  const uint32_t ms, pms, k;
-  explicit CoverCall(niqki_index *ix_) : ix(ix_), ms(ix_->d.min_score), pms(ix_->p.min_score), k(ix_->p.top_k) {
-    ix->d.min_score = std::max(ms, 1u);
-    ix->p.min_score = ix->d.min_score;
-    ix->p.top_k = 1;
-  }
-  ~CoverCall() {
-    ix->d.min_score = ms;
-    ix->p.min_score = pms;
-    ix->p.top_k = k;
-  }
-};
-
-// events of a batch while the handle is profiling: 0-1 hits, 1-2 pick, 2-3 compact scan, 4-5 compact, 6-7 finish
-struct CoverEvents {
-  niqki_index *ix;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  explicit CoverEvents(niqki_index *ix_) : ix(ix_) {}
-  ~CoverEvents() {
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  int create() {
-    if (ix->prof) for (auto &e : ev) NQ_HIP(ix, hipEventCreate(&e));
-    return NIQKI_OK;
-  }
-  int mark(int k) {
-    if (ix->prof) NQ_HIP(ix, hipEventRecord(ev[k], ix->stream));
-    return NIQKI_OK;
-  }
-  // the span a .. b, finished, into phase `to` of the call's stats
-  int add(int a, int b, int to) {
-    if (!ix->prof) return NIQKI_OK;
-    float ms = 0;
-    NQ_HIP(ix, hipEventSynchronize(ev[b]));
-    NQ_HIP(ix, hipEventElapsedTime(&ms, ev[a], ev[b]));
-    ix->cover_stats.ms[to] += ms;
-    return NIQKI_OK;
-  }
-};
-
-// room for `entries` log entries, the first `keep` of them kept
-int grow_log(niqki_index *ix, uint64_t keep, uint64_t entries) {
-  Buf &b = ix->ws_cv_log;
-  const size_t need = (size_t)entries * sizeof(nq::CoverPick);
-  if (need <= b.n && b.p) return NIQKI_OK;
-  if (!keep) return ensure(ix, b, need);
-  Buf nb;
-  int rc = ensure(ix, nb, need * 2);
-  if (rc) return rc;
-  NQ_HIP(ix, hipMemcpyAsync(nb.p, b.p, (size_t)keep * sizeof(nq::CoverPick), hipMemcpyDeviceToDevice, ix->stream));
-  NQ_HIP(ix, hipStreamSynchronize(ix->stream));
-  NQ_HIP(ix, hipFree(b.p));
-  b = nb;
-  return NIQKI_OK;
-}
-
 // The rounds of one batch: n queries whose sketches as given lie at d_orig.  Leaves the pick log (*n_log entries in
 // ws_cv_log) and the per-query pick counts (*n_picks, device) and returns the batch's picks.
-int cover_rounds(niqki_index *ix, const int32_t *d_orig, uint32_t n, uint32_t max_picks, uint32_t bound, CoverEvents &ev, uint64_t *n_log,
+int cover_rounds(niqki_index *ix, const int32_t *d_orig, uint32_t n, uint32_t max_picks, uint32_t bound, PhaseTimer &ev, uint64_t *n_log,
                  uint64_t *picks, const uint32_t **n_picks) {
   const uint32_t F = ix->d.F, N = ix->n_genomes;
   const uint64_t stride = NIQKI_ROW_STRIDE(ix->built_n);
@@ -98,7 +38,7 @@ int cover_rounds(niqki_index *ix, const int32_t *d_orig, uint32_t n, uint32_t ma
   while (active) {
     if (round >= bound) return fail(ix, NIQKI_E_STATE, "niqki_cover: more rounds than a cover can have picks (a bug)");
     round += 1;
-    if ((rc = grow_log(ix, *n_log, *n_log + active))) return rc;
+    if ((rc = ensure_keep(ix, ix->ws_cv_log, (size_t)*n_log * sizeof(nq::CoverPick), (size_t)(*n_log + active) * sizeof(nq::CoverPick)))) return rc;
     Planes pl;
     HitOut out;
     if ((rc = counter_planes(ix, active, stride, pl))) return rc;
@@ -153,10 +93,9 @@ int cover_rounds(niqki_index *ix, const int32_t *d_orig, uint32_t n, uint32_t ma
   return NIQKI_OK;
 }
 
-}  // namespace
-
-int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint32_t max_picks, uint64_t *hit_off,
-              uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem) {
+// the greedy cover of the nq whole sketches of src (niqki_hip.h); the outputs in host or device memory
+int cover_run(niqki_index *ix, const SketchSource &src, uint32_t nq, uint32_t max_picks, uint64_t *hit_off, uint32_t *hit_counts,
+              uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem) {
   ix->cover_stats = CoverStats();
   if (ix->resident_bytes) return fail(ix, NIQKI_E_STATE, "niqki_cover: not on a paged index (resident_bytes): its sketch store is host memory");
   if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, "niqki_cover: a slot-range shard sees partial counts; the cover needs a whole-range handle");
@@ -169,11 +108,13 @@ int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketc
     else std::fill(hit_off, hit_off + nq + 1, (uint64_t)0);
     return NIQKI_OK;
   }
-  CoverCall guard(ix);
+  // the query path at the handle's threshold raised to at least 1 and top_k = 1
+  CallParams guard(ix, std::max(ix->d.min_score, 1u), 1);
   uint32_t bound = std::min(N, F / ix->d.min_score);
   if (max_picks) bound = std::min(bound, max_picks);
   bound += 1;
-  CoverEvents ev(ix);
+  // events of a batch: 0-1 hits, 1-2 pick, 2-3 compact scan, 4-5 compact, 6-7 finish
+  PhaseTimer ev(ix, 8, ix->cover_stats.ms);
   if ((rc = ev.create())) return rc;
   const uint32_t qb = dev ? nq : std::max<uint32_t>(ix->query_batch, 1);
   std::vector<uint32_t> hc, hg, ht;
@@ -181,12 +122,8 @@ int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketc
   uint64_t base = 0;
   for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
     const uint32_t n = std::min(qb, nq - q0);
-    const int32_t *d_orig = d_sketches ? d_sketches + (size_t)q0 * F : nullptr;
-    if (!d_orig) {
-      if ((rc = ensure(ix, ix->ws_cv_orig, (size_t)n * F * 4))) return rc;
-      NQ_HIP(ix, hipMemcpyAsync(ix->ws_cv_orig.p, h_sketches + (size_t)q0 * F, (size_t)n * F * 4, hipMemcpyHostToDevice, ix->stream));
-      d_orig = (const int32_t *)ix->ws_cv_orig.p;
-    }
+    const int32_t *d_orig = nullptr;
+    if ((rc = src(q0, n, &d_orig))) return rc;
     uint64_t n_log = 0, picks = 0;
     const uint32_t *npk = nullptr;
     if ((rc = cover_rounds(ix, d_orig, n, max_picks, bound, ev, &n_log, &picks, &npk))) return rc;
@@ -230,6 +167,8 @@ int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketc
   return NIQKI_OK;
 }
 
+}  // namespace
+
 }  // namespace nqi
 
 using namespace nqi;
@@ -240,8 +179,8 @@ int niqki_cover(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint32_t 
                 uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem) {
   if (!ix || !hit_off || (!sketches && nq) || (capacity && (!hit_counts || !hit_gids))) return NIQKI_E_INVALID;
   NQ_HIP(ix, hipSetDevice(ix->device));
-  const bool dev = mem == NIQKI_MEM_DEVICE;
-  return cover_run(ix, dev ? sketches : nullptr, dev ? nullptr : sketches, nq, max_picks, hit_off, hit_counts, hit_gids, hit_totals, capacity, mem);
+  return cover_run(ix, mem == NIQKI_MEM_DEVICE ? device_rows(ix, sketches) : host_rows(ix, sketches), nq, max_picks, hit_off, hit_counts, hit_gids,
+                   hit_totals, capacity, mem);
 }
 
 int niqki_staged_cover(niqki_index *ix, uint32_t max_picks, uint64_t *hit_off, uint32_t *hit_counts, uint32_t *hit_gids,
@@ -251,7 +190,8 @@ int niqki_staged_cover(niqki_index *ix, uint32_t max_picks, uint64_t *hit_off, u
   int rc = staged_sketch_ws(ix);
   if (rc) return rc;
   // (the staged sketches are only read: the rounds work on copies, so niqki_staged_query answers as before)
-  return cover_run(ix, (const int32_t *)ix->ws_stsk.p, nullptr, ix->staged.n_entry, max_picks, hit_off, hit_counts, hit_gids, hit_totals, capacity, mem);
+  return cover_run(ix, device_rows(ix, (const int32_t *)ix->ws_stsk.p), ix->staged.n_entry, max_picks, hit_off, hit_counts, hit_gids, hit_totals,
+                   capacity, mem);
 }
 
 }  // extern "C"

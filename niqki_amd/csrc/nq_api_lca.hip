@@ -19,79 +19,24 @@ void drop_taxonomy(niqki_index *ix) {
 
 namespace {
 
-// The query path at the handle's threshold and no top-k; the handle's own values come back whatever happens.
-struct LcaCall {
-  niqki_index *ix;
-  const uint32_t ms, pms, k;
-  explicit LcaCall(niqki_index *ix_) : ix(ix_), ms(ix_->d.min_score), pms(ix_->p.min_score), k(ix_->p.top_k) { ix->p.top_k = 0; }
-  ~LcaCall() {
-    ix->d.min_score = ms;
-    ix->p.min_score = pms;
-    ix->p.top_k = k;
-  }
-};
-
-// events of a leaf while the handle is profiling: 0-1 hits, 1-2 fold
-struct LcaEvents {
-  niqki_index *ix;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  explicit LcaEvents(niqki_index *ix_) : ix(ix_) {}
-  ~LcaEvents() {
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  int create() {
-    if (ix->prof) for (auto &e : ev) NQ_HIP(ix, hipEventCreate(&e));
-    return NIQKI_OK;
-  }
-  int mark(int k) {
-    if (ix->prof) NQ_HIP(ix, hipEventRecord(ev[k], ix->stream));
-    return NIQKI_OK;
-  }
-  int add(int a, int b, int to) {
-    if (!ix->prof) return NIQKI_OK;
-    float ms = 0;
-    NQ_HIP(ix, hipEventSynchronize(ev[b]));
-    NQ_HIP(ix, hipEventElapsedTime(&ms, ev[a], ev[b]));
-    ix->lca_stats.ms[to] += ms;
-    return NIQKI_OK;
-  }
-};
-
 struct Lca {
   niqki_index *ix;
-  LcaEvents ev;
-  const char *who = "";
+  PhaseTimer ev;   // events of a leaf: 0-1 hits, 1-2 fold
   uint32_t top_permille = 0;
-  uint64_t stride = 0, room = 0;
   uint32_t *out[4] = {nullptr, nullptr, nullptr, nullptr};   // device rows of the batch: taxon, best_count, best_gid, considered
-  explicit Lca(niqki_index *ix_) : ix(ix_), ev(ix_) {}
+  explicit Lca(niqki_index *ix_) : ix(ix_), ev(ix_, 3, ix_->lca_stats.ms) {}
 };
 
-// Queries [q_at, q_at + n) of the batch, their sketches at d_sk: full lists into the fixed hit buffers, then one launch
-// that writes the leaf's result rows at q_at.  A leaf whose full lists exceed the room is halved (the rule of
-// self_join_batch), the first half before the second.
-int lca_leaf(Lca &c, const int32_t *d_sk, uint32_t q_at, uint32_t n) {
+// The consumer of a leaf (HitLists): the full lists `hits` of queries [q_at, q_at + n) of the batch; one launch that
+// writes the leaf's result rows at q_at.
+int lca_consume(Lca &c, const HitOut &hits, uint32_t q_at, uint32_t n) {
   niqki_index *ix = c.ix;
   int rc;
-  Planes pl;
-  HitOut out;
-  if ((rc = counter_planes(ix, n, c.stride, pl))) return rc;
-  if ((rc = hit_out_ws(ix, n, c.room, out))) return rc;
-  if ((rc = c.ev.mark(0))) return rc;
-  rc = query_hits_dev(ix, d_sk, n, pl, c.stride, out);
-  if (rc == NIQKI_E_CAPACITY) {
-    if (n == 1) return fail(ix, NIQKI_E_STATE, std::string(c.who) + ": one query's hits exceed the genome count");   // (room >= N)
-    ix->lca_stats.splits += 1;
-    const uint32_t h = n / 2;
-    if ((rc = lca_leaf(c, d_sk, q_at, h))) return rc;
-    return lca_leaf(c, d_sk + (size_t)h * ix->d.F, q_at + h, n - h);
-  }
-  if (rc) return rc;
   if ((rc = c.ev.mark(1))) return rc;
   nq::LcaArgs a{};
-  a.hit_off = out.off;
-  a.hit_counts = out.counts;
-  a.hit_gids = out.gids;
+  a.hit_off = hits.off;
+  a.hit_counts = hits.counts;
+  a.hit_gids = hits.gids;
   a.nodes = (const nq::TaxNode *)ix->tax_nodes.p;
   a.genome_taxon = (const uint32_t *)ix->tax_genome.p;
   a.n_genomes = ix->n_genomes;
@@ -122,26 +67,22 @@ int lca_no_hit(niqki_index *ix, uint32_t *const out[4], uint32_t n, bool dev) {
   return NIQKI_OK;
 }
 
-int lca_run(niqki_index *ix, const char *who, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint32_t top_permille,
-            uint32_t *taxon, uint32_t *best_count, uint32_t *best_gid, uint32_t *considered, int mem) {
+int lca_run(niqki_index *ix, const char *who, const SketchSource &src, uint32_t nq, uint32_t top_permille, uint32_t *taxon,
+            uint32_t *best_count, uint32_t *best_gid, uint32_t *considered, int mem) {
   ix->lca_stats = LcaStats();
   if (!whole_range(ix)) return fail(ix, NIQKI_E_STATE, std::string(who) + ": a slot-range shard sees partial counts; the LCA query needs a whole-range handle");
   if (top_permille > 1000) return fail(ix, NIQKI_E_INVALID, std::string(who) + ": top_permille " + std::to_string(top_permille) + " is above 1000");
   const bool dev = mem == NIQKI_MEM_DEVICE;
-  const uint32_t N = ix->n_genomes, F = ix->d.F;
+  const uint32_t N = ix->n_genomes;
   if (N && !ix->tax_set)
     return fail(ix, NIQKI_E_STATE, std::string(who) + ": no taxonomy on this genome set: call niqki_set_taxonomy (again, after genomes were added or dropped)");
   uint32_t *const user[4] = {taxon, best_count, best_gid, considered};
   if (nq == 0 || N == 0) return lca_no_hit(ix, user, nq, dev);
-  LcaCall guard(ix);
+  CallParams guard(ix, ix->d.min_score, 0);   // the query path at the handle's threshold and no top-k
   int rc = build_if_needed(ix);
   if (rc) return rc;
   Lca c(ix);
-  c.who = who;
   c.top_permille = top_permille;
-  c.stride = NIQKI_ROW_STRIDE(N);
-  // the hit buffers of the self-join calls: 16 bytes a hit, never below N, the hits of one query
-  c.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
   if ((rc = c.ev.create())) return rc;
   const uint32_t qb = dev ? nq : std::max<uint32_t>(ix->query_batch, 1);
   const uint32_t rows = std::min(qb, nq);
@@ -153,20 +94,16 @@ int lca_run(niqki_index *ix, const char *who, const int32_t *d_sketches, const i
     if ((rc = ensure(ix, ix->ws_lca_out, (size_t)rows * 16))) return rc;
     for (int j = 0; j < 4; ++j) c.out[j] = user[j] ? (uint32_t *)ix->ws_lca_out.p + (size_t)j * rows : nullptr;
   }
-  for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
-    const uint32_t n = std::min(qb, nq - q0);
-    const int32_t *d_orig = d_sketches ? d_sketches + (size_t)q0 * F : nullptr;
-    if (!d_orig) {
-      if ((rc = ensure(ix, ix->ws_cl_sk, (size_t)n * F * 4))) return rc;
-      NQ_HIP(ix, hipMemcpyAsync(ix->ws_cl_sk.p, h_sketches + (size_t)q0 * F, (size_t)n * F * 4, hipMemcpyHostToDevice, ix->stream));
-      d_orig = (const int32_t *)ix->ws_cl_sk.p;
-    }
-    if ((rc = lca_leaf(c, d_orig, 0, n))) return rc;
-    if (dev) break;   // (one batch)
-    for (int j = 0; j < 4; ++j)
-      if (user[j]) NQ_HIP(ix, hipMemcpyAsync(user[j] + q0, c.out[j], (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
-    NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // (the next batch writes the same rows)
-  }
+  HitLists hl{ix, who, c.ev, 0, ix->lca_stats.splits, false};
+  hl.consume = [&](const HitOut &hits, const int32_t *, uint32_t q_at, uint32_t n) { return lca_consume(c, hits, q_at, n); };
+  if (!dev)   // (device memory: one batch, its rows are the caller's)
+    hl.after = [&](uint32_t q0, uint32_t n) {
+      for (int j = 0; j < 4; ++j)
+        if (user[j]) NQ_HIP(ix, hipMemcpyAsync(user[j] + q0, c.out[j], (size_t)n * 4, hipMemcpyDeviceToHost, ix->stream));
+      NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // (the next batch writes the same rows)
+      return (int)NIQKI_OK;
+    };
+  if ((rc = hl.run(src, nq, qb))) return rc;
   uint32_t info[nq::kLcaInfoWords] = {0, 0, 0};
   NQ_HIP(ix, hipMemcpyAsync(info, ix->ws_lca_info.p, sizeof info, hipMemcpyDeviceToHost, ix->stream));
   NQ_HIP(ix, hipStreamSynchronize(ix->stream));
@@ -175,6 +112,7 @@ int lca_run(niqki_index *ix, const char *who, const int32_t *d_sketches, const i
   ix->lca_stats.no_common = info[nq::kLcaInfoNoCommon];
   return NIQKI_OK;
 }
+
 
 }  // namespace
 
@@ -273,9 +211,8 @@ int niqki_query_lca(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint3
                     uint32_t *best_gid, uint32_t *considered, int mem) {
   if (!ix || ((!sketches || !taxon) && nq)) return NIQKI_E_INVALID;
   NQ_HIP(ix, hipSetDevice(ix->device));
-  const bool dev = mem == NIQKI_MEM_DEVICE;
-  return lca_run(ix, "niqki_query_lca", dev ? sketches : nullptr, dev ? nullptr : sketches, nq, top_permille, taxon, best_count, best_gid,
-                 considered, mem);
+  return lca_run(ix, "niqki_query_lca", mem == NIQKI_MEM_DEVICE ? device_rows(ix, sketches) : host_rows(ix, sketches), nq, top_permille, taxon,
+                 best_count, best_gid, considered, mem);
 }
 
 int niqki_staged_query_lca(niqki_index *ix, uint32_t top_permille, uint32_t *taxon, uint32_t *best_count, uint32_t *best_gid,
@@ -286,8 +223,8 @@ int niqki_staged_query_lca(niqki_index *ix, uint32_t top_permille, uint32_t *tax
   if (rc) return rc;
   if (!taxon && ix->staged.n_entry) return NIQKI_E_INVALID;
   // (the staged sketches are only read, so niqki_staged_query answers as before)
-  return lca_run(ix, "niqki_staged_query_lca", (const int32_t *)ix->ws_stsk.p, nullptr, ix->staged.n_entry, top_permille, taxon, best_count,
-                 best_gid, considered, mem);
+  return lca_run(ix, "niqki_staged_query_lca", device_rows(ix, (const int32_t *)ix->ws_stsk.p), ix->staged.n_entry, top_permille, taxon,
+                 best_count, best_gid, considered, mem);
 }
 
 }  // extern "C"

@@ -23,111 +23,51 @@ bool whole_range(const niqki_index *ix) {
 
 namespace {
 
-// The query path with the call's threshold and no top-k; the handle's own values come back whatever happens.
-struct CallThreshold {
-  niqki_index *ix;
-  const uint32_t ms, pms, k;
-  CallThreshold(niqki_index *ix_, uint32_t threshold) : ix(ix_), ms(ix_->d.min_score), pms(ix_->p.min_score), k(ix_->p.top_k) {
-    ix->d.min_score = threshold;
-    ix->p.min_score = threshold;
-    ix->p.top_k = 0;
-  }
-  ~CallThreshold() {
-    ix->d.min_score = ms;
-    ix->p.min_score = pms;
-    ix->p.top_k = k;
-  }
-};
-
-// One self-join with a consumer of the hit buffers: niqki_cluster (the link kernel) or niqki_dereplicate (decide +
-// assign).  The batches go in index order and a halved batch finishes its first half before its second: the
-// dereplication relies on that (a batch's earlier genomes are all decided), clustering does not care.
+// One self-join with a consumer of the hit buffers: niqki_cluster (the link kernel), niqki_dereplicate (decide +
+// assign) or niqki_linkage (the forest kernels).  The batches go in index order and a halved batch finishes its first
+// half before its second (HitLists): the dereplication relies on that (a batch's earlier genomes are all decided),
+// clustering does not care.
 struct SelfJoin {
   niqki_index *ix;
   const char *who;
   SelfJoinStats &stats;
   // phases of a batch the stats time (stats.ms): store read, gather + hits, then the consumer's: 3 or 4 in all
   const int phases;
+  // events: 0-1 the store read of a batch; of a leaf 2-3 gather + hits, then phase k = 2 .. phases - 1 between k + 1
+  // and k + 2
+  PhaseTimer ev;
   // Enqueues the consumer's kernels on the hits (off, hit_counts, hit_gids) of genomes [t0, t0 + n) and ends each of
-  // its phases k = 2 .. phases - 1 with mark(k + 1).
+  // its phases k = 2 .. phases - 1 with ev.mark(k + 2).
   std::function<int(const unsigned long long *, const uint32_t *, const uint32_t *, uint32_t, uint32_t)> consume;
   bool count_pairs = false;   // stats.pairs also without profiling (the total is read back per batch anyway)
-  uint64_t stride = 0, room = 0;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // phase k lies between ev[k] and ev[k + 1]
 
-  SelfJoin(niqki_index *ix_, const char *who_, SelfJoinStats &stats_, int phases_) : ix(ix_), who(who_), stats(stats_), phases(phases_) {}
-  ~SelfJoin() {
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  int create_events() {   // (there are none unless the handle is profiling)
-    if (ix->prof) for (int k = 0; k <= phases; ++k) NQ_HIP(ix, hipEventCreate(&ev[k]));
-    return NIQKI_OK;
-  }
-  int mark(int k) {
-    if (ix->prof) NQ_HIP(ix, hipEventRecord(ev[k], ix->stream));
-    return NIQKI_OK;
-  }
+  SelfJoin(niqki_index *ix_, const char *who_, SelfJoinStats &stats_, int phases_)
+      : ix(ix_), who(who_), stats(stats_), phases(phases_), ev(ix_, phases_ + 2, stats_.ms) {}
 };
 
-// genomes [t0, t0 + n): hits at the threshold into the fixed hit buffers, then the consumer's kernels; a batch whose
-// hits exceed the room is halved.  The total is known only after the gather and the count, so a split loses that work:
-// the following batches start from the size that fitted and stay there (the batch size never grows back within a call).
-int self_join_batch(SelfJoin &r, uint32_t t0, uint32_t n, uint32_t *fitted) {
-  niqki_index *ix = r.ix;
-  int rc;
-  Planes pl;
-  HitOut out;
-  if ((rc = ensure(ix, ix->ws_misc, (size_t)n * ix->d.F * 4))) return rc;
-  if ((rc = counter_planes(ix, n, r.stride, pl))) return rc;
-  if ((rc = hit_out_ws(ix, n, r.room, out))) return rc;
-  if ((rc = r.mark(0))) return rc;
-  if ((rc = stored_sketch_rows(ix, t0, n, (int32_t *)ix->ws_misc.p))) return rc;
-  if ((rc = r.mark(1))) return rc;
-  rc = query_hits_dev(ix, (const int32_t *)ix->ws_misc.p, n, pl, r.stride, out);
-  if (rc == NIQKI_E_CAPACITY) {
-    if (n == 1) return fail(ix, NIQKI_E_STATE, std::string(r.who) + ": one query's hits exceed the genome count");   // (room >= N)
-    r.stats.splits += 1;
-    const uint32_t h = n / 2;
-    uint32_t f1 = 0, f2 = 0;
-    if ((rc = self_join_batch(r, t0, h, &f1))) return rc;
-    if ((rc = self_join_batch(r, t0 + h, n - h, &f2))) return rc;
-    *fitted = std::max(1u, std::min(f1, f2));
-    return NIQKI_OK;
-  }
-  if (rc) return rc;
-  if ((rc = r.mark(2))) return rc;
-  if ((rc = r.consume(out.off, out.counts, out.gids, t0, n))) return rc;
-  if (ix->prof) {
-    NQ_HIP(ix, hipEventSynchronize(r.ev[r.phases]));
-    for (int k = 0; k < r.phases; ++k) {
-      float ms = 0;
-      NQ_HIP(ix, hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
-      r.stats.ms[k] += ms;
-    }
-  }
-  if (ix->prof || r.count_pairs) r.stats.pairs += out.total;
-  *fitted = n;
-  return NIQKI_OK;
-}
-
-// the hit buffers, the events, then the batches of genomes [begin, n_run) in index order
+// The events, then the batches of genomes [begin, n_run) in index order: a batch's stored rows, read once, their hits at
+// the threshold into the fixed hit buffers, then the consumer's kernels.  A split loses the gather and the count of the
+// batch, so the following batches start from the size that fitted and stay there (HitLists::shrink).
 int self_join_batches(SelfJoin &r, uint32_t n_run, uint32_t begin = 0) {
   niqki_index *ix = r.ix;
-  const uint32_t N = ix->n_genomes;
-  r.stride = NIQKI_ROW_STRIDE(N);
-  // hit_counts + hit_gids and the two scratch arrays of the same size the hit kernels order them in: 16 bytes a hit;
-  // never below N, the hits of one query
-  r.room = std::max<uint64_t>(((uint64_t)std::max<uint32_t>(ix->cluster_ws_mib, 1) << 20) / 16, N);
-  int rc = r.create_events();
-  uint32_t qb = std::max<uint32_t>(ix->query_batch, 1);
-  for (uint32_t t0 = begin; t0 < n_run && !rc;) {
-    const uint32_t n = std::min(qb, n_run - t0);
-    uint32_t fitted = n;
-    rc = self_join_batch(r, t0, n, &fitted);
-    if (fitted < n) qb = fitted;   // a split batch: do not gather the following ones twice
-    t0 += n;
-  }
-  return rc;
+  int rc = r.ev.create();
+  if (rc) return rc;
+  const SketchSource rows = stored_rows(ix, begin);
+  const SketchSource timed_rows = [&](uint32_t q0, uint32_t n, const int32_t **d_sk) {
+    int rc_ = r.ev.mark(0);
+    if (!rc_) rc_ = rows(q0, n, d_sk);
+    return rc_ ? rc_ : r.ev.mark(1);
+  };
+  HitLists hl{ix, r.who, r.ev, 2, r.stats.splits, true};
+  hl.consume = [&](const HitOut &out, const int32_t *, uint32_t q_at, uint32_t n) {
+    int rc_ = r.ev.mark(3);
+    if (!rc_) rc_ = r.consume(out.off, out.counts, out.gids, begin + hl.q0 + q_at, n);
+    for (int k = 1; k < r.phases && !rc_; ++k) rc_ = r.ev.add(k + 1, k + 2, k);
+    if (!rc_ && (ix->prof || r.count_pairs)) r.stats.pairs += out.total;
+    return rc_;
+  };
+  hl.after = [&](uint32_t, uint32_t) { return r.ev.add(0, 1, 0); };
+  return hl.run(timed_rows, n_run - begin, std::max<uint32_t>(ix->query_batch, 1));
 }
 
 int cluster_run(niqki_index *ix, uint32_t *labels, uint32_t *n_clusters, int mem) {
@@ -141,22 +81,18 @@ int cluster_run(niqki_index *ix, uint32_t *labels, uint32_t *n_clusters, int mem
   SelfJoin r(ix, "niqki_cluster", ix->cluster_stats, 3);
   r.consume = [&](const unsigned long long *off, const uint32_t *, const uint32_t *hg, uint32_t t0, uint32_t n) {
     NQ_HIP(ix, nq::launch_cluster_link(parent, N, off, hg, t0, n, ix->stream));
-    return r.mark(3);
+    return r.ev.mark(4);
   };
   NQ_HIP(ix, nq::launch_cluster_init(parent, N, ix->stream));
   if ((rc = self_join_batches(r, N))) return rc;
-  if ((rc = r.mark(0))) return rc;
+  if ((rc = r.ev.mark(0))) return rc;
   NQ_HIP(ix, nq::launch_cluster_flatten(parent, N, d_labels, d_roots, ix->stream));
-  if ((rc = r.mark(1))) return rc;
+  if ((rc = r.ev.mark(1))) return rc;
   uint32_t roots = 0;
   if (mem != NIQKI_MEM_DEVICE) NQ_HIP(ix, hipMemcpyAsync(labels, d_labels, (size_t)N * 4, hipMemcpyDeviceToHost, ix->stream));
   NQ_HIP(ix, hipMemcpyAsync(&roots, d_roots, 4, hipMemcpyDeviceToHost, ix->stream));
   NQ_HIP(ix, hipStreamSynchronize(ix->stream));
-  if (ix->prof) {
-    float ms = 0;
-    NQ_HIP(ix, hipEventElapsedTime(&ms, r.ev[0], r.ev[1]));
-    ix->cluster_stats.ms[3] = ms;
-  }
+  if ((rc = r.ev.add(0, 1, 3))) return rc;   // flatten
   if (n_clusters) *n_clusters = roots;
   return NIQKI_OK;
 }
@@ -180,11 +116,11 @@ int derep_run(niqki_index *ix, uint32_t first, uint32_t threshold, uint32_t *lab
   SelfJoin r(ix, "niqki_dereplicate", ix->derep_stats, 4);
   r.consume = [&](const unsigned long long *off, const uint32_t *hc, const uint32_t *hg, uint32_t t0, uint32_t n) {
     NQ_HIP(ix, nq::launch_derep_decide(state, N, off, hg, t0, n, info, ix->stream));
-    int rc_ = r.mark(3);
+    int rc_ = r.ev.mark(4);
     if (rc_) return rc_;
     NQ_HIP(ix, nq::launch_derep_assign(state, best, N, off, hc, hg, t0, n, ix->stream));
     NQ_HIP(ix, nq::launch_derep_given(best, N, first, off, hc, hg, t0, n, ix->stream));
-    return r.mark(4);
+    return r.ev.mark(5);
   };
   NQ_HIP(ix, hipMemsetAsync(best, 0, (size_t)N * 8, ix->stream));
   NQ_HIP(ix, hipMemsetAsync(info, 0, 16, ix->stream));
@@ -240,7 +176,7 @@ int linkage_run(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_t 
   r.consume = [&](const unsigned long long *off, const uint32_t *hc, const uint32_t *hg, uint32_t t0, uint32_t n) {
     NQ_HIP(ix, nq::launch_linkage_batch(comp, best, forest[cur], forest[cur ^ 1], info, N, off, hc, hg, t0, n, ix->stream));
     cur ^= 1;
-    return r.mark(3);
+    return r.ev.mark(4);
   };
   NQ_HIP(ix, hipMemsetAsync(info, 0, (size_t)info_words * 4, ix->stream));
   if ((rc = self_join_batches(r, N))) return rc;
@@ -373,7 +309,7 @@ int niqki_cluster(niqki_index *ix, uint32_t threshold, uint32_t *labels, uint32_
     if (n_clusters) *n_clusters = 1;
     return NIQKI_OK;
   }
-  CallThreshold guard(ix, threshold);
+  CallParams guard(ix, threshold, 0);
   return cluster_run(ix, labels, n_clusters, mem);
 }
 
@@ -402,7 +338,7 @@ int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, 
     if (n_representatives) *n_representatives = N;
     return NIQKI_OK;
   }
-  CallThreshold guard(ix, threshold);
+  CallParams guard(ix, threshold, 0);
   return derep_run(ix, first, threshold, labels, label_counts, n_representatives, mem);
 }
 
@@ -425,7 +361,7 @@ int niqki_linkage(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_
     return NIQKI_OK;
   }
   if (!nq::linkage_fits(N)) return fail(ix, NIQKI_E_INVALID, "niqki_linkage: more than 2^23 genomes (the edge key holds 23 bits an id)");
-  CallThreshold guard(ix, std::max(floor, 1u));
+  CallParams guard(ix, std::max(floor, 1u), 0);
   return linkage_run(ix, floor, merge_into, merge_count, edge_lo, edge_hi, edge_count, n_roots, mem);
 }
 

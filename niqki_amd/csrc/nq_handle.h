@@ -1,6 +1,15 @@
 // nq_handle.h -- the handle behind the C ABI (niqki_index) and the library-internal helpers
 // shared by nq_api.hip (single-GPU entry points) and nq_group.hip (slot-sharded groups).
 // Private to libniqki_hip.so.
+//
+// Full hit lists: what the calls that consume a query's full hit lists on the device share -- niqki_cluster,
+// niqki_dereplicate and niqki_linkage (nq_api_selfjoin.hip), niqki_query_collapsed (nq_api_collapse.hip),
+// niqki_query_lca (nq_api_lca.hip) and, without the halving, niqki_cover (nq_api_cover.hip).  Bodies: nq_api_lists.hip.
+//   CallParams    the call's min_score / top_k on the handle, the handle's own back on every exit
+//   PhaseTimer    HIP events around the phases of a call while the handle is profiling
+//   hit_room      how many hits the fixed hit buffers take (option "cluster_ws_mib")
+//   HitLists      the batch loop over a SketchSource and the leaf that halves a batch whose lists exceed the room
+//   ensure_keep   ensure() that keeps what a batch has already written to the buffer
 #pragma once
 #include "../../include/niqki_hip.h"
 #include "../../include/niqki_hip_bench.h"
@@ -150,9 +159,9 @@ struct niqki_index {
   // niqki_linkage (stats "linkage_*"): store read, gather + hits, forest rounds, then sort + hierarchy + copies
   nqi::SelfJoinStats cluster_stats, derep_stats, linkage_stats;
   nqi::CoverStats cover_stats;
-  // niqki_cover: the batch's sketches as given (host calls), two buffers of masked rows with their query numbers, the
-  // per-row and per-query words, the pick log, a batch's picks on their way to the host
-  nqi::Buf ws_cv_orig, ws_cv_sk[2], ws_cv_idx, ws_cv_log, ws_cv_out;
+  // niqki_cover: two buffers of masked rows with their query numbers, the per-row and per-query words, the pick log, a
+  // batch's picks on their way to the host
+  nqi::Buf ws_cv_sk[2], ws_cv_idx, ws_cv_log, ws_cv_out;
   // niqki_set_labels: the genomes' labels as dense ids (device, n_genomes words) and how many there are; every call that
   // changes the genome set drops them (drop_labels)
   nqi::Buf lab_dense;
@@ -160,9 +169,9 @@ struct niqki_index {
   bool labels_set = false;
   uint32_t collapse_lds_cap = 1024;   // option "collapse_lds_cap": the longest list the LDS table of collapse_first_kernel takes
   nqi::CollapseStats collapse_stats;
-  // niqki_query_collapsed: a host call's sketches, a flag word per hit, the kept counts per query, a leaf's offsets and
-  // info words, the global tables, a batch's collapsed entries, its offsets on their way to the host
-  nqi::Buf ws_cl_sk, ws_cl_keep, ws_cl_nk, ws_cl_off, ws_cl_tab, ws_cl_stage;
+  // niqki_query_collapsed: a flag word per hit, the kept counts per query, a leaf's offsets and info words, the global
+  // tables, a batch's collapsed entries, its offsets on their way to the host
+  nqi::Buf ws_cl_keep, ws_cl_nk, ws_cl_off, ws_cl_tab, ws_cl_stage;
   bool cl_tab_clean = false;   // every entry of ws_cl_tab is cleared (false after growth and while a call is under way)
   // niqki_set_taxonomy: a node {parent, depth} per taxon and every genome's taxon (device), how many taxa there are and
   // the largest depth; every call that changes the genome set drops them (drop_taxonomy).  Independent of the labels.
@@ -171,7 +180,7 @@ struct niqki_index {
   bool tax_set = false;
   uint32_t lca_wave_cap = 1024;   // option "lca_wave_cap": the longest considered prefix one wavefront of lca_kernel folds
   nqi::LcaStats lca_stats;
-  // niqki_query_lca: a host call's result rows of a batch, the info words of a call (a host call's sketches: ws_cl_sk)
+  // niqki_query_lca: a host call's result rows of a batch, the info words of a call
   nqi::Buf ws_lca_out, ws_lca_info;
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
@@ -235,6 +244,8 @@ void *host_alloc(size_t bytes);   // page-locked host memory (niqki_host_alloc):
 void host_free(void *p);
 int fail(niqki_index *ix, int code, const std::string &msg);
 int ensure(niqki_index *ix, Buf &b, size_t bytes);   // device scratch of at least `bytes`
+// ... whose first `keep` bytes stay what they are (nq_api_lists.hip; grows to twice the need, synchronises when it grows)
+int ensure_keep(niqki_index *ix, Buf &b, size_t keep, size_t bytes);
 nq::IndexView view(const niqki_index *ix);
 std::string &create_error();   // thread-local: why the last niqki_create / niqki_import_* of the calling thread failed
 int derive(const niqki_params &p, nq::Derived &d, std::string &why);
@@ -296,10 +307,47 @@ SketchSource stored_rows(niqki_index *ix, uint32_t begin);             // genome
 uint32_t query_rows_per_batch(const niqki_index *ix);   // option "query_batch", or more where no counter rows are written
 int query_to_host(niqki_index *ix, const SketchSource &src, uint32_t nq, uint32_t qb, uint64_t *hit_off, uint32_t *hit_counts,
                   uint32_t *hit_gids, uint64_t capacity);
-// ---- nq_api_cover.hip ----
-// the greedy cover of nq device-resident whole sketches (niqki_hip.h); the outputs in host or device memory
-int cover_run(niqki_index *ix, const int32_t *d_sketches, const int32_t *h_sketches, uint32_t nq, uint32_t max_picks, uint64_t *hit_off,
-              uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_totals, uint64_t capacity, int mem);
+// ---- nq_api_lists.hip: full hit lists (the head of this file) ----
+// The query path with a call's own threshold and top_k; the handle's own values come back whatever happens.
+struct CallParams {
+  niqki_index *ix;
+  const uint32_t ms, pms, k;   // the handle's own d.min_score, p.min_score, p.top_k
+  CallParams(niqki_index *ix_, uint32_t min_score, uint32_t top_k);
+  ~CallParams();
+};
+// Events 0 .. n_events - 1 on the handle's stream.  Unless the handle is profiling (ix->prof) there are none, and
+// mark and add do nothing.  add: the span a .. b, finished (it synchronises on b), onto ms[to].
+struct PhaseTimer {
+  niqki_index *ix;
+  double *ms;
+  std::vector<hipEvent_t> ev;
+  PhaseTimer(niqki_index *ix_, int n_events, double *ms_) : ix(ix_), ms(ms_), ev((size_t)n_events, nullptr) {}
+  ~PhaseTimer();
+  int create();
+  int mark(int k);
+  int add(int a, int b, int to);
+};
+// hits the fixed hit buffers (hit_out_ws) take within option "cluster_ws_mib"; never below the genome count
+uint64_t hit_room(const niqki_index *ix);
+// One call that consumes full hit lists where the query path leaves them.  run: queries [0, nq) of src in batches of qb,
+// in order; per batch src, leaf, then `after` where there is one.  leaf: n whole sketch rows at d_sk, the queries
+// q_at .. q_at + n of the batch: counter_planes, hit_out_ws(hit_room), ev.mark(ev_hits), query_hits_dev.  Lists that
+// exceed the room: one query is refused ("<who>: one query's hits exceed the genome count"), more are halved -- one more
+// on `splits`, then the first n / 2 rows to the end, consumer included, before the others.  Lists that fit go to
+// `consume`, which enqueues the consumer's kernels and marks its own phases.  q0 is the running batch's first query.
+struct HitLists {
+  niqki_index *ix;
+  const char *who;
+  PhaseTimer &ev;
+  int ev_hits;
+  uint64_t &splits;
+  bool shrink;   // the batches after a halved one take the size of its smallest part (the self-join: no gather twice)
+  std::function<int(const HitOut &out, const int32_t *d_sk, uint32_t q_at, uint32_t n)> consume;
+  std::function<int(uint32_t q0, uint32_t n)> after;
+  uint32_t q0 = 0;
+  int run(const SketchSource &src, uint32_t nq, uint32_t qb);
+  int leaf(const int32_t *d_sk, uint32_t q_at, uint32_t n, uint32_t *fitted);
+};
 // ---- nq_api_collapse.hip ----
 void drop_labels(niqki_index *ix);   // the genome set changes: the labelling of niqki_set_labels goes
 // ---- nq_api_lca.hip ----

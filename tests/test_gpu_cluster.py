@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from lists_ref import room, splits
+
 pytestmark = pytest.mark.gpu
 
 S, W = 10, 8
@@ -139,6 +141,15 @@ def engine(native, form, sk, ms=50):
     return e
 
 
+def self_join_splits(native, sk, thr, mib, batch=1024):
+    """the halvings a self-join call at threshold thr makes (lists_ref.py), from the full list lengths of the stored
+    sketches: Engine.neighbors_range at min_score thr and top_k = 0, not the call under test"""
+    e = engine(native, "lists", sk, ms=thr)
+    off = e.neighbors_range(0, sk.shape[0])[0]
+    e.close()
+    return splits(np.diff(off.astype(np.int64)), batch, room(mib, sk.shape[0]), True)
+
+
 @pytest.mark.parametrize("form", FORMS)
 def test_cluster_equals_union_find_of_the_oracle_matrix(native, small, form):
     from niqki_amd import capi
@@ -198,11 +209,13 @@ def test_cluster_splits_a_batch_whose_hits_exceed_the_room(native, po):
     lab = labels_of_matrix(M, thr)
     assert np.max(np.bincount(lab)) >= 1500
     assert int(np.sum(M[:1024] >= thr)) > 10 * 65536
+    n_splits = self_join_splits(native, sk, thr, 1)
+    assert n_splits > 0
     e = engine(native, "lists", sk)
     e.set_option("cluster_ws_mib", 1)
     got, n = e.cluster(thr)
     assert e.stat("last_hits_form") == 1                   # the shape that takes hit lists
-    assert e.stat("cluster_splits") > 0
+    assert e.stat("cluster_splits") == n_splits
     assert np.array_equal(got, lab) and n == int(np.sum(lab == np.arange(N)))
     e.set_option("cluster_ws_mib", 1024)
     got, _ = e.cluster(thr)
@@ -210,7 +223,7 @@ def test_cluster_splits_a_batch_whose_hits_exceed_the_room(native, po):
     e.set_option("hit_lists", 0)                           # counter rows: the same split rule
     e.set_option("cluster_ws_mib", 1)
     got, _ = e.cluster(thr)
-    assert e.stat("cluster_splits") > 0 and np.array_equal(got, lab)
+    assert e.stat("cluster_splits") == n_splits and np.array_equal(got, lab)
     e.close()
 
 

@@ -7,6 +7,7 @@ import pytest
 
 import hit_designs as hd
 from collapse_ref import collapse_lists, few_cell_query
+from lists_ref import room, splits
 from test_gpu_cluster import S, T_CHAIN20, W, data, engine
 from test_gpu_cover import mixed_batch, own_params
 
@@ -195,15 +196,18 @@ def test_budget_splits_leave_the_result_unchanged(native, case):
     """1 MiB of hit buffers hold 65 536 hits; the batch's full lists hold more (checked on the expected arrays)"""
     sk, q, full, sets = case
     assert int(full[0][-1]) > 65536
+    # a host call: batches of query_batch = 1024 queries, every one at that size (lists_ref.py)
+    n_splits = splits(np.diff(full[0].astype(np.int64)), 1024, room(1, N), False)
+    assert n_splits > 0
     e = engine(native, "lists", sk)
     e.set_option("cluster_ws_mib", 1)
     e.set_labels(sets["mod7"])
     exp = collapse_lists(full, sets["mod7"])
     same(e.query_collapsed(q, members=True), exp)
-    assert e.stat("collapse_splits") > 0
+    assert e.stat("collapse_splits") == n_splits
     e.set_option("collapse_lds_cap", 64)             # ... and with the global tables inside the same small budget
     same(e.query_collapsed(q, members=True), exp)
-    assert e.stat("collapse_splits") > 0 and e.stat("collapse_long_lists") == int((np.diff(full[0].astype(np.int64)) > 64).sum())
+    assert e.stat("collapse_splits") == n_splits and e.stat("collapse_long_lists") == int((np.diff(full[0].astype(np.int64)) > 64).sum())
     e.close()
 
 

@@ -9,7 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_cluster import (F, FORMS, S, T_CHAIN10, T_CHAIN20, W, chain, data, engine, labels_of_matrix, oracle_matrix)
+from test_gpu_cluster import (F, FORMS, S, T_CHAIN10, T_CHAIN20, W, chain, data, engine, labels_of_matrix, oracle_matrix,
+                              self_join_splits)
 
 pytestmark = pytest.mark.gpu
 
@@ -183,17 +184,19 @@ def test_dereplicate_splits_a_batch_whose_hits_exceed_the_room(native, po):
     thr = T_CHAIN20
     assert int(np.sum(M[:1024] >= thr)) > 10 * 65536
     exp = derep_of_matrix(M, thr)
+    n_splits = self_join_splits(native, sk, thr, 1)
+    assert n_splits > 0
     e = engine(native, "lists", sk)
     e.set_option("cluster_ws_mib", 1)
     a = check(e, thr, exp)
-    assert e.stat("derep_splits") > 0
+    assert e.stat("derep_splits") == n_splits
     e.set_option("cluster_ws_mib", 1024)
     b = check(e, thr, exp)
     assert e.stat("derep_splits") == 0 and np.array_equal(a, b)
     e.set_option("hit_lists", 0)                           # counter rows: the same split rule
     e.set_option("cluster_ws_mib", 1)
     check(e, thr, exp)
-    assert e.stat("derep_splits") > 0
+    assert e.stat("derep_splits") == n_splits
     # niqki_cluster is not disturbed by the state the dereplication left, nor the other way round
     lab, _ = e.cluster(thr)
     assert np.array_equal(lab, labels_of_matrix(M, thr))

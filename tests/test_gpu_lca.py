@@ -8,6 +8,7 @@ import pytest
 import hit_designs as hd
 from collapse_ref import few_cell_query
 from lca_ref import NONE, depths, lca_lists
+from lists_ref import room, splits
 from test_gpu_cluster import S, T_CHAIN10, T_CHAIN20, W, data, engine
 from test_gpu_cover import mixed_batch, own_params
 
@@ -229,7 +230,9 @@ def test_budget_splits_leave_the_result_unchanged(native, case):
     same(at_default, exp[100])
     e.set_option("cluster_ws_mib", 1)
     same(e.query_lca(q, top_permille=100, details=True), exp[100])
-    assert e.stat("lca_splits") > 0
+    lens = np.diff(full[0].astype(np.int64))
+    n_splits = splits(lens, 1024, room(1, N), False)         # a host call: batches of query_batch = 1024 (lists_ref.py)
+    assert e.stat("lca_splits") == n_splits > 0
     # device memory: the whole batch in one call, halved where it does not fit
     e.set_stream(torch.cuda.current_stream().cuda_stream)
     nq = q.shape[0]
@@ -237,7 +240,7 @@ def test_budget_splits_leave_the_result_unchanged(native, case):
     out = [torch.full((nq,), FILL, dtype=torch.int32, device="cuda") for _ in range(4)]
     e.query_lca_dev(d_q, nq, 100, *out)
     torch.cuda.synchronize()
-    assert e.stat("lca_splits") > 0
+    assert e.stat("lca_splits") == splits(lens, nq, room(1, N), False) > 0      # one batch of nq
     same(tuple(x.cpu().numpy().view(np.uint32) for x in out), exp[100])
     out = [torch.full((nq,), FILL, dtype=torch.int32, device="cuda") for _ in range(4)]
     e.query_lca_dev(d_q, nq, 1000, out[0], None, out[2], None)

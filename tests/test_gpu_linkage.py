@@ -9,7 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_cluster import F, S, T_CHAIN10, T_CHAIN20, W, data, labels_of_matrix, oracle_matrix, union_find
+from test_gpu_cluster import (F, S, T_CHAIN10, T_CHAIN20, W, data, labels_of_matrix, oracle_matrix, self_join_splits,
+                              union_find)
 
 pytestmark = pytest.mark.gpu
 
@@ -171,11 +172,13 @@ def test_linkage_splits_a_batch_whose_hits_exceed_the_room(native):
     ref = e.linkage(T_CHAIN20)
     assert e.stat("linkage_splits") == 0
     assert np.max(np.bincount(native.cut_linkage(ref[0], ref[1], T_CHAIN20))) >= 1500
+    n_splits = self_join_splits(native, sk, T_CHAIN20, 1)
+    assert n_splits > 0
     for hit_lists in (1, 0):
         e.set_option("hit_lists", hit_lists)
         e.set_option("cluster_ws_mib", 1)
         got = e.linkage(T_CHAIN20)
-        assert e.stat("linkage_splits") > 0
+        assert e.stat("linkage_splits") == n_splits
         same(got, (ref[0], ref[1]) + ref[2] + (ref[3],))
     e.close()
 
