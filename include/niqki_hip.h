@@ -843,7 +843,9 @@ int niqki_group_insert(niqki_group *g, const int32_t *const *local_sketches, uin
                        uint32_t n_total);
 /* Index::query_sketch for such a batch: rank r receives the hits of ITS rows against the
  * whole index -- hit_off[i] per+1 offsets, hit_counts[i] / hit_gids[i] capacity entries
- * each, in the memory space `mem` (as niqki_query). */
+ * each, in the memory space `mem` (as niqki_query).  NIQKI_MEM_DEVICE: a rank whose lists hold
+ * more than `capacity` hits gets exact offsets and the first `capacity` entries of its lists in
+ * their order; nothing is written behind them. */
 int niqki_group_query(niqki_group *g, const int32_t *const *local_sketches, uint32_t per,
                       uint64_t *const *hit_off, uint32_t *const *hit_counts,
                       uint32_t *const *hit_gids, uint64_t capacity, int mem);

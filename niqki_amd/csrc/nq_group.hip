@@ -6,17 +6,25 @@
 //   1. every rank has sketched its share of the batch (`per` queries)            no communication
 //   2. slice exchange: a rank needs only ITS slots of every query -> one all-to-all of int16
 //      slices (2*F/G bytes per query and peer)                                    slice_pack / unpack
-//   3. gather-histogram over the local slots for ALL G*per queries                gather_kernel
-//   4. cross-shard sum of the per-genome hit vectors, scattered by query:
+//   3. gather over the local slots for ALL G*per queries                          gather_kernel
+//        dense   into u16 counter rows, one per query
+//        sparse  without counter rows: per query the kernel leaves the CANDIDATES (genomes whose
+//                partial count reaches thr = ceil(min_score / G): ids only, at most cand_cap kept)
+//                and the SURVIVORS (partial count >= max(1, thr / 2): {id, count}, at most surv_cap)
+//   4. cross-shard sum of the partial counts, scattered by query:
 //        dense   reduce-scatter of the u16 counters as packed pairs in u32 words -- a count never
 //                exceeds F <= 2^15, so the halves cannot carry (RCCL has no 16-bit integer type)
-//        sparse  a genome whose summed count reaches min_score has a partial count of at least
-//                ceil(min_score / G) on some rank: ranks all-gather those candidate ids
-//                (candidates_kernel), look their own partial counts up for the union
-//                (cand_lookup_kernel), reduce-scatter just these values and scatter the sums into
-//                otherwise empty counter rows (cand_scatter_kernel).  Exact; a candidate list that
-//                overflows its capacity makes every rank redo the step densely.
-//   5. every rank thresholds + orders the hits of its own `per` queries          hits_* kernels
+//        sparse  a genome whose summed count reaches min_score has a partial count of at least thr
+//                on some rank: ranks all-gather their candidate ids with the list sizes (one blob
+//                per rank, cand_blob_ints), each looks its own partial counts of the union up --
+//                in its survivor list, or, for an id that is weak here, counted exactly from the
+//                sketch store (surv_lookup_kernel) -- and these values are reduce-scattered.
+//                Exact; a candidate or survivor list of any rank that holds more than its capacity
+//                (blob_overflow_kernel: the same words on every rank) makes every rank redo the
+//                batch densely in niqki_group_query_end.
+//   5. every rank thresholds + orders the hits of its own `per` queries: from counter rows
+//      (hits_* kernels, nq_hits.hip) or, sparse, from the candidates' sums alone -- distinct ids,
+//      sorted in LDS, written behind a prefix sum (cand_hits_kernel, _scan_kernel, _write_kernel)
 //
 // Transports:
 //   rccl   librccl, loaded on first use -- one communicator per local rank, so the same code serves one
@@ -188,13 +196,15 @@ constexpr uint32_t kCandMax = 4096;       // ids per query cand_hits_kernel can 
 // query (every genome with a partial count >= surv_thr, indexed here by an LDS hash table) or, for an id
 // that is not among them -- another rank's candidate that is weak here --, counted exactly as the slots
 // in which the genome's stored sketch equals the query's (the identity behind the matrix path, DESIGN.md
-// 4.6): f_local strided 2-byte reads per such id, rare by construction.  flag[0] |= a list overflowed.
+// 4.6): f_local strided 2-byte reads per such id, rare by construction.  A survivor list that holds more than
+// SC entries is read up to SC (the rest of its ids are counted from the store like any other): the overflow itself
+// is blob_overflow_kernel's to report.
 // CT: uint16_t, or uint32_t where the cross-shard sums can pass 2^16 - 1 (S = 16)
 template <typename CT>
 __global__ __launch_bounds__(256) void surv_lookup_kernel(const int2 *surv, const int32_t *surv_n, uint32_t SC, uint32_t T, uint32_t m,
                                                          IdView ids, const int32_t *sk, uint32_t q_stride, uint32_t q_off,
                                                          uint32_t f_local, const uint16_t *store, uint64_t store_cap, uint32_t R,
-                                                         CT *mine, uint32_t *flag) {
+                                                         CT *mine) {
   extern __shared__ __align__(8) int lds_tab[];
   int2 *tab = (int2 *)lds_tab;                  // T x {id, count}
   uint32_t *missing = (uint32_t *)(tab + T);    // one bit per position i < m <= kCandMax
@@ -203,8 +213,8 @@ __global__ __launch_bounds__(256) void surv_lookup_kernel(const int2 *surv, cons
   for (uint32_t i = tid; i < T; i += 256) tab[i] = make_int2(-1, 0);
   for (uint32_t i = tid; i < mw; i += 256) missing[i] = 0;
   __syncthreads();
-  const uint32_t ns_all = (uint32_t)surv_n[q], ns = ns_all < SC ? ns_all : SC;   // (an overflow is every rank's to see:
-  for (uint32_t i = tid; i < ns; i += 256) {                                     //  blob_overflow_kernel)
+  const uint32_t ns_all = (uint32_t)surv_n[q], ns = ns_all < SC ? ns_all : SC;
+  for (uint32_t i = tid; i < ns; i += 256) {
     const int2 e = surv[(uint64_t)q * SC + i];
     uint32_t h = id_hash((uint32_t)e.x) & (T - 1);
     while (atomicCAS(&tab[h].x, -1, e.x) != -1) h = (h + 1) & (T - 1);   // (ids of one list are distinct)
@@ -243,7 +253,6 @@ __global__ __launch_bounds__(256) void surv_lookup_kernel(const int2 *surv, cons
       __syncthreads();
     }
   }
-  (void)flag;
 }
 
 // The hits of one query from its candidates alone: ids id(first_q + ql, i) with summed counts tot[ql][i]
@@ -352,6 +361,16 @@ __global__ __launch_bounds__(256) void cand_hits_write_kernel(const unsigned lon
     const unsigned long long k = keys[(uint64_t)ql * m + i];
     hc[base + i] = (uint32_t)(k >> 32);
     hg[base + i] = (uint32_t)k;
+  }
+}
+
+// hc / hg[0 .. min(*total, capacity)) = the head of the lists in staging buffers (total: hit_off[per], on the device)
+__global__ __launch_bounds__(256) void hits_head_kernel(const unsigned long long *total, unsigned long long capacity, const uint32_t *sc,
+                                                       const uint32_t *sg, uint32_t *hc, uint32_t *hg) {
+  const unsigned long long n = *total < capacity ? *total : capacity, step = (unsigned long long)gridDim.x * 256;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
+    hc[i] = sc[i];
+    hg[i] = sg[i];
   }
 }
 
@@ -1239,7 +1258,7 @@ uint32_t pow2_at_least(uint32_t x) {
 // (wide: `mine` holds uint32_t values)
 hipError_t launch_surv_lookup(niqki_index *ix, const int2 *surv, const int32_t *surv_n, uint32_t SC, uint32_t nq_, uint32_t m,
                               const nq::IdView &ids, const int32_t *sk, uint32_t q_stride, uint32_t q_off, void *mine,
-                              uint32_t *flag, bool wide = false) {
+                              bool wide = false) {
   if (nq_ == 0 || m == 0) return hipSuccess;
   const uint32_t T = pow2_at_least(2 * std::max(SC, 1u));
   const size_t lds = (size_t)T * 8 + (size_t)((m + 31) / 32) * 4;
@@ -1248,12 +1267,12 @@ hipError_t launch_surv_lookup(niqki_index *ix, const int2 *surv, const int32_t *
     hipError_t e = hipFuncSetAttribute((const void *)nq::surv_lookup_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(nq::surv_lookup_kernel<uint32_t>, dim3(nq_), dim3(256), lds, ix->stream, surv, surv_n, SC, T, m, ids, sk, q_stride,
-                       q_off, f_local, (const uint16_t *)ix->store, (uint64_t)ix->cap, ix->d.R, (uint32_t *)mine, flag);
+                       q_off, f_local, (const uint16_t *)ix->store, (uint64_t)ix->cap, ix->d.R, (uint32_t *)mine);
   } else {
     hipError_t e = hipFuncSetAttribute((const void *)nq::surv_lookup_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(nq::surv_lookup_kernel<uint16_t>, dim3(nq_), dim3(256), lds, ix->stream, surv, surv_n, SC, T, m, ids, sk, q_stride,
-                       q_off, f_local, (const uint16_t *)ix->store, (uint64_t)ix->cap, ix->d.R, (uint16_t *)mine, flag);
+                       q_off, f_local, (const uint16_t *)ix->store, (uint64_t)ix->cap, ix->d.R, (uint16_t *)mine);
   }
   return hipGetLastError();
 }
@@ -1349,8 +1368,24 @@ int run_hits(niqki_group *g, uint32_t per, uint32_t N, uint64_t stride) {
       NQ_G(g, l, nqi::ensure(ix, w.hc, (size_t)std::max<uint64_t>(pd.capacity, 1) * 4));
       NQ_G(g, l, nqi::ensure(ix, w.hg, (size_t)std::max<uint64_t>(pd.capacity, 1) * 4));
       out = nqi::HitOut{(unsigned long long *)w.hitoff.p, (uint32_t *)w.hc.p, (uint32_t *)w.hg.p, pd.capacity};
+    } else if (pd.capacity) {
+      // Device outputs are final as they stand: where the batch holds more than `capacity` hits the caller keeps the
+      // first `capacity` of them, so the list that crosses that border must be the HEAD of the query's list.  The hit
+      // kernels leave out a crossing list's entries past the border BEFORE they order it (its smallest gids, not its
+      // last entries): the lists are made in staging buffers with room for one more whole list and their head copied.
+      const uint64_t room = pd.capacity + N;
+      NQ_G(g, l, nqi::ensure(ix, w.hc, (size_t)room * 4));
+      NQ_G(g, l, nqi::ensure(ix, w.hg, (size_t)room * 4));
+      out = nqi::HitOut{(unsigned long long *)pd.hit_off[l], (uint32_t *)w.hc.p, (uint32_t *)w.hg.p, room};
     }
     NQ_G(g, l, nqi::hits_dev(ix, (const uint16_t *)w.red.p, plane2, per, stride, 0, N, out));
+    if (!pd.host && pd.capacity) {
+      const uint32_t blocks = (uint32_t)std::min<uint64_t>((pd.capacity + 255) / 256, 1024);
+      hipLaunchKernelGGL(nq::hits_head_kernel, dim3(blocks), dim3(256), 0, ix->stream, (const unsigned long long *)pd.hit_off[l] + per,
+                         (unsigned long long)pd.capacity, (const uint32_t *)w.hc.p, (const uint32_t *)w.hg.p, pd.hit_counts[l],
+                         pd.hit_gids[l]);
+      NQ_GH(g, hipGetLastError());
+    }
   }
   return NIQKI_OK;
 }
@@ -1428,8 +1463,7 @@ int niqki_group_query_begin(niqki_group *g, const int32_t *const *local_sketches
       NQ_GH(g, hipMemsetAsync(w.flag.p, 0, 4, ix->stream));
       const nq::IdView ids{(const int32_t *)w.cand_all.p, (uint64_t)(blob / 4), C};
       NQ_GH(g, launch_surv_lookup(ix, (const int2 *)w.surv.p, (const int32_t *)w.cand.p + (size_t)nq * C + nq, SC, nq, G * C, ids,
-                                  (const int32_t *)w.allsk.p, ix->d.slot_end - ix->d.slot_begin, 0, w.mine.p,
-                                  (uint32_t *)w.flag.p, g->wide));
+                                  (const int32_t *)w.allsk.p, ix->d.slot_end - ix->d.slot_begin, 0, w.mine.p, g->wide));
       // a candidate list of ANY rank that overflowed (same words on every rank: all decide alike)
       hipLaunchKernelGGL(nq::blob_overflow_kernel, dim3((nq + 255) / 256), dim3(256), 0, ix->stream, (const int32_t *)w.cand_all.p,
                          (uint64_t)(blob / 4), nq, G, C, SC, (uint32_t *)w.flag.p);
@@ -1540,11 +1574,8 @@ int niqki_survivor_counts(niqki_index *ix, const int32_t *sketches, uint32_t nq,
   if (ix->resident_bytes) return nqi::fail(ix, NIQKI_E_STATE, "not on a paged index (the sketch store is in host memory)");
   if (m > nq::kCandMax || surv_cap > nq::kSurvMax || !surv_cap) return nqi::fail(ix, NIQKI_E_INVALID, "at most 4096 ids per query and 4096 survivors");
   NQ_HIP(ix, hipSetDevice(ix->device));
-  int rc = nqi::ensure(ix, ix->ws_misc, 256);
-  if (rc) return rc;
   const nq::IdView view{ids, 0, std::max(m, 1u)};
-  NQ_HIP(ix, launch_surv_lookup(ix, (const int2 *)surv, n_surv, surv_cap, nq, m, view, sketches, ix->d.F, ix->d.slot_begin, counts,
-                                (uint32_t *)ix->ws_misc.p));
+  NQ_HIP(ix, launch_surv_lookup(ix, (const int2 *)surv, n_surv, surv_cap, nq, m, view, sketches, ix->d.F, ix->d.slot_begin, counts));
   return NIQKI_OK;
 }
 

@@ -2,7 +2,7 @@
 start `world` of these as fresh processes).  NIQKI_TEST_TRANSPORT = ipc (default) | rccl; NIQKI_TEST_DEVICES = number
 of devices the ranks are dealt over (default 1: all ranks on device 0, which only the ipc transport allows).
 
-    python tests/group_ipc_worker.py <rank> <world> <group id hex> <npz in> <npz out> <exchange> <cand_cap>
+    python tests/group_ipc_worker.py <rank> <world> <group id hex> <npz in> <npz out> <exchange> <cand_cap> [<surv_cap>]
 
 npz in: sk [N, F] int32, q [NQ, F] int32, S, W, min_score.  The rank inserts its rows of every batch through
 niqki_group_insert, answers its share of the queries twice (the second batch through the begin / end halves)
@@ -46,6 +46,8 @@ def main():
         assert words_kind == {"host": 2, "coarse": 0}[want]
     grp.set_option("exchange", {"sparse": 1, "dense": 2}[exchange])
     grp.set_option("cand_cap", cand_cap)
+    if len(sys.argv) > 8:
+        grp.set_option("surv_cap", int(sys.argv[8]))
     ins_per = 41
     for a in range(0, sk.shape[0], world * ins_per):
         blk = sk[a:a + world * ins_per]

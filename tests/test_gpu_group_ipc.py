@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_world(tmp_path, native, world, sk, q, S, W, MS, exchange, cand_cap, transport="ipc", devices=1, words=None):
+def run_world(tmp_path, native, world, sk, q, S, W, MS, exchange, cand_cap, transport="ipc", devices=1, words=None, surv_cap=None):
     """`world` fresh processes, one rank each, dealt over `devices` devices (tests/group_ipc_worker.py)"""
     env = dict(os.environ, NIQKI_TEST_TRANSPORT=transport, NIQKI_TEST_DEVICES=str(devices))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # (exported on this pool already: dmabuf IPC is what its driver supports)
@@ -42,7 +42,8 @@ def run_world(tmp_path, native, world, sk, q, S, W, MS, exchange, cand_cap, tran
     for r in range(world):
         out = tmp_path / ("out%d.npz" % r)
         procs.append((out, subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "group_ipc_worker.py"), str(r), str(world),
-                                             bytes(gid).hex(), str(inp), str(out), exchange, str(cand_cap)],
+                                             bytes(gid).hex(), str(inp), str(out), exchange, str(cand_cap)] +
+                                            ([] if surv_cap is None else [str(surv_cap)]),
                                             env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     res = []
     for out, p in procs:
@@ -97,6 +98,32 @@ def test_one_process_per_rank_on_one_gpu(tmp_path, native, po, world, exchange, 
     check_world(res, native, po, sk, q, S, W, MS, world, exchange, cand_cap)
     if words is None:    # the default: coherent by contract -- fine-grained device memory, or the host block where that failed
         assert all(int(d["words_kind"]) in (1, 2) for d in res)
+
+
+def test_designed_survivor_overflow_one_process_per_rank(tmp_path, native):
+    """World 3, cand_cap 8, surv_cap 16, the designed "surv + 1" batch (tests/exchange_ref.py): 17 survivors on rank 1.
+    Every rank sees the same list sizes in the all-gathered blobs, so all of them redo the batch densely; the lists are
+    the plain reference's."""
+    import exchange_ref as X
+    from hit_designs import first_difference
+    world, S, W = 3, 9, 8
+    MS = X.designed_min_scores(world)[0]
+    d = X.designed_capacity(world, S, W, MS)
+    q = d.q[[2]]
+    qp, per = X.pad_queries(q, world)
+    ex = X.Exchange(d.sk, qp, W, world, MS)
+    assert ex.expected_overflow(X.CAND_CAP, X.SURV_CAP) and ex.n_cand.max() <= X.CAND_CAP and ex.n_surv.max() == X.SURV_CAP + 1
+    res = run_world(tmp_path, native, world, d.sk, q, S, W, MS, "sparse", X.CAND_CAP, surv_cap=X.SURV_CAP)
+    assert all(int(r["per"]) == per for r in res)
+    exp = ex.lists()
+    off = np.concatenate([[0]] + [r["off"].astype(np.int64)[1:] + sum(int(p["off"][-1]) for p in res[:k]) for k, r in enumerate(res)])
+    diff = first_difference((off, np.concatenate([r["hc"] for r in res]), np.concatenate([r["hg"] for r in res])), exp)
+    assert diff is None, diff
+    off2 = np.concatenate([[0]] + [r["off2"][1:] + sum(int(p["off2"][-1]) for p in res[:k]) for k, r in enumerate(res)])
+    diff = first_difference((off2, np.concatenate([r["hc2"] for r in res]), np.concatenate([r["hg2"] for r in res])), exp)
+    assert diff is None, diff
+    assert exp[0][-1] >= 4 and all(int(r["overflows"]) >= 1 for r in res)
+    assert len({int(r["overflows"]) for r in res}) == 1
 
 
 def test_bench_two_ranks_on_one_gpu(tmp_path):
