@@ -857,7 +857,8 @@ int niqki_group_query(niqki_group *g, const int32_t *const *local_sketches, uint
  * sparse batch whose lists overflowed is redone densely here), copies host results out
  * (NIQKI_MEM_HOST) and reports a peer that never answered (ipc transport).  One batch in
  * flight per group; the argument arrays of _begin may go away after it returns, the buffers
- * they point to must stay until _end.  niqki_group_query = _begin + _end. */
+ * they point to must stay until _end.  A _begin that fails leaves no batch in flight (an _end
+ * after it returns NIQKI_E_STATE).  niqki_group_query = _begin + _end. */
 int niqki_group_query_begin(niqki_group *g, const int32_t *const *local_sketches, uint32_t per,
                             uint64_t *const *hit_off, uint32_t *const *hit_counts,
                             uint32_t *const *hit_gids, uint64_t capacity, int mem);

@@ -1,7 +1,7 @@
 // tests/fake_rccl/fake_rccl.hip -- TEST INFRASTRUCTURE ONLY: a stand-in `librccl.so.1` for ranks that all live in
 // ONE process (any devices, also one shared device -- which the real RCCL refuses).
 //
-// Why: nq_group.hip's RCCL branch (ncclSend / ncclRecv pairs inside a group call, ncclAllGather,
+// Why: nq_group_transport.hip's RCCL branch (ncclSend / ncclRecv pairs inside a group call, ncclAllGather,
 // ncclReduceScatter(ncclUint32, ncclSum), one communicator per local rank) can only run with more than one rank on
 // a box with more than one GPU, and this pool hands out one-GPU boxes.  With this library first on the loader's
 // path (LD_LIBRARY_PATH, tests/test_gpu_fake_rccl.py) every count, offset, datatype, communicator and stream the
@@ -52,6 +52,7 @@ thread_local ncclResult_t t_err = ncclSuccess;
 // counters a test reads back (fake_rccl_stat): proof that THIS library served the calls
 std::atomic<uint64_t> n_init{0}, n_send{0}, n_recv{0}, n_allgather{0}, n_reduce_scatter{0}, n_groups{0}, n_bytes{0};
 std::atomic<int64_t> fail_send_after{-1};   // fake_rccl_fail_send(n): the n-th ncclSend from now on fails (0 = the next)
+std::atomic<int64_t> fail_allgather_after{-1};   // fake_rccl_fail_allgather(n): the same for ncclAllGather
 
 size_t type_size(ncclDataType_t t) {
   switch (t) {
@@ -265,6 +266,10 @@ ncclResult_t ncclRecv(void *recvbuff, size_t count, ncclDataType_t datatype, int
 ncclResult_t ncclAllGather(const void *sendbuff, void *recvbuff, size_t sendcount, ncclDataType_t datatype, ncclComm_t comm,
                            hipStream_t stream) {
   if (!comm || !type_size(datatype) || (sendcount && (!sendbuff || !recvbuff))) return ncclInvalidArgument;
+  if (fail_allgather_after.load() >= 0 && fail_allgather_after.fetch_sub(1) == 0) {
+    t_err = ncclInternalError;   // (as in ncclSend)
+    return ncclInternalError;
+  }
   ++n_allgather;
   Op o{kAllGather, comm};
   o.send = sendbuff; o.recv = recvbuff; o.count = sendcount; o.esize = type_size(datatype); o.stream = stream;
@@ -316,5 +321,6 @@ uint64_t fake_rccl_stat(int what) {
   }
 }
 void fake_rccl_fail_send(int64_t after) { fail_send_after = after; }
+void fake_rccl_fail_allgather(int64_t after) { fail_allgather_after = after; }
 
 }  // extern "C"

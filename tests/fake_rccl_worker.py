@@ -3,11 +3,12 @@ standing in for librccl (tests/test_gpu_fake_rccl.py starts this with that direc
 NIQKI_GROUP_TRANSPORT=rccl).  No torch here: torch brings its own librccl.so.1 into the process, and the loader
 would hand THAT to the product's dlopen("librccl.so.1").  Device buffers come from the HIP runtime through ctypes.
 
-    python tests/fake_rccl_worker.py <world> <exchange: sparse|dense|overflow|fail> <S>
+    python tests/fake_rccl_worker.py <world> <exchange: sparse|dense|overflow|fail|fail_gather> <S>
 
 Checks, at world ranks on the one device: transport == rccl, the communicator has seen `world` ranks, hit lists of
 the group == a whole-range handle == the oracle; the stand-in served the calls; no group call is left open --
-also after an injected ncclSend failure, after which the group still works."""
+also after an injected ncclSend failure, after which the group still works; and an ncclAllGather that fails inside
+niqki_group_query_begin leaves no batch in flight (fail_gather)."""
 import ctypes as C
 import os
 import sys
@@ -50,6 +51,7 @@ def main():
     fake.fake_rccl_stat.restype = C.c_uint64
     fake.fake_rccl_stat.argtypes = [C.c_int]
     fake.fake_rccl_fail_send.argtypes = [C.c_int64]
+    fake.fake_rccl_fail_allgather.argtypes = [C.c_int64]
     import niqki_amd as native
     from oracle import pyoracle as po
     from test_gpu_group import make_data
@@ -111,6 +113,27 @@ def main():
             assert err.code == 3 and "Send" in str(err), str(err)
         assert fake.fake_rccl_stat(7) == 0, "a failed send left the group call open"
         assert fake.fake_rccl_stat(5) == g0 + 1
+    if exchange == "fail_gather":
+        # the 2nd ncclAllGather of a sparse batch fails inside niqki_group_query_begin, after the slice exchange went
+        # through: the call reports it, the group call is closed, and NO batch is left in flight -- a query_end that
+        # found one would wait on an earlier batch's event and return success over outputs nobody wrote
+        cap = 4096
+        off_d = [hip.to_dev(np.zeros(per + 1, np.uint64)) for _ in range(world)]
+        hc_d = [hip.to_dev(np.zeros(cap, np.uint32)) for _ in range(world)]
+        hg_d = [hip.to_dev(np.zeros(cap, np.uint32)) for _ in range(world)]
+        assert grp.stat("sparse") == 1
+        fake.fake_rccl_fail_allgather(1)
+        try:
+            grp.query_begin_dev(loc, per, off_d, hc_d, hg_d, cap)
+            raise AssertionError("the injected ncclAllGather failure was not reported")
+        except native.NiqkiError as err:
+            assert err.code == 3 and "AllGather" in str(err), str(err)      # NIQKI_E_HIP
+        assert fake.fake_rccl_stat(7) == 0, "a failed all-gather left the group call open"
+        try:
+            grp.query_end()
+            raise AssertionError("a batch whose begin failed was still in flight")
+        except native.NiqkiError as err:
+            assert err.code == 5 and "no query batch in flight" in str(err), str(err)      # NIQKI_E_STATE
     got = query()
     assert fake.fake_rccl_stat(7) == 0
     p = po.make_params(31, S, W, 3, 0.0)
@@ -129,7 +152,7 @@ def main():
     assert (grp.stat("overflows") >= 1) == (exchange == "overflow")
     sends, recvs, ag, rs = (fake.fake_rccl_stat(k) for k in (1, 2, 3, 4))
     assert sends >= world * world and recvs >= world * world and rs >= world, (sends, recvs, ag, rs)
-    if exchange in ("sparse", "overflow", "fail"):
+    if exchange in ("sparse", "overflow", "fail", "fail_gather"):
         assert ag >= world
     grp.close()
     assert fake.fake_rccl_stat(8) == 0, "niqki_group_destroy must destroy its communicators"

@@ -1,11 +1,12 @@
-"""GPU: nq_group.hip's RCCL branch with MORE THAN ONE RANK on a one-GPU box.
+"""GPU: the group's RCCL branch (nq_group_transport.hip) with MORE THAN ONE RANK on a one-GPU box.
 
 The product loads librccl by name (dlopen("librccl.so.1")); here a stand-in of that name
 (tests/fake_rccl/fake_rccl.hip: the nccl* entry points the product uses, for ranks that all live in one
 process, made of hipMemcpyAsync + a summing kernel) is put first on the loader's path of a fresh process, so
 that every count, offset, datatype, communicator and stream of the RCCL call sites -- which the real library
 only ever saw at world 1 on this pool -- runs at world 2, 3 and 8: sparse, dense and overflowing exchange,
-S = 16 (u32 sums), and an injected ncclSend failure (the group call must be closed on the way out).  Hit lists =
+S = 16 (u32 sums), an injected ncclSend failure (the group call must be closed on the way out) and an injected
+ncclAllGather failure inside niqki_group_query_begin (no batch may stay in flight: query_end says so).  Hit lists =
 whole-range handle = oracle (tests/fake_rccl_worker.py).  Sum being sharded: src/niqki_index.cpp:652-661."""
 import os
 import subprocess
@@ -30,7 +31,7 @@ def fake_lib():
 
 @pytest.mark.parametrize("world,exchange,S", [(2, "sparse", 9), (2, "dense", 9), (3, "sparse", 9), (3, "overflow", 9),
                                               (8, "sparse", 9), (8, "dense", 9), (8, "overflow", 9), (2, "sparse", 16),
-                                              (2, "dense", 16), (3, "fail", 9)])
+                                              (2, "dense", 16), (3, "fail", 9), (3, "fail_gather", 9)])
 def test_rccl_branch_with_several_ranks(fake_lib, world, exchange, S):
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = FAKE_DIR + ":" + env.get("LD_LIBRARY_PATH", "")
