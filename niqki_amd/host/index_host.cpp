@@ -9,12 +9,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +28,7 @@
 #include "label_file.h"
 #include "taxonomy_file.h"
 #include "linkage_text.h"
+#include "piece_reader.h"
 #include "seqio.h"
 
 namespace nqhost {
@@ -72,14 +68,74 @@ struct Index::Batch {
   size_t n_gz = 0;
 };
 
-void Index::check(int rc, const char *what) const {
+void Index::check_on(niqki_index *h, int rc, const char *what) {
   if (rc == NIQKI_OK) return;
-  throw std::runtime_error(std::string(what) + ": " + niqki_status_string(rc) + " (" + niqki_last_error(h_) + ")");
+  throw std::runtime_error(std::string(what) + ": " + niqki_status_string(rc) + " (" + niqki_last_error(h) + ")");
 }
 
 void Index::check_group(int rc, const char *what) const {
   if (rc == NIQKI_OK) return;
   throw std::runtime_error(std::string(what) + ": " + niqki_status_string(rc) + " (" + niqki_group_last_error(grp_) + ")");
+}
+
+// ---- the calls an engine may lack ---------------------------------------------------
+namespace {
+// per Index::Feature, in its order: the symbols it needs and the text of an engine without one of them
+const struct {
+  const char *symbols[3];
+  const char *text;
+} kFeatures[] = {
+    {{"niqki_append_begin", "niqki_append_slots", "niqki_append_cancel"}, "this engine cannot merge dumps"},
+    {{"niqki_dereplicate_from"}, "this engine has no dereplication"},
+    {{"niqki_retain"}, "this engine cannot drop genomes"},
+    {{"niqki_neighbors_range", "niqki_cluster"}, "this engine has no self-join"},
+    {{"niqki_dereplicate"}, "this engine has no dereplication"},
+    {{"niqki_linkage"}, "this engine has no linkage"},
+    {{"niqki_set_taxonomy", "niqki_staged_query_lca"}, "this engine has no LCA query"},
+    {{"niqki_staged_cover"}, "this engine has no cover"},
+    {{"niqki_set_labels", "niqki_staged_query_collapsed"}, "this engine has no collapsed query"},
+};
+template <typename Fn>
+Fn engine_call(const char *name) { return (Fn)dlsym(RTLD_DEFAULT, name); }
+}  // namespace
+
+const char *Index::lacks(Feature f) {
+  for (const char *symbol : kFeatures[(size_t)f].symbols)
+    if (symbol && !engine_call<void *>(symbol)) return kFeatures[(size_t)f].text;
+  return nullptr;
+}
+
+template <typename Fn>
+Fn Index::need(Feature f, const char *name) const {
+  if (lacks(f) || grp_) throw std::runtime_error(kFeatures[(size_t)f].text);
+  return engine_call<Fn>(name);
+}
+// the call as the header declares it: NEED(COVER, niqki_staged_cover)(h_, ...)
+#define NEED(feature, call) need<decltype(&call)>(Feature::feature, #call)
+
+void Index::refuse(const std::string &text) {
+  outfile->close();
+  (void)::unlink(out_path_.c_str());
+  throw std::runtime_error(text);
+}
+
+// One capacity retry for every call that fills hit lists: `sets` x n lists (off, hc, hg of a Hits), room for `first`
+// hits in each to begin with.  call(cap) runs the engine call; while it answers that cap is too small and cap is below
+// `limit` (the most the lists can hold: then the answer is an error), cap becomes twice the larger of itself and the
+// largest total the engine reported in off[n], but no more than limit, and the call runs again.  Returns the last answer.
+template <typename Set, typename Call>
+static int fill_lists(Set *sets, size_t n_sets, size_t n, uint64_t first, uint64_t limit, Call &&call) {
+  for (size_t s = 0; s < n_sets; ++s) sets[s].off.resize(n + 1);
+  for (uint64_t cap = first;;) {
+    for (size_t s = 0; s < n_sets; ++s) {
+      sets[s].hc.resize(cap);
+      sets[s].hg.resize(cap);
+    }
+    const int rc = call(cap);
+    if (rc != NIQKI_E_CAPACITY || cap >= limit) return rc;
+    for (size_t s = 0; s < n_sets; ++s) cap = std::max(cap, sets[s].off[n]);
+    cap = std::min(limit, cap * 2);
+  }
 }
 
 // One handle per GPU: with n_gpus > 1 shard r owns the slots of rank r (niqki_group_slot_range) on device
@@ -94,8 +150,8 @@ void Index::make_shards(const niqki_params &p0, int device, int n_gpus, const ui
     if (n_gpus > 1 && std::getenv("NIQKI_SHARDS_ON_ONE_DEVICE")) p.device = device;
     if (n_gpus > 1) niqki_group_slot_range((uint32_t)r, (uint32_t)n_gpus, dump_header ? ((const uint32_t *)dump_header)[0] : p.S, &p.slot_begin, &p.slot_end);
     niqki_index *h = nullptr;
-    const int rc = dump_header ? niqki_import_begin(&p, dump_header, &h) : niqki_create(&p, &h);
-    if (rc) throw std::runtime_error(std::string(dump_header ? "niqki_import_begin: " : "niqki_create: ") + niqki_status_string(rc) + " (" + niqki_last_error(nullptr) + ")");
+    check_on(nullptr, dump_header ? niqki_import_begin(&p, dump_header, &h) : niqki_create(&p, &h),
+             dump_header ? "niqki_import_begin" : "niqki_create");
     sh_.push_back(h);
   }
   h_ = sh_[0];
@@ -109,13 +165,8 @@ Index::Index(uint32_t ilF, uint32_t iK, uint32_t iW, uint32_t iH, const std::str
   p.top_k = top_k = itop_k;
   p.min_score = niqki_min_score(min_fract, ilF);
   make_shards(p, device, n_gpus, nullptr);
-  if (n_gpus > 1) {
-    const int rc = niqki_group_create(sh_.data(), (uint32_t)sh_.size(), 0, (uint32_t)sh_.size(), nullptr, &grp_);
-    if (rc) throw std::runtime_error(std::string("niqki_group_create: ") + niqki_status_string(rc) + " (" + niqki_last_error(h_) + ")");
-  }
   K = iK; W = iW; H = iH; lF = ilF; F = 1u << ilF; min_score = p.min_score;
-  out_path_ = out_filename;
-  outfile.reset(new ParallelTextWriter(out_filename, host_threads()));
+  open_group_and_output(out_filename);
 }
 
 namespace {
@@ -210,16 +261,22 @@ Index::Index(const std::string &dump_file, bool pretty, const std::string &out_f
         for (auto *h : sh_) check(niqki_import_slots(h, s0, s1, data, len, &used), "niqki_import_slots");
       },
       filenames);
-  if (n_gpus > 1) {
-    const int rc = niqki_group_create(sh_.data(), (uint32_t)sh_.size(), 0, (uint32_t)sh_.size(), nullptr, &grp_);
-    if (rc) throw std::runtime_error(std::string("niqki_group_create: ") + niqki_status_string(rc) + " (" + niqki_last_error(h_) + ")");
-  }
+  open_group_and_output(out_filename);
+}
+
+void Index::open_group_and_output(const std::string &out_filename) {
+  if (sh_.size() > 1)
+    check(niqki_group_create(sh_.data(), (uint32_t)sh_.size(), 0, (uint32_t)sh_.size(), nullptr, &grp_), "niqki_group_create");
   out_path_ = out_filename;
   outfile.reset(new ParallelTextWriter(out_filename, host_threads()));
 }
 
 Index::~Index() {
-  if (outfile) outfile->close();
+  // (after an error pending text may fail to be written once more: the error that ended the run has been reported)
+  try {
+    if (outfile) outfile->close();
+  } catch (...) {
+  }
   if (grp_) niqki_group_destroy(grp_);
   for (auto *h : sh_) niqki_destroy(h);
 }
@@ -264,13 +321,15 @@ query_output Index::query_sketch(const std::vector<int32_t> &sketch) const {
 
 // ---- insertion / query drivers ---------------------------------------------------
 
-// stage the files of a batch: one entry per file (insert_file_whole / query_file_whole,
-// src/niqki_index.cpp:442-456, :505-519)
-// multi-GPU: the batch's files are dealt to the shards in list order, `per` to each
-static void rank_share(size_t n, size_t per, size_t r, size_t &lo, size_t &hi) {
-  lo = std::min(n, r * per);
-  hi = std::min(n, lo + per);
+Index::Share Index::rank_share(size_t n) const {
+  Share s;
+  s.per = (uint32_t)((n + sh_.size() - 1) / sh_.size());
+  for (size_t r = 0, lo = 0; r < sh_.size(); ++r, lo += s.per) s.n_entry.push_back((uint32_t)std::min<size_t>(s.per, n - std::min(n, lo)));
+  return s;
 }
+
+// stage the files of a batch: one entry per file (insert_file_whole / query_file_whole,
+// src/niqki_index.cpp:442-456, :505-519); multi-GPU: rank_share's files to each shard
 
 // prefetch: only start the batch's host-to-device copy (niqki_stage_raw_prefetch); the stage_batch call
 // that follows for the same batch takes those bytes
@@ -308,20 +367,13 @@ void Index::stage_batch(Batch &b, bool prefetch) {
           }
         if (redone) continue;
       }
-      if (rc) throw std::runtime_error(std::string("niqki_stage_raw: ") + niqki_status_string(rc) + " (" + niqki_last_error(h) + ")");
+      check_on(h, rc, "niqki_stage_raw");
       return;
     }
   };
-  if (!grp_) {
-    stage(h_, 0, b.files.size());
-    return;
-  }
-  const size_t n = b.files.size(), per = per_rank(n);
-  for (size_t r = 0; r < sh_.size(); ++r) {
-    size_t lo, hi;
-    rank_share(n, per, r, lo, hi);
-    if (lo < hi) stage(sh_[r], lo, hi);
-  }
+  const Share s = rank_share(b.files.size());
+  for (size_t r = 0, lo = 0; r < sh_.size(); lo += s.n_entry[r++])
+    if (s.n_entry[r]) stage(sh_[r], lo, lo + s.n_entry[r]);
 }
 
 namespace {
@@ -336,81 +388,57 @@ struct Lap {  // adds the time since construction (or the last lap) to an accumu
 };
 }  // namespace
 
+void Index::staged_insert(const Share &s) {
+  if (grp_) check_group(niqki_group_staged_insert(grp_, s.per, s.n_entry.data()), "niqki_group_staged_insert");
+  else check(niqki_staged_insert(h_), "niqki_staged_insert");
+}
+
+void Index::staged_hits(const Share &s, Hits &h) {
+  h.collapsed = h.lca = false;
+  if (grp_) group_query_staged(s, h);
+  else query_staged(s.n_entry[0], h);
+}
+
 // the staged batch of b's files: sketched and inserted
 void Index::flush_insert(Batch &b) {
   Lap lap;
-  if (grp_) {
-    const size_t n = b.files.size(), per = per_rank(n);
-    std::vector<uint32_t> n_entry(sh_.size());
-    for (size_t r = 0; r < sh_.size(); ++r) {
-      size_t lo, hi;
-      rank_share(n, per, r, lo, hi);
-      n_entry[r] = (uint32_t)(hi - lo);
-    }
-    check_group(niqki_group_staged_insert(grp_, (uint32_t)per, n_entry.data()), "niqki_group_staged_insert");
-  } else {
-    check(niqki_staged_insert(h_), "niqki_staged_insert");
-  }
+  staged_insert(rank_share(b.files.size()));
   for (auto &nm : b.names) filenames.push_back(nm);
   lap.to(t_dev_);
 }
 
+// the first capacity of a call that returns the whole lists of n queries: with top_k at most n x k hits (that is
+// never too small), else `floor` or `each` per query
+static uint64_t first_capacity(uint64_t n, uint64_t top_k, uint64_t longest, uint64_t floor, uint64_t each) {
+  return top_k ? std::max<uint64_t>(n * std::min(top_k, longest), 1) : std::max(floor, n * each);
+}
+
 // hits of the entries staged on the shards, rank after rank = entry order
-void Index::group_query_staged(uint32_t per, const std::vector<uint32_t> &n_entry, Hits &h) {
+void Index::group_query_staged(const Share &s, Hits &h) {
   const size_t G = sh_.size();
   const uint64_t N = niqki_genome_count(h_);
-  // top-k: at most per x k hits per rank, never NIQKI_E_CAPACITY
-  uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)per * std::min<uint64_t>(top_k, N), 1)
-                       : std::max<uint64_t>(uint64_t(1) << 20, (uint64_t)per * 64);
-  std::vector<std::vector<uint64_t>> off(G, std::vector<uint64_t>(per + 1));
-  std::vector<std::vector<uint32_t>> hc(G), hg(G);
-  for (;;) {
-    std::vector<uint64_t *> p_off(G);
-    std::vector<uint32_t *> p_hc(G), p_hg(G);
-    for (size_t r = 0; r < G; ++r) {
-      hc[r].resize(cap);
-      hg[r].resize(cap);
-      p_off[r] = off[r].data(); p_hc[r] = hc[r].data(); p_hg[r] = hg[r].data();
-    }
-    const int rc = niqki_group_staged_query(grp_, per, n_entry.data(), p_off.data(), p_hc.data(), p_hg.data(), cap, NIQKI_MEM_HOST);
-    if (rc == NIQKI_E_CAPACITY && cap < (uint64_t)per * N) {
-      for (size_t r = 0; r < G; ++r) cap = std::max(cap, off[r][per]);
-      cap *= 2;
-      continue;
-    }
-    check_group(rc, "niqki_group_staged_query");
-    break;
-  }
+  std::vector<Hits> part(G);   // (off, hc, hg of each rank)
+  std::vector<uint64_t *> p_off(G);
+  std::vector<uint32_t *> p_hc(G), p_hg(G);
+  check_group(fill_lists(part.data(), G, s.per, first_capacity(s.per, top_k, N, uint64_t(1) << 20, 64), (uint64_t)s.per * N,
+                         [&](uint64_t cap) {
+                           for (size_t r = 0; r < G; ++r) { p_off[r] = part[r].off.data(); p_hc[r] = part[r].hc.data(); p_hg[r] = part[r].hg.data(); }
+                           return niqki_group_staged_query(grp_, s.per, s.n_entry.data(), p_off.data(), p_hc.data(), p_hg.data(), cap, NIQKI_MEM_HOST);
+                         }),
+              "niqki_group_staged_query");
   h.off.assign(1, 0);
   h.hc.clear();
   h.hg.clear();
   for (size_t r = 0; r < G; ++r)
-    for (uint32_t i = 0; i < n_entry[r]; ++i) {
-      h.hc.insert(h.hc.end(), hc[r].begin() + off[r][i], hc[r].begin() + off[r][i + 1]);
-      h.hg.insert(h.hg.end(), hg[r].begin() + off[r][i], hg[r].begin() + off[r][i + 1]);
+    for (uint32_t i = 0; i < s.n_entry[r]; ++i) {
+      h.hc.insert(h.hc.end(), part[r].hc.begin() + part[r].off[i], part[r].hc.begin() + part[r].off[i + 1]);
+      h.hg.insert(h.hg.end(), part[r].hg.begin() + part[r].off[i], part[r].hg.begin() + part[r].off[i + 1]);
       h.off.push_back(h.hc.size());
     }
 }
 
-namespace {
-using cover_fn = int (*)(niqki_index *, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint32_t *, uint64_t, int);
-cover_fn engine_cover() { return (cover_fn)dlsym(RTLD_DEFAULT, "niqki_staged_cover"); }
-}  // namespace
-
-bool Index::has_cover() { return engine_cover() != nullptr; }
-
-namespace {
-using set_labels_fn = int (*)(niqki_index *, const uint32_t *, uint32_t, int);
-using collapsed_fn = int (*)(niqki_index *, uint64_t *, uint32_t *, uint32_t *, uint32_t *, uint64_t, int);
-set_labels_fn engine_set_labels() { return (set_labels_fn)dlsym(RTLD_DEFAULT, "niqki_set_labels"); }
-collapsed_fn engine_collapsed() { return (collapsed_fn)dlsym(RTLD_DEFAULT, "niqki_staged_query_collapsed"); }
-}  // namespace
-
-bool Index::has_collapse() { return engine_set_labels() != nullptr && engine_collapsed() != nullptr; }
-
 void Index::set_collapse(const std::string &filestr) {
-  const set_labels_fn call = engine_set_labels();
-  if (!call || !engine_collapsed() || grp_) throw std::runtime_error("this engine has no collapsed query");
+  const auto call = NEED(COLLAPSE, niqki_set_labels);
   LabelFile lf;
   std::string err;
   try {
@@ -419,30 +447,15 @@ void Index::set_collapse(const std::string &filestr) {
     lf = parse_label_file((const char *)bytes.p, bytes.size, filenames);
     err = lf.error;
   } catch (const std::exception &e) { err = e.what(); }
-  if (!err.empty()) {
-    // refused before anything is written: the output file the constructor made goes away again
-    outfile->close();
-    (void)::unlink(out_path_.c_str());
-    throw std::runtime_error("--collapse '" + filestr + "': " + err);
-  }
+  if (!err.empty()) refuse("--collapse '" + filestr + "': " + err);
   label_of_ = std::move(lf.label_of);
   label_text_ = std::move(lf.texts);
   check(call(h_, label_of_.empty() ? nullptr : label_of_.data(), (uint32_t)label_of_.size(), NIQKI_MEM_HOST), "niqki_set_labels");
   collapse_ = true;
 }
 
-namespace {
-using set_taxonomy_fn = int (*)(niqki_index *, const uint32_t *, uint32_t, const uint32_t *, uint32_t, int);
-using lca_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, int);
-set_taxonomy_fn engine_set_taxonomy() { return (set_taxonomy_fn)dlsym(RTLD_DEFAULT, "niqki_set_taxonomy"); }
-lca_fn engine_lca() { return (lca_fn)dlsym(RTLD_DEFAULT, "niqki_staged_query_lca"); }
-}  // namespace
-
-bool Index::has_lca() { return engine_set_taxonomy() != nullptr && engine_lca() != nullptr; }
-
 void Index::set_lca(const std::string &filestr, uint32_t top_permille, const std::string &label_file) {
-  const set_taxonomy_fn call = engine_set_taxonomy();
-  if (!call || !engine_lca() || grp_) throw std::runtime_error("this engine has no LCA query");
+  const auto call = NEED(LCA, niqki_set_taxonomy);
   LabelFile lf;
   TaxonomyFile tf;
   std::string err, which = "--lca '" + filestr + "'";
@@ -463,12 +476,7 @@ void Index::set_lca(const std::string &filestr, uint32_t top_permille, const std
       err = tf.error;
     }
   } catch (const std::exception &e) { err = e.what(); }
-  if (!err.empty()) {
-    // refused before anything is written: the output file the constructor made goes away again
-    outfile->close();
-    (void)::unlink(out_path_.c_str());
-    throw std::runtime_error(which + ": " + err);
-  }
+  if (!err.empty()) refuse(which + ": " + err);
   taxon_text_ = std::move(tf.texts);
   if (!lf.label_of.empty())
     check(call(h_, lf.label_of.data(), (uint32_t)lf.label_of.size(), tf.parent.data(), (uint32_t)tf.parent.size(), NIQKI_MEM_HOST), "niqki_set_taxonomy");
@@ -476,15 +484,11 @@ void Index::set_lca(const std::string &filestr, uint32_t top_permille, const std
   lca_ = true;
 }
 
-// hits of the staged entries, written in entry order
-// hits of the staged entries
+// hits of the n entries staged on the one GPU
 void Index::query_staged(size_t n, Hits &h) {
   const uint64_t N = niqki_genome_count(h_);
-  h.collapsed = false;
-  h.lca = false;
   if (lca_) {   // --lca: each entry's taxon in the place of its hits, with the count of its best hit; no entry without a hit
-    const lca_fn call = engine_lca();
-    if (!call) throw std::runtime_error("this engine has no LCA query");
+    const auto call = NEED(LCA, niqki_staged_query_lca);
     std::vector<uint32_t> taxon(std::max<size_t>(n, 1)), best(std::max<size_t>(n, 1)), considered(std::max<size_t>(n, 1));
     check(call(h_, lca_permille_, taxon.data(), best.data(), nullptr, considered.data(), NIQKI_MEM_HOST), "niqki_staged_query_lca");
     h.off.assign(n + 1, 0);
@@ -498,51 +502,22 @@ void Index::query_staged(size_t n, Hits &h) {
       h.off[i + 1] = h.hc.size();
     }
     h.lca = true;
-    return;
-  }
-  if (collapse_) {   // --collapse: each entry's best hit per label in the place of its hits, at most top_k labels
-    const collapsed_fn call = engine_collapsed();
-    if (!call) throw std::runtime_error("this engine has no collapsed query");
+  } else if (collapse_) {   // --collapse: each entry's best hit per label in the place of its hits, at most top_k labels
+    const auto call = NEED(COLLAPSE, niqki_staged_query_collapsed);
     const uint64_t L = label_text_.size();
-    uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, L), 1) : std::max<uint64_t>(uint64_t(1) << 16, n * 8);
-    h.off.resize(n + 1);
-    for (;;) {
-      h.hc.resize(cap);
-      h.hg.resize(cap);
-      const int rc = call(h_, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST);
-      if (rc == NIQKI_E_CAPACITY && cap < n * L) { cap = std::max(h.off[n], cap * 2); continue; }
-      check(rc, "niqki_staged_query_collapsed");
-      break;
-    }
+    check(fill_lists(&h, 1, n, first_capacity(n, top_k, L, uint64_t(1) << 16, 8), n * L,
+                     [&](uint64_t cap) { return call(h_, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST); }),
+          "niqki_staged_query_collapsed");
     h.collapsed = N != 0;
-    return;
-  }
-  if (cover) {   // --cover: each entry's greedy cover in the place of its hits, at most top_k picks (n x k never overflows)
-    const cover_fn call = engine_cover();
-    if (!call) throw std::runtime_error("this engine has no cover");
-    uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1) : std::max<uint64_t>(uint64_t(1) << 16, n * 8);
-    h.off.resize(n + 1);
-    for (;;) {
-      h.hc.resize(cap);
-      h.hg.resize(cap);
-      const int rc = call(h_, top_k, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST);
-      if (rc == NIQKI_E_CAPACITY && cap < n * N) { cap = std::max(h.off[n], cap * 2); continue; }
-      check(rc, "niqki_staged_cover");
-      break;
-    }
-    return;
-  }
-  // top-k: at most n x k hits, never NIQKI_E_CAPACITY
-  uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1)
-                       : std::max<uint64_t>(uint64_t(1) << 20, n * 64);
-  h.off.resize(n + 1);
-  for (;;) {
-    h.hc.resize(cap);
-    h.hg.resize(cap);
-    const int rc = niqki_staged_query(h_, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST);
-    if (rc == NIQKI_E_CAPACITY && cap < n * N) { cap = std::max(h.off[n], cap * 2); continue; }
-    check(rc, "niqki_staged_query");
-    break;
+  } else if (cover) {   // --cover: each entry's greedy cover in the place of its hits, at most top_k picks
+    const auto call = NEED(COVER, niqki_staged_cover);
+    check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 16, 8), n * N,
+                     [&](uint64_t cap) { return call(h_, top_k, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST); }),
+          "niqki_staged_cover");
+  } else {
+    check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 20, 64), n * N,
+                     [&](uint64_t cap) { return niqki_staged_query(h_, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST); }),
+          "niqki_staged_query");
   }
 }
 
@@ -579,31 +554,61 @@ void Index::write_hits(const Hits &h) {
   outfile->write(text);
 }
 
-// ... sketched, queried and written out
+// The thread that puts the hit lines of a batch together and writes them while the next batch is on the GPU.  It owns
+// n_hits Hits that go round: get() waits for a free one (so at most n_hits batches are filled, wait or are written),
+// push() hands a filled one over, the thread writes them in push order -- after the first error it only takes them
+// back -- and finish() returns when everything pushed is written; `err` holds the first error then.  Lines mode: the
+// names are cut out of the piece of input here, and `release` is told when the piece (Hits::keep) is no longer needed.
+struct Index::HitsWriter {
+  std::string err;
+  HitsWriter(Index *ix, size_t n_hits, std::function<void(void *)> release = nullptr)
+      : ix_(ix), release_(std::move(release)), pool_(n_hits), th_([this] { run(); }) {
+    for (auto &h : pool_) free_.push(&h);
+  }
+  ~HitsWriter() { finish(); }
+  Hits *get() { return free_.pop(); }
+  void push(Hits *h) { queue_.push(h); }
+  void give_back(Hits *h) {   // (also a Hits that was never pushed: its call failed)
+    if (h->keep) release_(h->keep);
+    h->keep = nullptr;
+    h->name_base = nullptr;
+    free_.push_front(h);   // (the next to be taken again: its arrays are warm, the pool's untouched ones cost page faults)
+  }
+  void finish() {
+    queue_.push(nullptr);
+    if (th_.joinable()) th_.join();
+  }
+
+ private:
+  void run() {
+    while (Hits *h = queue_.pop()) {
+      try {
+        if (h->name_base) {   // the header lines of the entries, cut out here instead of on the GPU thread
+          h->names.clear();
+          h->names.reserve(h->name_at.size());
+          for (uint64_t at : h->name_at) h->names.push_back(header_line(h->name_base, h->name_room, at));
+        }
+        if (err.empty()) ix_->write_hits(*h);
+      } catch (const std::exception &e) { err = e.what(); }
+      give_back(h);
+    }
+  }
+  Index *ix_;
+  std::function<void(void *)> release_;
+  std::deque<Hits> pool_;
+  Channel<Hits *> free_, queue_;
+  std::thread th_;   // (the last member: it runs on the ones above)
+};
+
+// ... sketched, queried and handed to the writer thread
 void Index::flush_query(Batch &b) {
   Lap lap;
-  if (grp_) {
-    const size_t n = b.files.size(), per = per_rank(n);
-    std::vector<uint32_t> n_entry(sh_.size());
-    for (size_t r = 0; r < sh_.size(); ++r) {
-      size_t lo, hi;
-      rank_share(n, per, r, lo, hi);
-      n_entry[r] = (uint32_t)(hi - lo);
-    }
-    auto h = std::make_unique<Hits>();
-    h->names = b.names;
-    group_query_staged((uint32_t)per, n_entry, *h);
-    lap.to(t_dev_);
-    if (hits_sink_) hits_sink_(std::move(h)); else write_hits(*h);
-    lap.to(t_out_);
-    return;
-  }
-  auto h = std::make_unique<Hits>();
-  h->names = b.names;
-  query_staged(b.names.size(), *h);
-  lap.to(t_dev_);
-  if (hits_sink_) hits_sink_(std::move(h)); else write_hits(*h);
+  Hits *h = writer_->get();
   lap.to(t_out_);
+  h->names = b.names;
+  staged_hits(rank_share(b.files.size()), *h);
+  lap.to(t_dev_);
+  writer_->push(h);
 }
 
 // The files of `paths` in batches: reader threads fill page-locked buffers ahead, the bytes of batch i+1 cross
@@ -659,62 +664,12 @@ void Index::for_each_batch(const std::vector<std::string> &paths, void (Index::*
   // about as fast as the device): batch i is staged first, so that the readers' buffers are not all spoken for while it
   // runs -- waiting for batch i + 1 up front cost a third of the rate there.
   // Queries: a batch's hit lines are put together and written by a thread of their own while the next batch is on the
-  // GPU (at most four batches wait there; output order is batch order).  With thousands of hits per query the text
-  // took as long as the GPU calls: 4000 virus-sized genomes against themselves, 0.20 of 0.43 s.
-  struct HitsWriter {
-    Index *ix;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::unique_ptr<Hits>> q;
-    bool closed = false;
-    std::string err;
-    std::thread th;
-    explicit HitsWriter(Index *i) : ix(i), th([this] { run(); }) {}
-    void run() {
-      for (;;) {
-        std::unique_ptr<Hits> h;
-        {
-          std::unique_lock<std::mutex> g(mu);
-          cv.wait(g, [&] { return closed || !q.empty(); });
-          if (q.empty()) return;
-          h = std::move(q.front());
-          q.pop_front();
-        }
-        cv.notify_all();
-        try {
-          if (err.empty()) ix->write_hits(*h);
-        } catch (const std::exception &e) {
-          std::lock_guard<std::mutex> g(mu);
-          err = e.what();
-        }
-      }
-    }
-    void push(std::unique_ptr<Hits> h) {
-      std::unique_lock<std::mutex> g(mu);
-      cv.wait(g, [&] { return q.size() < 4; });
-      q.push_back(std::move(h));
-      g.unlock();
-      cv.notify_all();
-    }
-    void finish() {   // everything handed over is written (or the first error kept) when this returns
-      {
-        std::lock_guard<std::mutex> g(mu);
-        closed = true;
-      }
-      cv.notify_all();
-      if (th.joinable()) th.join();
-    }
-    ~HitsWriter() { finish(); }
-  };
+  // GPU (HitsWriter: four batches may wait there beside the one being filled and the one being written; output order
+  // is batch order).  With thousands of hits per query the text took as long as the GPU calls: 4000 virus-sized genomes
+  // against themselves, 0.20 of 0.43 s.
   std::unique_ptr<HitsWriter> writer;
-  if (flush == &Index::flush_query) {
-    writer.reset(new HitsWriter(this));
-    hits_sink_ = [&writer](std::unique_ptr<Hits> h) { writer->push(std::move(h)); };
-  }
-  struct SinkReset {   // (also when a GPU call throws: nothing may hand hits to a writer that is gone)
-    std::function<void(std::unique_ptr<Hits>)> &f;
-    ~SinkReset() { f = nullptr; }
-  } sink_reset{hits_sink_};
+  if (flush == &Index::flush_query) writer.reset(new HitsWriter(this, 6));
+  writer_ = writer.get();   // (flush_query runs only from here)
   Batch cur, nxt;
   assemble(cur);
   if (!cur.files.empty()) stage_batch(cur, true);
@@ -783,67 +738,41 @@ void Index::query_file_of_file_whole(const std::string &filestr) {
 }
 
 // ---- lines mode: reader thread -> GPU calls (caller's thread) -> writer thread ------
-namespace {
 
-// End of the last complete record in buf[0, size): the reader cuts its pieces there, so
-// every piece holds whole records (the GPU frames them; this is only a safe place to cut).
-// FASTA: a line that starts with '>' begins a record.  FASTQ: records are 4 lines, and a
-// piece starts at a record, so the cut is after a multiple of 4 newlines.  0 = none yet.
-size_t record_cut(const uint8_t *buf, size_t size, char type) {
-  if (type == 'Q') {
-    size_t lines = 0, cut = 0;
-    const uint8_t *p = buf, *end = buf + size;
-    while (p < end) {
-      const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-      if (!nl) break;
-      p = nl + 1;
-      if ((++lines & 3) == 0) cut = (size_t)(p - buf);
-    }
-    return cut;
-  }
-  size_t hi = size;
-  while (hi > 1) {
-    const uint8_t *gt = (const uint8_t *)memrchr(buf + 1, '>', hi - 1);
-    if (!gt) return 0;
-    if (gt[-1] == '\n') return (size_t)(gt - buf);
-    hi = (size_t)(gt - buf);
-  }
-  return 0;
+niqki_stage_info Index::stage_lines(niqki_index *h, const uint8_t *raw, size_t size, char type, std::vector<uint64_t> &hdr) {
+  const uint64_t off[2] = {0, size};
+  const uint8_t type_u8 = (uint8_t)type;
+  niqki_raw_batch rb{};
+  rb.raw = raw;
+  rb.file_off = off;
+  rb.file_type = &type_u8;
+  rb.n_files = 1;
+  rb.lines = 1;
+  rb.final = 1;  // pieces hold whole records
+  rb.max_entries = (uint32_t)hdr.size();
+  niqki_stage_info info{};
+  check_on(h, niqki_stage_raw(h, &rb, NIQKI_MEM_HOST, &info, hdr.data()), "niqki_stage_raw");
+  return info;
 }
 
-// Small blocking queue for handing buffers between the stages.
-template <typename T>
-class Channel {
- public:
-  void push(T v) {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      q_.push_back(std::move(v));
-    }
-    cv_.notify_all();
+size_t Index::deal_lines(const uint8_t *raw, size_t size, char type, std::vector<uint64_t> &hdr, Share &s, std::vector<uint64_t> &name_at) {
+  const size_t G = sh_.size();
+  std::vector<size_t> cut(G + 1, 0);   // rank r takes raw[cut[r], cut[r + 1])
+  cut[G] = size;
+  for (size_t r = 1; r < G; ++r) cut[r] = std::max(cut[r - 1], record_cut(raw, size * r / G, type));
+  s.per = 0;
+  s.n_entry.assign(G, 0);
+  name_at.clear();
+  for (size_t r = 0; r < G; ++r) {
+    if (cut[r + 1] == cut[r]) continue;
+    const niqki_stage_info info = stage_lines(sh_[r], raw + cut[r], cut[r + 1] - cut[r], type, hdr);
+    s.n_entry[r] = info.n_entry;
+    s.per = std::max(s.per, info.n_entry);
+    for (uint32_t e = 0; e < info.n_entry; ++e) name_at.push_back(cut[r] + hdr[e]);
+    if (info.consumed < cut[r + 1] - cut[r]) return cut[r] + info.consumed;   // more entries than one call takes: the round ends inside this run
   }
-  T pop() {
-    std::unique_lock<std::mutex> g(mu_);
-    cv_.wait(g, [&] { return !q_.empty(); });
-    T v = std::move(q_.front());
-    q_.pop_front();
-    return v;
-  }
-
- private:
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::deque<T> q_;
-};
-
-struct Piece {
-  PinnedBuf buf;
-  bool last = false;
-  std::string err;
-  std::atomic<int> refs{0};   // the GPU thread while it works on the piece + every batch of hits whose names still lie in it
-};
-
-}  // namespace
+  return size;
+}
 
 // One entry per record longer than K, named by its header line (insert_file_lines /
 // query_file_lines, :383-430).  A reader thread streams the file into page-locked pieces
@@ -854,212 +783,57 @@ void Index::stream_lines(const std::string &filestr, bool insert) {
   const auto t_begin = clk::now();
   uint64_t n_entries_total = 0;
   const char type = data_type(filestr);
-  const uint8_t type_u8 = (uint8_t)type;
   // sketches of one call stay below 2 GB
   const uint32_t max_entries = (uint32_t)std::min<uint64_t>(65536, std::max<uint64_t>(1024, (uint64_t(2) << 30) / ((uint64_t)F * 4)));
-  constexpr size_t kPieces = 6;   // one being read, one on the GPU, up to four whose header lines the writer still needs
-  std::deque<Piece> pieces(kPieces);
-  Channel<Piece *> free_q, ready_q;
-  for (auto &pc : pieces) free_q.push(&pc);
-
-  std::thread reader([&] {
-    std::vector<uint8_t> carry;
-    size_t target = size_t(8) << 20;
-    bool eof = false;
-    try {
-      GzReader in(filestr);
-      while (!eof) {
-        Piece *pc = free_q.pop();
-        if (!pc) return;  // the consumer gave up
-        pc->err.clear();
-        pc->last = false;
-        pc->buf.size = 0;
-        pc->buf.reserve(std::max(target, carry.size()) + (size_t(1) << 16));
-        if (!carry.empty()) std::memcpy(pc->buf.p, carry.data(), carry.size());   // (an empty vector's data() may be null)
-        pc->buf.size = carry.size();
-        carry.clear();
-        size_t cut = 0;
-        for (;;) {
-          while (!eof && pc->buf.size < target) {
-            const size_t n = in.read(pc->buf.p + pc->buf.size, target - pc->buf.size);
-            pc->buf.size += n;
-            if (n == 0 || in.eof()) eof = true;
-          }
-          if (eof) { cut = pc->buf.size; break; }
-          cut = record_cut(pc->buf.p, pc->buf.size, type);
-          if (cut) break;
-          target *= 2;  // not one complete record yet: a longer piece
-          pc->buf.reserve(target + (size_t(1) << 16));
-        }
-        carry.assign(pc->buf.p + cut, pc->buf.p + pc->buf.size);
-        pc->buf.size = cut;
-        pc->last = eof;
-        ready_q.push(pc);
-      }
-    } catch (const std::exception &e) {
-      Piece *pc = free_q.pop();
-      if (pc) { pc->err = e.what(); pc->last = true; pc->buf.size = 0; ready_q.push(pc); }
-    }
-  });
-
-  Channel<Hits *> out_q;
-  Channel<Hits *> out_free;
-  std::deque<Hits> results(4);
-  for (auto &r : results) out_free.push(&r);
-  std::string writer_err;
-  auto drop_ref = [&](Piece *pc) {
-    if (pc->refs.fetch_sub(1) == 1) free_q.push(pc);   // the last user hands the piece back to the reader
-  };
-  std::thread writer([&] {
-    for (;;) {
-      Hits *h = out_q.pop();
-      if (!h) return;
-      try {
-        if (h->keep) {   // the names: the header lines of the entries, cut out here instead of on the GPU thread
-          h->names.clear();
-          h->names.reserve(h->name_at.size());
-          for (uint64_t at : h->name_at) {
-            const uint8_t *b = h->name_base + at;
-            const uint8_t *nl = (const uint8_t *)memchr(b, '\n', h->name_room - at);
-            h->names.emplace_back((const char *)b, nl ? (size_t)(nl - b) : (size_t)(h->name_room - at));
-          }
-        }
-        if (writer_err.empty()) write_hits(*h);
-      } catch (const std::exception &e) { writer_err = e.what(); }
-      if (h->keep) {
-        Piece *pc = (Piece *)h->keep;
-        h->keep = nullptr;
-        drop_ref(pc);
-      }
-      out_free.push(h);
-    }
-  });
-
+  PieceReader reader(filestr, type);
+  HitsWriter writer(this, 4, [&reader](void *pc) { reader.release((Piece *)pc); });
   std::string err;
-  std::vector<uint64_t> hdr(max_entries);
+  std::vector<uint64_t> hdr(max_entries), name_at;
+  Share share;
   double t_piece = 0, t_frame = 0, t_names = 0, t_engine = 0, t_slot = 0;   // NIQKI_HOST_TIMING: where this thread's time goes
   try {
     for (bool last = false; !last;) {
       Lap lap;
-      Piece *pc = ready_q.pop();
-      pc->refs.store(1);
+      Piece *pc = reader.next();
       lap.to(t_piece);
       last = pc->last;
-      if (!pc->err.empty()) throw std::runtime_error(pc->err);
-      size_t at = 0;
-      while (grp_ && at < pc->buf.size) {
-        // multi-GPU: the rest of the piece is cut into one run of whole records per GPU; every GPU
-        // frames and sketches its run, the entries keep the order of the file
-        const size_t G = sh_.size(), left = pc->buf.size - at;
+      for (size_t at = 0; at < pc->buf.size;) {
         const uint8_t *base = pc->buf.p + at;
-        std::vector<size_t> cutp(G + 1, 0);
-        cutp[G] = left;
-        for (size_t r = 1; r < G; ++r) cutp[r] = std::max(cutp[r - 1], record_cut(base, left * r / G, type));
-        std::vector<niqki_stage_info> info(G);
-        std::vector<std::vector<uint64_t>> hdrs(G, std::vector<uint64_t>(max_entries));
-        std::vector<uint32_t> n_entry(G, 0);
-        size_t done = left;       // bytes of the piece this round covers
-        for (size_t r = 0; r < G; ++r) {
-          if (cutp[r + 1] == cutp[r]) continue;
-          const uint64_t off[2] = {0, cutp[r + 1] - cutp[r]};
-          niqki_raw_batch rb{};
-          rb.raw = base + cutp[r];
-          rb.file_off = off;
-          rb.file_type = &type_u8;
-          rb.n_files = 1;
-          rb.lines = 1;
-          rb.final = 1;
-          rb.max_entries = max_entries;
-          const int rc = niqki_stage_raw(sh_[r], &rb, NIQKI_MEM_HOST, &info[r], hdrs[r].data());
-          if (rc) throw std::runtime_error(std::string("niqki_stage_raw: ") + niqki_status_string(rc) + " (" + niqki_last_error(sh_[r]) + ")");
-          n_entry[r] = info[r].n_entry;
-          if (info[r].consumed < off[1]) {   // more entries than one call takes: the round ends inside this run
-            done = cutp[r] + info[r].consumed;
-            break;
-          }
-        }
-        uint32_t per = 0, total = 0;
-        for (size_t r = 0; r < G; ++r) { per = std::max(per, n_entry[r]); total += n_entry[r]; }
+        const size_t left = pc->buf.size - at;
+        const size_t done = deal_lines(base, left, type, hdr, share, name_at);
+        lap.to(t_frame);
+        const size_t total = name_at.size();
         n_entries_total += total;
-        if (total) {
-          Hits *h = insert ? nullptr : out_free.pop();
-          std::vector<std::string> local;
-          std::vector<std::string> &names = h ? h->names : local;
-          names.clear();
-          for (size_t r = 0; r < G; ++r)
-            for (uint32_t e = 0; e < n_entry[r]; ++e) {
-              const uint8_t *b = base + cutp[r] + hdrs[r][e];
-              const size_t room = left - cutp[r] - hdrs[r][e];
-              const uint8_t *nl = (const uint8_t *)memchr(b, '\n', room);
-              names.emplace_back((const char *)b, nl ? (size_t)(nl - b) : room);
-            }
-          if (insert) {
-            check_group(niqki_group_staged_insert(grp_, per, n_entry.data()), "niqki_group_staged_insert");
-            for (auto &nm : names) filenames.push_back(nm);
-          } else {
-            try { group_query_staged(per, n_entry, *h); } catch (...) { out_free.push(h); throw; }
-            out_q.push(h);
-          }
+        if (insert && total) {
+          for (uint64_t a : name_at) filenames.push_back(header_line(base, left, a));
+          lap.to(t_names);
+          staged_insert(share);
+        } else if (total) {
+          Hits *h = writer.get();
+          lap.to(t_slot);
+          // the writer thread cuts the names out of the piece (it stays alive until then: Piece::refs)
+          h->name_base = base;
+          h->name_room = left;
+          h->name_at.swap(name_at);
+          h->keep = pc;
+          reader.retain(pc);
+          lap.to(t_names);
+          try { staged_hits(share, *h); } catch (...) { writer.give_back(h); throw; }
+          writer.push(h);
         }
+        lap.to(t_engine);
         if (done == 0 && total == 0) break;   // nothing but a header without end
         at += done;
       }
-      if (!grp_) do {
-        const uint64_t off[2] = {0, pc->buf.size - at};
-        niqki_raw_batch rb{};
-        rb.raw = pc->buf.p + at;
-        rb.file_off = off;
-        rb.file_type = &type_u8;
-        rb.n_files = 1;
-        rb.lines = 1;
-        rb.final = 1;  // pieces hold whole records
-        rb.max_entries = max_entries;
-        niqki_stage_info info{};
-        Lap lap2;
-        check(niqki_stage_raw(h_, &rb, NIQKI_MEM_HOST, &info, hdr.data()), "niqki_stage_raw");
-        lap2.to(t_frame);
-        n_entries_total += info.n_entry;
-        if (info.n_entry) {
-          Hits *h = insert ? nullptr : out_free.pop();
-          lap2.to(t_slot);
-          const uint8_t *base = pc->buf.p + at;
-          const size_t left = pc->buf.size - at;
-          if (insert) {
-            for (uint32_t e = 0; e < info.n_entry; ++e) {
-              const uint8_t *b = base + hdr[e];
-              const uint8_t *nl = (const uint8_t *)memchr(b, '\n', left - hdr[e]);
-              filenames.emplace_back((const char *)b, nl ? (size_t)(nl - b) : (size_t)(left - hdr[e]));
-            }
-            lap2.to(t_names);
-            check(niqki_staged_insert(h_), "niqki_staged_insert");
-          } else {
-            // the writer thread cuts the names out of the piece (it stays alive until then: Piece::refs)
-            h->names.clear();
-            h->name_base = base;
-            h->name_room = left;
-            h->name_at.assign(hdr.begin(), hdr.begin() + info.n_entry);
-            h->keep = pc;
-            pc->refs.fetch_add(1);
-            lap2.to(t_names);
-            try { query_staged(info.n_entry, *h); } catch (...) { h->keep = nullptr; pc->refs.fetch_sub(1); out_free.push(h); throw; }
-            out_q.push(h);
-          }
-          lap2.to(t_engine);
-        }
-        if (info.consumed == 0 && info.n_entry == 0) break;  // nothing but a header without end
-        at += info.consumed;
-      } while (at < pc->buf.size);
-      drop_ref(pc);
+      reader.release(pc);
     }
   } catch (const std::exception &e) {
     err = e.what();
-    free_q.push(nullptr);  // releases a reader that waits for a buffer
   }
-  reader.join();
-  out_q.push(nullptr);
-  writer.join();
+  reader.stop();
+  writer.finish();
   if (!err.empty()) throw std::runtime_error(err);
-  if (!writer_err.empty()) throw std::runtime_error(writer_err);
+  if (!writer.err.empty()) throw std::runtime_error(writer.err);
   if (std::getenv("NIQKI_HOST_TIMING"))
     std::cerr << "[niqki timing] lines mode: " << n_entries_total << " entries in "
               << std::chrono::duration<double>(clk::now() - t_begin).count() << " s (this thread: waiting for file bytes " << t_piece
@@ -1132,54 +906,17 @@ void Index::query_matrix() {
 
 // ---- self-join --------------------------------------------------------------------
 
-namespace {
-using neighbors_fn = int (*)(niqki_index *, uint32_t, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint64_t, int);
-using cluster_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, int);
-using derep_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, int);
-neighbors_fn engine_neighbors() { return (neighbors_fn)dlsym(RTLD_DEFAULT, "niqki_neighbors_range"); }
-cluster_fn engine_cluster() { return (cluster_fn)dlsym(RTLD_DEFAULT, "niqki_cluster"); }
-using retain_fn = int (*)(niqki_index *, const uint8_t *, uint32_t *, uint32_t *, int);
-derep_fn engine_derep() { return (derep_fn)dlsym(RTLD_DEFAULT, "niqki_dereplicate"); }
-using derep_from_fn = int (*)(niqki_index *, uint32_t, uint32_t, uint32_t *, uint32_t *, uint32_t *, int);
-derep_from_fn engine_derep_from() { return (derep_from_fn)dlsym(RTLD_DEFAULT, "niqki_dereplicate_from"); }
-using append_begin_fn = int (*)(niqki_index *, const uint8_t *);
-using append_slots_fn = int (*)(niqki_index *, uint32_t, uint32_t, const uint8_t *, uint64_t, uint64_t *);
-using append_cancel_fn = int (*)(niqki_index *);
-append_begin_fn engine_append_begin() { return (append_begin_fn)dlsym(RTLD_DEFAULT, "niqki_append_begin"); }
-append_slots_fn engine_append_slots() { return (append_slots_fn)dlsym(RTLD_DEFAULT, "niqki_append_slots"); }
-append_cancel_fn engine_append_cancel() { return (append_cancel_fn)dlsym(RTLD_DEFAULT, "niqki_append_cancel"); }
-retain_fn engine_retain() { return (retain_fn)dlsym(RTLD_DEFAULT, "niqki_retain"); }
-using linkage_fn = int (*)(niqki_index *, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, int);
-linkage_fn engine_linkage() { return (linkage_fn)dlsym(RTLD_DEFAULT, "niqki_linkage"); }
-}  // namespace
-
-bool Index::has_self_join() { return engine_neighbors() != nullptr && engine_cluster() != nullptr; }
-bool Index::has_dereplication() { return engine_derep() != nullptr; }
-bool Index::has_linkage() { return engine_linkage() != nullptr; }
-bool Index::has_retain() { return engine_retain() != nullptr; }
-bool Index::has_dereplication_from() { return engine_derep_from() != nullptr; }
-bool Index::has_append() { return engine_append_begin() != nullptr && engine_append_slots() != nullptr && engine_append_cancel() != nullptr; }
-
 void Index::query_neighbors() {
-  const neighbors_fn call = engine_neighbors();
-  if (!call || grp_) throw std::runtime_error("this engine has no self-join");
+  const auto call = NEED(SELF_JOIN, niqki_neighbors_range);
   const uint32_t N = (uint32_t)filenames.size(), rows = 1024;
   Hits h;
   for (uint32_t t0 = 0; t0 < N; t0 += rows) {
     const uint32_t t1 = std::min(N, t0 + rows), n = t1 - t0;
     h.names.assign(filenames.begin() + t0, filenames.begin() + t1);
-    // (capacity as query_staged: top-k never exceeds n x k)
-    uint64_t cap = top_k ? std::max<uint64_t>((uint64_t)n * std::min<uint64_t>(top_k, N), 1)
-                         : std::max<uint64_t>(uint64_t(1) << 20, (uint64_t)n * 64);
-    h.off.resize(n + 1);
-    for (;;) {
-      h.hc.resize(cap);
-      h.hg.resize(cap);
-      const int rc = call(h_, t0, t1, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST);
-      if (rc == NIQKI_E_CAPACITY && cap < (uint64_t)n * N) { cap = std::max(h.off[n], cap * 2); continue; }
-      check(rc, "niqki_neighbors_range");
-      break;
-    }
+    // (capacity as query_staged)
+    check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 20, 64), (uint64_t)n * N,
+                     [&](uint64_t cap) { return call(h_, t0, t1, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST); }),
+          "niqki_neighbors_range");
     write_hits(h);
   }
 }
@@ -1210,8 +947,7 @@ void Index::write_groups(const std::string &filestr, const std::vector<uint32_t>
 }
 
 void Index::cluster_to_file(const std::string &filestr) {
-  const cluster_fn call = engine_cluster();
-  if (!call || grp_) throw std::runtime_error("this engine has no self-join");
+  const auto call = NEED(SELF_JOIN, niqki_cluster);
   const uint32_t N = (uint32_t)filenames.size();
   niqki_params p{};
   check(niqki_get_params(h_, &p), "niqki_get_params");
@@ -1223,8 +959,7 @@ void Index::cluster_to_file(const std::string &filestr) {
 }
 
 void Index::dereplicate(const std::string &list_file, const std::string &dump_file) {
-  const derep_fn call = engine_derep();
-  if (!call || grp_) throw std::runtime_error("this engine has no dereplication");
+  const auto call = NEED(DEREPLICATION, niqki_dereplicate);
   const uint32_t N = (uint32_t)filenames.size();
   niqki_params p{};
   check(niqki_get_params(h_, &p), "niqki_get_params");
@@ -1240,8 +975,7 @@ void Index::dereplicate(const std::string &list_file, const std::string &dump_fi
 }
 
 void Index::linkage_to_files(const std::string &mst_file, const std::string &linkage_file, const std::string &tree_file) {
-  const linkage_fn call = engine_linkage();
-  if (!call || grp_) throw std::runtime_error("this engine has no linkage");
+  const auto call = NEED(LINKAGE, niqki_linkage);
   const uint32_t N = (uint32_t)filenames.size();
   niqki_params p{};
   check(niqki_get_params(h_, &p), "niqki_get_params");
@@ -1267,10 +1001,9 @@ void Index::linkage_to_files(const std::string &mst_file, const std::string &lin
 // ---- merging dumps ------------------------------------------------------------------
 
 void Index::merge_dump(const std::string &dump_file) {
-  const append_begin_fn begin = engine_append_begin();
-  const append_slots_fn slots = engine_append_slots();
-  const append_cancel_fn cancel = engine_append_cancel();
-  if (!begin || !slots || !cancel || grp_) throw std::runtime_error("this engine cannot merge dumps");
+  const auto begin = NEED(APPEND, niqki_append_begin);
+  const auto slots = NEED(APPEND, niqki_append_slots);
+  const auto cancel = NEED(APPEND, niqki_append_cancel);
   std::vector<std::string> names;
   bool pending = false;
   try {
@@ -1294,16 +1027,13 @@ void Index::merge_dump(const std::string &dump_file) {
   } catch (const std::exception &e) {
     // refused: the index is the one before the merge, and nothing is written, the -O file included
     if (pending) (void)cancel(h_);
-    outfile->close();
-    (void)::unlink(out_path_.c_str());
-    throw std::runtime_error("--merge '" + dump_file + "': " + e.what());
+    refuse("--merge '" + dump_file + "': " + e.what());
   }
   filenames.insert(filenames.end(), std::make_move_iterator(names.begin()), std::make_move_iterator(names.end()));
 }
 
 void Index::keep_novel(uint32_t first, uint32_t threshold, const std::string &list_file) {
-  const derep_from_fn call = engine_derep_from();
-  if (!call || grp_) throw std::runtime_error("this engine has no dereplication");
+  const auto call = NEED(DEREPLICATION_FROM, niqki_dereplicate_from);
   const uint32_t N = (uint32_t)filenames.size();
   std::vector<uint32_t> labels(N);
   check(call(h_, first, threshold, labels.data(), nullptr, nullptr, NIQKI_MEM_HOST), "niqki_dereplicate_from");
@@ -1317,8 +1047,7 @@ void Index::keep_novel(uint32_t first, uint32_t threshold, const std::string &li
 // ---- dropping genomes ---------------------------------------------------------------
 
 void Index::retain(const std::vector<uint8_t> &keep) {
-  const retain_fn call = engine_retain();
-  if (!call || grp_) throw std::runtime_error("this engine cannot drop genomes");
+  const auto call = NEED(RETAIN, niqki_retain);
   if (keep.size() != filenames.size()) throw std::runtime_error("retain: one flag per indexed genome");
   uint32_t n_kept = 0;
   check(call(h_, keep.data(), nullptr, &n_kept, NIQKI_MEM_HOST), "niqki_retain");
@@ -1345,12 +1074,7 @@ void Index::remove_listed(const std::string &filestr) {
   for (size_t g = 0; g < filenames.size(); ++g)
     if (listed.count(filenames[g])) { keep[g] = 0; seen.insert(filenames[g]); }
   for (const std::string &name : in_order)
-    if (!seen.count(name)) {
-      // refused before anything is written: the output file the constructor made goes away again
-      outfile->close();
-      (void)::unlink(out_path_.c_str());
-      throw std::runtime_error("--remove: no indexed genome is named '" + name + "'");
-    }
+    if (!seen.count(name)) refuse("--remove: no indexed genome is named '" + name + "'");
   if (!listed.empty()) retain(keep);
 }
 

@@ -57,71 +57,59 @@ class Index {
   void query_matrix();                                          // :614-628
   void dump_index_disk(const std::string &filestr);            // :42-59
 
-  // The self-join (long options --neighbors / --cluster; single-GPU index).  The two engine calls are looked up at run
-  // time, so that the program still links against an engine that answers the C ABI without them.
-  static bool has_self_join();
-  // the indexed genomes as queries, in index order, written like a -Q batch (niqki_neighbors_range)
+  // What an engine may answer the C ABI without (the CPU stand-in of the test suite is such an engine): the calls behind
+  // the long options below are looked up at run time, so the program links against any engine, and a run that needs one
+  // the engine lacks is refused with the feature's text.  One table in index_host.cpp holds, per feature, the symbols it
+  // needs and that text.  All of these work on a single-GPU index only.
+  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, SELF_JOIN, DEREPLICATION, LINKAGE, LCA, COVER, COLLAPSE };
+  // null where the engine has every call of the feature, else the text that says what is missing
+  static const char *lacks(Feature f);
+
+  // --neighbors: the indexed genomes as queries, in index order, written like a -Q batch (niqki_neighbors_range)
   void query_neighbors();
-  // single-linkage clusters at min_score (niqki_cluster) as lines representative<TAB>member: clusters in the order of
-  // their representative's index position, members in index order; a gzip file like every output of the program
+  // --cluster: single-linkage clusters at min_score (niqki_cluster) as lines representative<TAB>member: clusters in the
+  // order of their representative's index position, members in index order; a gzip file like every output of the program
   void cluster_to_file(const std::string &filestr);
-  // Dereplication (long option --derep; single-GPU index; niqki_dereplicate, looked up at run time like the two above):
-  // greedy representatives at min_score in index order, as lines representative<TAB>member: groups in the order of
-  // their representative's index position, the representative's own line first, then its members in index order
-  static bool has_dereplication();
+  // --derep / --derep-dump, ONE niqki_dereplicate call for both: greedy representatives at min_score in index order.
+  // list_file (unless empty) gets lines representative<TAB>member of the full index: groups in the order of their
+  // representative's index position, the representative's own line first, then its members in index order.  Then, unless
+  // dump_file is empty, only the representatives are retained and dumped there (dump_index_disk); the index in memory
+  // is the dereplicated one from then on.
+  void dereplicate(const std::string &list_file, const std::string &dump_file);
   void dereplicate_to_file(const std::string &filestr) { dereplicate(filestr, ""); }
-  // Dropping genomes (long options --remove / --derep-dump; single-GPU index; niqki_retain, looked up at run time like
-  // the calls above).  retain: the genomes with a zero flag leave the engine's index and `filenames`; the rest keep
-  // their order.  remove_listed: drops every genome that carries a name of the file (one per line); a name no genome
-  // carries is an error, and then nothing is written, the -O file included.
-  static bool has_retain();
+  // --remove (niqki_retain).  retain: the genomes with a zero flag leave the engine's index and `filenames`; the rest
+  // keep their order.  remove_listed: drops every genome that carries a name of the file (one per line); a name no
+  // genome carries is an error, and then nothing is written, the -O file included.
   void retain(const std::vector<uint8_t> &keep);
   void remove_listed(const std::string &filestr);
-  // ONE niqki_dereplicate call for --derep and --derep-dump: the list of the full index into list_file (unless empty),
-  // then, unless dump_file is empty, only the representatives are retained and dumped there (dump_index_disk); the
-  // index in memory is the dereplicated one from then on
-  void dereplicate(const std::string &list_file, const std::string &dump_file);
-
-  // Merging dumps (long option --merge; single-GPU index; niqki_append_begin / _slots / _cancel, looked up at run time
-  // like the calls above).  The dump file is streamed through the readers of the loading constructor, whole slots go to
-  // the engine's pending append, and its names follow `filenames` (duplicates are kept as they are).  A dump the engine
-  // refuses (other lF / K / W / H, a broken payload) leaves the index as it was and is an error, and then nothing is
-  // written, the -O file included.
-  static bool has_append();
+  // --merge (niqki_append_begin / _slots / _cancel).  The dump file is streamed through the readers of the loading
+  // constructor, whole slots go to the engine's pending append, and its names follow `filenames` (duplicates are kept as
+  // they are).  A dump the engine refuses (other lF / K / W / H, a broken payload) leaves the index as it was and is an
+  // error, and then nothing is written, the -O file included.
   void merge_dump(const std::string &dump_file);
-  // The novelty filter (long option --novel; niqki_dereplicate_from + niqki_retain): the genomes below `first` are
-  // given; of the others the representatives at `threshold` (a co-occurrence count, as min_score) stay.  list_file gets the --derep lines of the genomes from
-  // `first` on; the index in memory holds the given genomes and the new representatives from then on.
-  static bool has_dereplication_from();
+  // --novel (niqki_dereplicate_from + niqki_retain): the genomes below `first` are given; of the others the
+  // representatives at `threshold` (a co-occurrence count, as min_score) stay.  list_file gets the --derep lines of the
+  // genomes from `first` on; the index in memory holds the given genomes and the new representatives from then on.
   void keep_novel(uint32_t first, uint32_t threshold, const std::string &list_file);
-
-  // The linkage phase (long options --mst / --linkage / --tree; single-GPU index; niqki_linkage, looked up at run time
-  // like the calls above): ONE engine call at min_score as the floor serves the three files (an empty name: not
-  // written); the texts are linkage_text.h's, gzip files like every output of the program.
-  static bool has_linkage();
+  // --mst / --linkage / --tree: ONE niqki_linkage call at min_score as the floor serves the three files (an empty name:
+  // not written); the texts are linkage_text.h's, gzip files like every output of the program.
   void linkage_to_files(const std::string &mst_file, const std::string &linkage_file, const std::string &tree_file);
 
-  // The greedy cover (long option --cover; single-GPU resident index; niqki_staged_cover, looked up at run time like
-  // the calls above).  With `cover` set the list of every -Q / -l query is its cover instead of its hits: per pick the
-  // genome and the slots it newly explains, at most top_k picks where top_k > 0; --neighbors and -M are not affected.
-  static bool has_cover();
+  // The three that replace the list of every -Q / -l query; --neighbors and -M are not affected.
+  // --cover (niqki_staged_cover; resident index): with `cover` set the list is the query's greedy cover: per pick the
+  // genome and the slots it newly explains, at most top_k picks where top_k > 0.
   bool cover = false;
-  // Collapsed hits (long option --collapse <file>; single-GPU index; niqki_set_labels + niqki_staged_query_collapsed,
-  // looked up at run time like the calls above).  set_collapse reads the label file (label_file.h; plain or gzip) against
-  // `filenames` as they are at that moment and hands the labels to the engine; from then on the list of every -Q / -l
-  // query holds one entry per label -- the label's text and the jaccard of its best member -- at most top_k labels
-  // where top_k > 0; --neighbors and -M are not affected.  A file error is an error of the run, and then nothing is
-  // written, the -O file included.
-  static bool has_collapse();
+  // --collapse <file> (niqki_set_labels + niqki_staged_query_collapsed).  set_collapse reads the label file
+  // (label_file.h; plain or gzip) against `filenames` as they are at that moment and hands the labels to the engine;
+  // from then on the list holds one entry per label -- the label's text and the jaccard of its best member -- at most
+  // top_k labels where top_k > 0.  A file error is an error of the run, and then nothing is written, the -O file included.
   void set_collapse(const std::string &filestr);
-  // Taxon of a query (long options --lca <file>, --lca-top <permille>; single-GPU index; niqki_set_taxonomy +
-  // niqki_staged_query_lca, looked up at run time like the calls above).  set_lca reads the taxonomy file
+  // --lca <file>, --lca-top <permille> (niqki_set_taxonomy + niqki_staged_query_lca).  set_lca reads the taxonomy file
   // (taxonomy_file.h; plain or gzip) over the label texts of the run -- those of label_file (the --collapse file)
   // where it is not empty, else every genome under its own name -- and hands genome taxa and parents to the engine;
-  // from then on the list of every -Q / -l query holds at most one entry, taxonText:jaccard of the best hit
-  // ("no_common_taxon" where the considered hits lie in two trees); --neighbors and -M are not affected.  A file error
-  // is an error of the run, and then nothing is written, the -O file included.
-  static bool has_lca();
+  // from then on the list holds at most one entry, taxonText:jaccard of the best hit ("no_common_taxon" where the
+  // considered hits lie in two trees).  A file error is an error of the run, and then nothing is written, the -O file
+  // included.
   void set_lca(const std::string &filestr, uint32_t top_permille, const std::string &label_file);
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
@@ -129,7 +117,20 @@ class Index {
 
  private:
   void write_groups(const std::string &filestr, const std::vector<uint32_t> &labels, uint32_t first = 0);   // lines of members >= first
+  // the feature's call `name` as an Fn; throws the feature's text where the engine lacks it or the index is a --gpus group
+  template <typename Fn>
+  Fn need(Feature f, const char *name) const;
+  // a run refused before anything is written: the output file the constructor made goes away again, `text` is thrown
+  [[noreturn]] void refuse(const std::string &text);
+  void open_group_and_output(const std::string &out_filename);   // the tail of both constructors
   struct Batch;
+  // The entries of a batch dealt to the GPUs in order: n_entry[r] of them on rank r, at most `per` on any (one GPU:
+  // all of them on rank 0).
+  struct Share {
+    uint32_t per = 0;
+    std::vector<uint32_t> n_entry;
+  };
+  Share rank_share(size_t n) const;   // whole-file mode: n files, ceil(n / GPUs) to each rank in list order
   void stage_batch(Batch &b, bool prefetch);
   void flush_insert(Batch &b);
   void flush_query(Batch &b);
@@ -147,7 +148,12 @@ class Index {
     std::vector<uint64_t> name_at;
     void *keep = nullptr;
   };
-  void query_staged(size_t n, Hits &h);
+  struct HitsWriter;   // the thread that formats and writes a batch's hits while the next batch is on the GPU
+  // the staged entries of `s`: inserted / their hits, in entry order (rank after rank)
+  void staged_insert(const Share &s);
+  void staged_hits(const Share &s, Hits &h);
+  void query_staged(size_t n, Hits &h);                    // ... one GPU
+  void group_query_staged(const Share &s, Hits &h);       // ... the shards of a group
   void write_hits(const Hits &h);
   bool collapse_ = false;                // --collapse: set_collapse has run
   std::vector<uint32_t> label_of_;      // ... per genome its label, per label its text (label_file.h)
@@ -156,20 +162,22 @@ class Index {
   uint32_t lca_permille_ = 0;
   std::vector<std::string> taxon_text_;  // ... per taxon its text (taxonomy_file.h)
   std::string out_text_;                // write_hits' lines before they go to the writer
-  std::string out_path_;                // the -O file (remove_listed takes it away again when it refuses)
+  std::string out_path_;                // the -O file (refuse takes it away again)
+  // Lines mode.  stage_lines: one niqki_stage_raw of the whole records at raw[0, size) on h -- at most hdr.size()
+  // entries, hdr gets the offsets of their header lines.  deal_lines: the same for all GPUs -- the bytes are cut into one
+  // run of whole records per GPU, the entries keep the order of the file; `s` gets the entries per rank, name_at their
+  // header lines' offsets from raw; returns the bytes taken (less than size: a call took all the entries it may).
+  niqki_stage_info stage_lines(niqki_index *h, const uint8_t *raw, size_t size, char type, std::vector<uint64_t> &hdr);
+  size_t deal_lines(const uint8_t *raw, size_t size, char type, std::vector<uint64_t> &hdr, Share &s, std::vector<uint64_t> &name_at);
   void stream_lines(const std::string &filestr, bool insert);
-  void check(int rc, const char *what) const;
+  static void check_on(niqki_index *h, int rc, const char *what);
+  void check(int rc, const char *what) const { check_on(h_, rc, what); }
   void check_group(int rc, const char *what) const;
   void make_shards(const niqki_params &p, int device, int n_gpus, const uint8_t *dump_header);
-  uint32_t per_rank(size_t n) const { return (uint32_t)((n + sh_.size() - 1) / sh_.size()); }
-  // multi-GPU: hits of a batch whose entries sit in the shards' staged batches (n_entry[r] of rank r)
-  void group_query_staged(uint32_t per, const std::vector<uint32_t> &n_entry, Hits &h);
   niqki_index *h_ = nullptr;            // shard 0 (the only one with one GPU)
   std::vector<niqki_index *> sh_;       // all shards, rank order
   niqki_group *grp_ = nullptr;          // null with one GPU
-  // whole-file queries: where flush_query hands a batch's hits (for_each_batch: a writer thread formats and writes them
-  // while the next batch is on the GPU); empty: written on the spot
-  std::function<void(std::unique_ptr<Hits>)> hits_sink_;
+  HitsWriter *writer_ = nullptr;        // whole-file queries: where flush_query hands a batch's hits (for_each_batch)
   double t_stage_ = 0, t_dev_ = 0, t_out_ = 0;  // NIQKI_HOST_TIMING: copy + frame / sketch + insert or query / output text
 };
 

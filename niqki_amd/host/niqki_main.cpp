@@ -269,6 +269,29 @@ void run_matrix(nqhost::Index &ix, const Parsed &o, RunClock &clk) {
 
 int int_opt(const Parsed &o, Opt id, int dflt) { return o.has(id) ? atoi(o.last(id).c_str()) : dflt; }
 
+// Which options need which optional calls of the engine (nqhost::Index::lacks), in the order a run is refused for
+// them: a row per Feature, in its order.
+using Feature = nqhost::Index::Feature;
+const struct { Opt asked_by[3]; Feature feature; } kNeeds[] = {
+    {{MERGE, MERGE, MERGE}, Feature::APPEND},
+    {{NOVEL, NOVEL, NOVEL}, Feature::DEREPLICATION_FROM},
+    {{NOVEL, REMOVE, DEREP_DUMP}, Feature::RETAIN},
+    {{NEIGHBORS, CLUSTER, CLUSTER}, Feature::SELF_JOIN},
+    {{DEREP, DEREP_DUMP, DEREP_DUMP}, Feature::DEREPLICATION},
+    {{MST, LINKAGE, TREE}, Feature::LINKAGE},
+    {{LCA, LCA, LCA}, Feature::LCA},
+    {{COVER, COVER, COVER}, Feature::COVER},
+    {{COLLAPSE, COLLAPSE, COLLAPSE}, Feature::COLLAPSE},
+};
+// the text of the first row in [first, last] that the options ask for and the engine lacks, else null (main has
+// refusals of its own between the rows: the loop runs over one stretch of them at a time)
+const char *engine_lacks(const Parsed &o, Feature first, Feature last) {
+  for (size_t r = (size_t)first; r <= (size_t)last; ++r)
+    for (Opt opt : kNeeds[r].asked_by)
+      if (const char *text = o.has(opt) ? nqhost::Index::lacks(kNeeds[r].feature) : nullptr) return text;
+  return nullptr;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[]) {
@@ -305,43 +328,16 @@ int main(int argc, char *argv[]) {
     top_k = (uint32_t)v;
   }
 
+  const auto refused = [](const char *text) {
+    cerr << "niqki: " << text << endl;
+    return EXIT_FAILURE;
+  };
   // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts; and only a
   // single-GPU index can drop genomes or take the genomes of a dump
   const bool linkage = o.has(MST) || o.has(LINKAGE) || o.has(TREE);
-  if (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL) || linkage) {
-    if (n_gpus > 1) {
-      cerr << "niqki: the self-join (--neighbors, --cluster, --derep), dropping genomes and merging dumps (--merge, --novel) need a single-GPU index (--gpus 1)" << endl;
-      return EXIT_FAILURE;
-    }
-    if (o.has(MERGE) && !nqhost::Index::has_append()) {
-      cerr << "niqki: this engine cannot merge dumps" << endl;
-      return EXIT_FAILURE;
-    }
-    if (o.has(NOVEL) && !nqhost::Index::has_dereplication_from()) {
-      cerr << "niqki: this engine has no dereplication" << endl;
-      return EXIT_FAILURE;
-    }
-    if (o.has(NOVEL) && !nqhost::Index::has_retain()) {
-      cerr << "niqki: this engine cannot drop genomes" << endl;
-      return EXIT_FAILURE;
-    }
-    if ((o.has(REMOVE) || o.has(DEREP_DUMP)) && !nqhost::Index::has_retain()) {
-      cerr << "niqki: this engine cannot drop genomes" << endl;
-      return EXIT_FAILURE;
-    }
-    if ((o.has(NEIGHBORS) || o.has(CLUSTER)) && !nqhost::Index::has_self_join()) {
-      cerr << "niqki: this engine has no self-join" << endl;
-      return EXIT_FAILURE;
-    }
-    if ((o.has(DEREP) || o.has(DEREP_DUMP)) && !nqhost::Index::has_dereplication()) {
-      cerr << "niqki: this engine has no dereplication" << endl;
-      return EXIT_FAILURE;
-    }
-    if (linkage && !nqhost::Index::has_linkage()) {
-      cerr << "niqki: this engine has no linkage" << endl;
-      return EXIT_FAILURE;
-    }
-  }
+  if (n_gpus > 1 && (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL) || linkage))
+    return refused("the self-join (--neighbors, --cluster, --derep), dropping genomes and merging dumps (--merge, --novel) need a single-GPU index (--gpus 1)");
+  if (const char *text = engine_lacks(o, Feature::APPEND, Feature::LINKAGE)) return refused(text);
 
   // --lca-top: thousandths of the best count, a plain integer
   uint32_t lca_permille = 100;
@@ -359,50 +355,21 @@ int main(int argc, char *argv[]) {
   }
   // the taxon is folded on one device from whole counts
   if (o.has(LCA)) {
-    if (n_gpus > 1) {
-      cerr << "niqki: --lca needs a single-GPU index (--gpus 1)" << endl;
-      return EXIT_FAILURE;
-    }
-    if (o.has(COVER)) {
-      cerr << "niqki: --lca and --cover both replace a query's list: choose one" << endl;
-      return EXIT_FAILURE;
-    }
-    if (!nqhost::Index::has_lca()) {
-      cerr << "niqki: this engine has no LCA query" << endl;
-      return EXIT_FAILURE;
-    }
+    if (n_gpus > 1) return refused("--lca needs a single-GPU index (--gpus 1)");
+    if (o.has(COVER)) return refused("--lca and --cover both replace a query's list: choose one");
+    if (const char *text = engine_lacks(o, Feature::LCA, Feature::LCA)) return refused(text);
   }
-
-  if (o.has(COLLAPSE) && o.has(COVER)) {
-    cerr << "niqki: --collapse and --cover both replace a query's list: choose one" << endl;
-    return EXIT_FAILURE;
-  }
+  if (o.has(COLLAPSE) && o.has(COVER)) return refused("--collapse and --cover both replace a query's list: choose one");
   // the cover reads whole counts and the winner's column of a device-resident sketch store
   if (o.has(COVER)) {
-    if (n_gpus > 1) {
-      cerr << "niqki: --cover needs a single-GPU index (--gpus 1)" << endl;
-      return EXIT_FAILURE;
-    }
-    if (resident_mib > 0) {
-      cerr << "niqki: --cover needs a resident index (--resident-mib 0): a paged index keeps its sketch store in host memory" << endl;
-      return EXIT_FAILURE;
-    }
-    if (!nqhost::Index::has_cover()) {
-      cerr << "niqki: this engine has no cover" << endl;
-      return EXIT_FAILURE;
-    }
+    if (n_gpus > 1) return refused("--cover needs a single-GPU index (--gpus 1)");
+    if (resident_mib > 0) return refused("--cover needs a resident index (--resident-mib 0): a paged index keeps its sketch store in host memory");
+    if (const char *text = engine_lacks(o, Feature::COVER, Feature::COVER)) return refused(text);
   }
-
   // the collapsed list is selected on one device from whole counts
   if (o.has(COLLAPSE) && !o.has(LCA)) {   // (beside --lca the file supplies the labels only: no collapsed query runs)
-    if (n_gpus > 1) {
-      cerr << "niqki: --collapse needs a single-GPU index (--gpus 1)" << endl;
-      return EXIT_FAILURE;
-    }
-    if (!nqhost::Index::has_collapse()) {
-      cerr << "niqki: this engine has no collapsed query" << endl;
-      return EXIT_FAILURE;
-    }
+    if (n_gpus > 1) return refused("--collapse needs a single-GPU index (--gpus 1)");
+    if (const char *text = engine_lacks(o, Feature::COLLAPSE, Feature::COLLAPSE)) return refused(text);
   }
 
   const char *rule = "+-----------------------------------+-------------------------------+";
