@@ -105,6 +105,9 @@ __device__ __forceinline__ void walk64(const uint16_t *gl, uint32_t a, uint32_t 
 // take their chunk's position straight from the wave's LDS queue (one ds_read_b32 per load, its queue
 // slot in the instruction's offset field) instead of a v_readlane + s_lshl per line.  Per line now:
 // 0.5 load, 0.5 LDS read, ~5 vector ALU ops, 1 LDS atomic per lane and id (2 per load).
+// Beside the sketch kernel the launch runs on a quarter of the CUs and the CU's LDS pipe counts: an atomic costs what its
+// active lanes and their bank conflicts cost (tools/ubench_lds_atomics.hip, rows 6 and 7), so the lanes that hold nothing
+// but padding ids (39 % at the bench's fill) leave both atomics of their load (apply).
 template <int UNROLL>
 struct PairWalk {
   static_assert(UNROLL == 16 || UNROLL == 32, "a round is UNROLL lines = UNROLL / 2 loads; two or four rounds per batch");
@@ -113,9 +116,12 @@ struct PairWalk {
   uint32_t half;                         // lane >> 5: which chunk of a pair this lane reads
   uint32_t ga[L], gb[L];
 
-  __device__ __forceinline__ void init(const uint16_t *gl, uint32_t lane) {
+  uint32_t tile;                         // ids from here on are padding ids (IndexView::padded)
+
+  __device__ __forceinline__ void init(const uint16_t *gl, uint32_t lane, uint32_t tile_ids) {
     lane_base = (const uint8_t *)gl + (lane & 31u) * 4u;
     half = lane >> 5;
+    tile = tile_ids;
   }
   // loads of the chunks [j0, j0 + UNROLL) of the batch whose items start at `items` (LDS, this wave's queue)
   __device__ __forceinline__ void fetch(uint32_t (&g)[L], const Item *items, uint32_t j0) {
@@ -139,16 +145,22 @@ struct PairWalk {
       // (profiles/r03_opcode_costs.txt).
       uint32_t even, addr, odd, inc, hi;
       asm("v_and_b32 %0, 0xfffe, %1" : "=v"(even) : "v"(g[k]));
-      asm("v_add_u32 %0, %1, %1" : "=v"(addr) : "v"(even));
-      asm("v_and_b32 %0, 1, %1" : "=v"(odd) : "v"(g[k]));
-      asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(inc) : "v"(odd), "s"(0xFFFFu));
-      __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      asm("v_lshrrev_b32 %0, 16, %1" : "=v"(hi) : "v"(g[k]));
-      asm("v_and_b32 %0, 0xfffe, %1" : "=v"(even) : "v"(hi));
-      asm("v_add_u32 %0, %1, %1" : "=v"(addr) : "v"(even));
-      asm("v_and_b32 %0, 1, %1" : "=v"(odd) : "v"(hi));
-      asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(inc) : "v"(odd), "s"(0xFFFFu));
-      __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      // A chunk's ids stand at the front of its line, padding ids (tile + 2 * position, the tile even) behind them: a
+      // dword whose first id is a padding id lies wholly beyond the chunk's length, and its lane leaves both atomics
+      // (it would add to dummy words that nobody reads).  The lane with the last id of an odd-length chunk stays, its
+      // second id lands in the dummy words as before; a "no chunk" line of the last batch has no lane left.
+      if (even < tile) {
+        asm("v_add_u32 %0, %1, %1" : "=v"(addr) : "v"(even));
+        asm("v_and_b32 %0, 1, %1" : "=v"(odd) : "v"(g[k]));
+        asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(inc) : "v"(odd), "s"(0xFFFFu));
+        __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        asm("v_lshrrev_b32 %0, 16, %1" : "=v"(hi) : "v"(g[k]));
+        asm("v_and_b32 %0, 0xfffe, %1" : "=v"(even) : "v"(hi));
+        asm("v_add_u32 %0, %1, %1" : "=v"(addr) : "v"(even));
+        asm("v_and_b32 %0, 1, %1" : "=v"(odd) : "v"(hi));
+        asm("v_mad_u32_u24 %0, %1, %2, 1" : "=v"(inc) : "v"(odd), "s"(0xFFFFu));
+        __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)addr, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
     }
   }
   // 64 chunks: items[0 .. 64) of the wave's queue; all their lines in flight before the first id is counted
@@ -200,7 +212,7 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
   constexpr bool PAIR = PAD && (UNROLL == 16 || UNROLL == 32);
   uint32_t prio_turn = wave >> 2;   // the four waves of a SIMD take turns at the issue arbiter's top priority (PAIR)
   PairWalk<PAIR ? UNROLL : 32> pw;
-  pw.init(gl, lane);
+  pw.init(gl, lane, v.tile);
 
   struct Look { Entry e[NE]; };
   // HM: a single-tile index with its per-slot class mask (IndexView::hmask): a fingerprint whose class holds no

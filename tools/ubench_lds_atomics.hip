@@ -8,6 +8,10 @@
 //   form 3: ds_add_rtn_u32, random words (what byte counters with a wrap test would need)
 //   form 4: ds_read_b32, random words (for comparison)
 //   form 5: ds_add_u32 random + the walk's 5 vector ops per id in between (address and increment from the id)
+//   form 6: ds_add_u32, random words, lanes 20..31 and 52..63 switched off in the exec mask (the padding lanes of an
+//           average line pair: lines are 61 % full)
+//   form 7: the same lanes active on dummy words of their own (what the walk did before its padding lanes left)
+//   form 8: ds_read_b32, all lanes of a half-wave read one word (the walk's chunk position from the wave's queue)
 // Prints SIMD cycles per wave-instruction and CU, and wave-instructions per microsecond and CU.
 // Build: hipcc -O3 --offload-arch=gfx950 tools/ubench_lds_atomics.hip -o tools/bin/ubench_lds_atomics
 // Measurement aid for DESIGN.md 4.4; not part of the product.
@@ -37,15 +41,18 @@ __global__ __launch_bounds__(1024) void atom_kernel(uint32_t iters, uint32_t *si
     uint32_t w = mix32(blockIdx.x * 7919u + tid * 16u + (uint32_t)k) % kWords;
     if (FORM == 1) w = (tid + 1024u * (uint32_t)k) % kWords;
     if (FORM == 2 && (lane & 1u)) w = kWords + (lane >> 1);
+    if (FORM == 7 && (lane & 31u) >= 20u) w = kWords + lane;
+    if (FORM == 8) w = mix32(blockIdx.x * 7919u + (tid >> 5) * 16u + (uint32_t)k) % kWords;
     a[k] = w * 4u;
   }
   uint32_t acc = 0;
+  if (FORM == 6 && (lane & 31u) >= 20u) iters = 0;   // these lanes sit out: the loop runs under a partial exec mask
   for (uint32_t it = 0; it < iters; ++it) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       if (FORM == 3) {
         acc += __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)a[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      } else if (FORM == 4) {
+      } else if (FORM == 4 || FORM == 8) {
         acc += *(volatile lds_u32 *)(uintptr_t)a[k];
       } else if (FORM == 5) {
         // the walk's per-id work: word address and increment from a 16-bit id (here: the stored address plays the id)
@@ -94,6 +101,9 @@ int main() {
   run<3>("3: ds_add_rtn_u32, random words", sink);
   run<4>("4: ds_read_b32, random words", sink);
   run<5>("5: ds_add_u32 random + the walk's 4 vector ops per id", sink);
+  run<6>("6: ds_add_u32, random words, lanes 20-31 and 52-63 off in the exec mask", sink);
+  run<7>("7: ds_add_u32, random words, lanes 20-31 and 52-63 on dummy words of their own", sink);
+  run<8>("8: ds_read_b32, one word per half-wave (the queue's chunk position)", sink);
   (void)hipFree(sink);
   return 0;
 }
