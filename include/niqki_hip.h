@@ -885,6 +885,10 @@ int niqki_group_staged_query(niqki_group *g, uint32_t per, const uint32_t *n_ent
  * NT = -1 look-ups from the pre-pass, 2..4 the stash form of that many tiles, 1 one look-up per tile; PAD = 1
  * the padded walk was launched, which takes "bucket_align_log2" 6 and a 1024-thread shape; option
  * "gather_variant" 1..5 = BLOCK, UNROLL 1024, 8 / 1024, 32 / 512, 16 / 256, 16 / 128, 16),
+ * "last_densify_form" (the densification the last niqki_sketch / niqki_densify / staged sketch call chose: 0 = none
+ * yet or an empty batch, 1 = the one-wavefront short-record kernel, 2 = plain passes inside the sketch kernel,
+ * 3 = passes over distinct values inside the sketch kernel, 4 = distinct-value passes as a launch of its own,
+ * 5 = the global-memory launch of sketches whose cells do not fit LDS; where a batch takes several launches, the first one's),
  * "bucket_align_log2" (the built index's bucket alignment, as set by the option or chosen from the tile size),
  * "last_hits_form" (1 =the last niqki_query* call took the hit-list form, option "hit_lists"), "class_mask" (1 = the built index carries its per-slot class mask: single-tile
  * indexes; the gather kernel then looks up only fingerprints whose sixteenth of the

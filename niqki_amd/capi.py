@@ -830,6 +830,10 @@ class Engine:
         self._ck(self.L.niqki_sketch(self.h, _p(seqs), _p(rec_off), n_rec, _p(entry_rec),
                                      n_rec if n_entry is None else n_entry, _p(sketches), MEM_DEVICE))
 
+    def densify_dev(self, sketches, n):
+        """niqki_densify in place on n rows of device memory (on the handle's stream)."""
+        self._ck(self.L.niqki_densify(self.h, _p(sketches), n, MEM_DEVICE))
+
     def insert_dev(self, sketches, n):
         self._ck(self.L.niqki_insert(self.h, _p(sketches), n, MEM_DEVICE))
 

@@ -632,6 +632,7 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!std::strcmp(key, "tiles")) { *value = ix->n_tiles; return NIQKI_OK; }
   if (!std::strcmp(key, "class_mask")) { *value = (ix->built && ix->hmask_ok) ? 1 : 0; return NIQKI_OK; }
   if (!std::strcmp(key, "last_gather_form")) { *value = ix->last_form; return NIQKI_OK; }
+  if (!std::strcmp(key, "last_densify_form")) { *value = ix->last_densify_form; return NIQKI_OK; }
   if (!std::strcmp(key, "last_gather_kernel")) { *value = ix->last_kernel; return NIQKI_OK; }
   if (!std::strcmp(key, "bucket_align_log2")) { *value = ix->align_log2; return NIQKI_OK; }
   if (!std::strcmp(key, "last_hits_form")) { *value = ix->last_hits_form; return NIQKI_OK; }

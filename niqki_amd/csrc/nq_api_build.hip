@@ -61,6 +61,7 @@ int reserve_store(niqki_index *ix, uint64_t want) {
 // Launches the sketch kernel(s) on device-resident inputs.
 int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, uint32_t n_rec,
                const uint32_t *entry_rec, uint32_t n_entry, int32_t *sketches, uint64_t total_bytes) {
+  ix->last_densify_form = 0;
   if (n_entry == 0) return NIQKI_OK;
   nq::SketchArgs a;
   a.d = ix->d;
@@ -90,7 +91,7 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
     b.splits = 1;
     b.accumulate = 1;
     b.densify = 1;
-    NQ_HIP(ix, nq::launch_sketch(b, n_entry, (uint64_t)1 << 22, ix->stream));
+    NQ_HIP(ix, nq::launch_sketch(b, n_entry, (uint64_t)1 << 22, ix->stream, &ix->last_densify_form));
   } else if (const uint32_t list = nq::sketch_read_list(ix->d, avg)) {
     // Short records: the one-wavefront kernel, with its 192-entry list (nine sketches per CU) where the average record
     // has at most 200 bases.  A record with more occupied cells than the list holds -- far longer than the batch's
@@ -104,18 +105,18 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
     a.redo = (uint32_t *)flags.p;
     if (list < 384) {
       a.redo_only = 0; a.redo_mark = 1;
-      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream));
+      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream, &ix->last_densify_form));
       a.redo_only = 1; a.redo_mark = 2;
       NQ_HIP(ix, nq::launch_sketch(a, n_entry, 400, ix->stream));   // (an average that takes the long list)
     } else {
       a.redo_only = 0; a.redo_mark = 2;
-      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream));
+      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream, &ix->last_densify_form));
     }
     a.redo_only = 2; a.redo_mark = 0;
     NQ_HIP(ix, nq::launch_sketch(a, n_entry, nq::kSketchWorkgroupLen, ix->stream));
   } else {
     Span sp(ix, NIQKI_KC_SKETCH);
-    NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream));
+    NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream, &ix->last_densify_form));
   }
   (void)n_rec;
   return NIQKI_OK;
@@ -367,6 +368,7 @@ int niqki_sketch(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, 
 int niqki_densify(niqki_index *ix, int32_t *sketches, uint32_t n, int mem) {
   if (!ix || (!sketches && n)) return NIQKI_E_INVALID;
   NQ_HIP(ix, hipSetDevice(ix->device));
+  ix->last_densify_form = 0;
   if (n == 0) return NIQKI_OK;
   int32_t *d_sk = sketches;
   const size_t bytes = (size_t)n * ix->d.F * 4;
@@ -390,7 +392,7 @@ int niqki_densify(niqki_index *ix, int32_t *sketches, uint32_t n, int mem) {
   {
     Span sp(ix, NIQKI_KC_DENSIFY);
     // (an average that picks the one-wavefront kernel with its long entry list)
-    NQ_HIP(ix, nq::launch_sketch(a, n, ix->d.F <= 4096 ? 256 : ((uint64_t)1 << 22), ix->stream));
+    NQ_HIP(ix, nq::launch_sketch(a, n, ix->d.F <= 4096 ? 256 : ((uint64_t)1 << 22), ix->stream, &ix->last_densify_form));
   }
   if (mem == NIQKI_MEM_HOST) {
     NQ_HIP(ix, hipMemcpyAsync(sketches, d_sk, bytes, hipMemcpyDeviceToHost, ix->stream));
@@ -442,6 +444,7 @@ int niqki_get_sketches(niqki_index *ix, uint32_t begin, uint32_t n, int32_t *ske
   if (!ix || (!sketches && n)) return NIQKI_E_INVALID;
   if ((uint64_t)begin + n > ix->n_genomes) return fail(ix, NIQKI_E_INVALID, "genome range out of bounds");
   NQ_HIP(ix, hipSetDevice(ix->device));
+  ix->last_densify_form = 0;
   if (n == 0) return NIQKI_OK;
   int32_t *d_sk = sketches;
   const size_t bytes = (size_t)n * ix->d.F * 4;

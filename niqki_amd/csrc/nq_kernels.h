@@ -27,9 +27,18 @@ struct SketchArgs {
   uint32_t redo_mark;         // != 0 (one-wavefront kernel): a sketch that exceeds the entry list gets this flag and is left
                               // to a later launch -- nothing of it is stored
 };
-// avg_len: average input bytes per sketch (picks the launch shape)
+// the densification a launch_sketch call chose (stat "last_densify_form")
+enum DensifyForm : uint32_t {
+  kDensifyNone = 0,          // the launch stores the cells as they are
+  kDensifyWave = 1,          // sketch_reads_kernel: entry windows + closed-form tail, or its pass over all cells
+  kDensifyPlain = 2,         // densify_lds inside sketch_kernel
+  kDensifyDistinct = 3,      // densify_lds_distinct inside sketch_kernel
+  kDensifyDistinctLate = 4,  // densify_distinct_kernel, a launch of its own behind sketch_kernel
+  kDensifyGlobal = 5,        // densify_global_kernel (the cells do not fit LDS)
+};
+// avg_len: average input bytes per sketch (picks the launch shape); form (may be nullptr): receives the DensifyForm chosen
 hipError_t launch_sketch(const SketchArgs &a, uint32_t n_entry, uint64_t avg_len,
-                         hipStream_t stream);
+                         hipStream_t stream, uint32_t *form = nullptr);
 hipError_t launch_fill_u32(uint32_t *p, uint64_t n, uint32_t v, hipStream_t stream);
 // 0: launch_sketch would not take the one-wavefront short-record kernel for this average length; else the capacity of
 // the entry list it would take (192 or 384)

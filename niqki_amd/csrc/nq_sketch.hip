@@ -1313,8 +1313,9 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 // to a cell that several entries reach in its pass s*, and only if one of the LOSING ones has won some cell in an
 // earlier pass of the tail: that case (a few reads in a hundred) is detected and handed back to the passes, which
 // are exact for anything -- nothing is written before the check.  Cells no orbit reaches stay empty, as after the F
-// fruitless passes that end the loop (documented divergences).  Pinned by the goldens, tests/test_gpu_fuzz.py,
-// tests/test_gpu_reads_config.py.
+// fruitless passes that end the loop (documented divergences).  Pinned by tests/test_gpu_densify_designed.py
+// (designed cells: every instantiation with and without ties, hand-backs the closed form would get wrong, unreachable
+// cells), the goldens, tests/test_gpu_fuzz.py, tests/test_gpu_reads_config.py.
 constexpr uint32_t kTailCells = 16;   // (8 .. 24 measure the same; 48: 3 % slower)
 
 // T: every entry's target of the NEXT pass, B its stride, mk = 2^31 | the smallest index that holds its value, V its
@@ -1800,12 +1801,16 @@ uint32_t sketch_read_list(const Derived &d, uint64_t avg_len) {
 }
 
 hipError_t launch_sketch(const SketchArgs &a_in, uint32_t n_entry, uint64_t avg_len,
-                         hipStream_t stream) {
+                         hipStream_t stream, uint32_t *form) {
+  uint32_t form_local;
+  if (!form) form = &form_local;
+  *form = kDensifyNone;
   if (n_entry == 0) return hipSuccess;
   SketchArgs a = a_in;
   a.halves = sketch_needs_merge(a.d) ? 2u : 1u;
   if (a.halves > 1) {
     if (a.seqs == nullptr) {  // densify-only launch
+      *form = kDensifyGlobal;
       hipLaunchKernelGGL(densify_global_kernel, dim3(n_entry), dim3(1024), 0, stream, a);
       return hipGetLastError();
     }
@@ -1822,6 +1827,7 @@ hipError_t launch_sketch(const SketchArgs &a_in, uint32_t n_entry, uint64_t avg_
     if (sketch_reads_shape(a.d, avg_len, a.splits, a.halves)) {
       hipError_t e = hipFuncSetAttribute((const void *)sketch_reads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
       if (e != hipSuccess) return e;
+      *form = a.densify ? kDensifyWave : kDensifyNone;
       hipLaunchKernelGGL(sketch_reads_kernel, dim3(n_entry), dim3(64), wl, stream, a);
       return hipGetLastError();
     }
@@ -1855,6 +1861,9 @@ hipError_t launch_sketch(const SketchArgs &a_in, uint32_t n_entry, uint64_t avg_
   const bool late_distinct = a.densify && !a.distinct && regular && own_cells && avg_len < (1u << 19) && a.halves == 1 && a.splits == 1 &&
                              4u * a.d.R <= a.d.F && a.d.R <= (uint32_t)kLateValues * 1024u && late_lds <= kLdsLimit;
   if (late_distinct) a.densify = 0;
+  // (a part of a split record and a half of the slots are merged in global memory, not densified)
+  *form = late_distinct ? kDensifyDistinctLate
+          : !(a.densify && a.splits == 1 && a.halves == 1) ? kDensifyNone : a.distinct ? kDensifyDistinct : kDensifyPlain;
   const size_t lds = sketch_lds_bytes(a.d, a.distinct != 0, a.filter ? (short_records ? 4 : 16) : 0, a.halves);
   if (lds > kLdsLimit) return hipErrorInvalidValue;   // (cells, stacks and leveling words: S <= 15 per half fits)
   dim3 grid(n_entry * a.splits * a.halves);

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 E_INVALID = 1
 
 HANDLE_KEYS = [
-    "store_bytes", "index_bytes", "delta_genomes", "tiles", "class_mask", "last_gather_form", "last_gather_kernel",
+    "store_bytes", "index_bytes", "delta_genomes", "tiles", "class_mask", "last_gather_form", "last_gather_kernel", "last_densify_form",
     "bucket_align_log2", "last_hits_form", "labels", "taxa", "taxonomy_depth", "retain_us_rank", "retain_us_compact",
     "inflate_files_in_flight", "inflate_files_in_flight_8k", "page_slots", "pages",
 ]
@@ -29,7 +29,7 @@ CALL_KEYS = [
 
 
 def test_every_stat_key_answers_on_a_fresh_handle(native):
-    assert len(set(HANDLE_KEYS + CALL_KEYS)) == len(HANDLE_KEYS) + len(CALL_KEYS) == 55
+    assert len(set(HANDLE_KEYS + CALL_KEYS)) == len(HANDLE_KEYS) + len(CALL_KEYS) == 56
     e = native.Engine(K=31, S=S, W=W, H=3, min_score_value=50, tile_genomes=0, resident_mib=0, top_k=0)
     v = C.c_uint64(0)
     for key in HANDLE_KEYS + CALL_KEYS:

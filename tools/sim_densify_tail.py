@@ -5,6 +5,7 @@ windows of 8 passes until at most 16 cells are empty, then once by the passes to
 the kernel's rule for ties (a cell that several entries reach in its pass goes to the smallest index at the START of
 the tail; the read is handed back when a losing entry has won a cell in an earlier pass of the tail).  Prints how
 many reads had a tail, how many were handed back, and the mismatches (must be 0).  CPU only; uses the oracle's hashes.
+The closed form's arithmetic is that of tests/densify_ref.py (solve_tail), which the designed-cell tests share.
 
     python tools/sim_densify_tail.py [S] [W] [reads]"""
 import os
@@ -12,8 +13,10 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from oracle import pyoracle as po
+from densify_ref import solve_tail
 S=int(sys.argv[1]) if len(sys.argv)>1 else 12
 W=int(sys.argv[2]) if len(sys.argv)>2 else 10
 NR=int(sys.argv[3]) if len(sys.argv)>3 else 200
@@ -36,10 +39,6 @@ def passes(cells, ent, start, stop_at):
             cells[t]=e['v']; e['mk']=min(e['mk'],t)
         idle = 0 if prop else idle+1
         s+=1
-def inv_odd(o):
-    x=o
-    for _ in range(3): x=(x*(2-o*x)) & 0xFFFFFFFF
-    return x
 nb=0; nt=0; bad_exact=0; tailed=0
 for r in range(NR):
     L=int(rng.integers(60,300))
@@ -67,30 +66,13 @@ for r in range(NR):
     # reference continuation
     ref=cells.copy(); ent_ref=[dict(e) for e in ent]
     passes(ref,ent_ref,s,0)
-    # closed form
+    # closed form: targets of the next pass, strides and indexes as they are at the start of the tail
     empt=np.nonzero(cells<0)[0]
-    res={}
-    win_min={id(e):1<<60 for e in ent}; lose_max={id(e):-1 for e in ent}
-    for c in empt:
-        keys=[]
-        for e in ent:
-            T=(e['A']+s*e['B'])&0xFFFFFFFF
-            b=e['B']&Fm
-            j=((b|F)&-(b|F)).bit_length()-1
-            odd=((e['B']>>j)|1)&0xFFFFFFFF
-            x=(int(c)-T)&0xFFFFFFFF
-            if x & ((1<<j)-1): continue
-            sv=((x*inv_odd(odd))&Fm)>>j
-            keys.append(((sv<<15)|e['mk'],e))
-        if not keys: continue
-        keys.sort(key=lambda t:t[0])
-        wkey,we=keys[0]; sstar=wkey>>15
-        res[int(c)]=we['v']; win_min[id(we)]=min(win_min[id(we)],sstar)
-        for k,e in keys[1:]:
-            if k>>15==sstar: lose_max[id(e)]=max(lose_max[id(e)],sstar); nt+=1
-    bail=any(win_min[id(e)]<lose_max[id(e)] for e in ent)
+    writes,ties,unreach,bail=solve_tail(empt,[(e['A']+s*e['B'])&0xFFFFFFFF for e in ent],[e['B'] for e in ent],[e['mk'] for e in ent],F)
+    nt+=ties
+    res={c:ent[k]['v'] for c,k in writes.items()}
     if bail: nb+=1; continue
     out=cells.copy()
     for c,v in res.items(): out[c]=v
     if not np.array_equal(out,ref): bad_exact+=1
-print("S=%d W=%d reads with a tail %d, bails %d, tied losers %d, MISMATCH %d"%(S,W,tailed,nb,nt,bad_exact))
+print("S=%d W=%d reads with a tail %d, bails %d, cells with ties %d, MISMATCH %d"%(S,W,tailed,nb,nt,bad_exact))
