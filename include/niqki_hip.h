@@ -687,6 +687,66 @@ int niqki_query_lca(niqki_index *ix, const int32_t *sketches, uint32_t nq, uint3
 int niqki_staged_query_lca(niqki_index *ix, uint32_t top_permille, uint32_t *taxon, uint32_t *best_count,
                            uint32_t *best_gid, uint32_t *considered, int mem);
 
+/* Taxon tally: the rows of the LCA calls counted per taxon and per clade on the device -- what a read classifier's
+ * report holds.  The LCA calls answer per query; a read set asks how many reads landed ON each taxon and how many in
+ * the clade BELOW it.  The rows are on the device already and so is the taxonomy; the tally is an accumulator beside
+ * them, and a caller in NIQKI_MEM_DEVICE reads back 32 bytes per taxon instead of 16 bytes per read.  It counts nothing
+ * new in the index and touches no gather or hit kernel: its answer is a pure function of rows the LCA calls return.
+ * State.  A handle has at most one tally; it belongs to the handle's taxonomy.  niqki_tally_begin allocates and clears
+ * the accumulators for n_taxa taxa and opens the tally; on an open or broken tally it clears and reopens it; without
+ * a taxonomy it returns NIQKI_E_STATE and niqki_last_error says to set one; on a slot-range shard NIQKI_E_STATE, as the
+ * LCA calls.  niqki_tally_end discards the tally (NIQKI_OK also when none is open).  Whatever replaces or drops the
+ * taxonomy ends the tally: a successful niqki_set_taxonomy (set or remove) and every call that drops the taxonomy
+ * (inserts, a committed niqki_append_*, niqki_retain, import); a refused niqki_set_taxonomy leaves it alone.
+ * niqki_tally_add and niqki_tally_read without a tally return NIQKI_E_STATE.
+ * Rows.  A row is (taxon, best_count, considered) as the LCA calls write them.  taxon < n_taxa: classified,
+ * direct[taxon] += 1 and direct_best[taxon] += best_count.  taxon == NIQKI_TAXON_NONE and considered == 0: no_hit.
+ * taxon == NIQKI_TAXON_NONE and considered >= 1: no_common.  Anything else is a bad row: it is never used as an index,
+ * the call returns NIQKI_E_INVALID, niqki_last_error gives the number of bad rows, and the tally becomes BROKEN,
+ * because the good rows of that call have already been added.  niqki_tally_add: best_count == NULL counts as all
+ * zeros, considered == NULL counts every NONE row as no_hit, n == 0 adds nothing; mem names the space of the three
+ * arrays.  Host arrays are staged by the library and the call synchronises.  Device arrays are read in stream order and
+ * the call does not synchronise, so bad rows among them are reported by the next niqki_tally_read, which returns
+ * NIQKI_E_INVALID and breaks the tally then.
+ * While a tally is open every niqki_query_lca and niqki_staged_query_lca on the handle adds each row it returns,
+ * exactly once: in both memory spaces, for every batch and every halved leaf, and whichever of the three optional
+ * output arrays the caller left NULL (the library keeps those rows in a workspace of its own).  The rows the caller gets
+ * are unchanged.  A call refused before its first batch (a bad top_permille, a missing taxonomy, an argument error)
+ * adds nothing and leaves the tally usable; a call that fails later marks it broken.  On a broken tally
+ * niqki_tally_read and niqki_tally_add return NIQKI_E_STATE and niqki_last_error says why; niqki_tally_begin starts
+ * afresh.  Plain, collapsed, cover and self-join calls are never tallied; groups, the _shared calls and the _ahead
+ * calls have no tally because they have no LCA form.
+ * Read.  niqki_tally_read leaves the tally open: more rows may follow, and a second read without new rows returns the
+ * same bytes.  With sub(t) = t and all its descendants under parent: clade[t] = the sum of direct[u] over u in sub(t),
+ * clade_best[t] = the sum of direct_best[u] over u in sub(t).  Each of the four arrays has n_taxa entries in `mem` and
+ * may be NULL; totals is host memory whatever mem is and may be NULL.  The call synchronises.
+ * Always: queries = classified + no_hit + no_common; the sum of direct = classified; the sum of clade over the roots =
+ * classified; clade[t] >= direct[t].  All sums are exact 64-bit integers.  The result is a function of the multiset of
+ * rows and the taxonomy only: call boundaries, batch size, memory space, "lca_wave_cap", splits and the order in which
+ * the device adds do not change it.
+ * Stats: "tally" = 0 none, 1 open, 2 broken; "tally_queries" = the rows added as of the last read (0 without a tally);
+ * while profiling is on "tally_us_add" (the row kernel of the last LCA or add call) and "tally_us_clade" (the last
+ * read), microseconds.
+ * How: tally_rows_kernel gives a 256-thread workgroup passes of 1024 rows.  A pass is entered into an open-addressing
+ * table in LDS keyed by taxon (2048 slots of {key, count, best sum}, 32 KiB; LDS atomics; probing bounded by the table
+ * size, which a pass cannot fill); after a barrier every occupied slot leaves with one 64-bit global atomic per array
+ * and is cleared -- a read set that sends most of a batch to one taxon costs that taxon's cache line one add per pass,
+ * not one per read.  Rows without a taxon and bad rows are counted per workgroup and leave once.  At read,
+ * tally_clade_kernel takes a thread per taxon with direct > 0 and walks to its root, adding at every node, at most
+ * "taxonomy_depth" + 1 steps.  Device state: 32 bytes per taxon and four words.  DESIGN.md 4.5g. */
+typedef struct niqki_tally_totals {
+  uint64_t queries;     /* rows added */
+  uint64_t classified;  /* rows with a taxon */
+  uint64_t no_hit;      /* NIQKI_TAXON_NONE, considered == 0 */
+  uint64_t no_common;   /* NIQKI_TAXON_NONE, considered >= 1 */
+} niqki_tally_totals;
+int niqki_tally_begin(niqki_index *ix);
+int niqki_tally_add(niqki_index *ix, const uint32_t *taxon, const uint32_t *best_count, const uint32_t *considered,
+                    uint32_t n, int mem);
+int niqki_tally_read(niqki_index *ix, uint64_t *direct, uint64_t *clade, uint64_t *direct_best,
+                     uint64_t *clade_best, niqki_tally_totals *totals, int mem);
+int niqki_tally_end(niqki_index *ix);
+
 /* Drops genomes from the index.  keep: niqki_genome_count(ix) bytes, nonzero = the genome stays.  new_ids (may be
  * NULL; same length, same `mem` space) receives every old genome's new id, 0xFFFFFFFF for a dropped one; *n_kept (may
  * be NULL, host memory whatever mem is) the number of genomes left.  mem as in niqki_cluster: NIQKI_MEM_DEVICE uses

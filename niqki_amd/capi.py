@@ -52,6 +52,13 @@ class StageInfo(C.Structure):
                 ("seq_bytes", C.c_uint64)]
 
 
+class TallyTotals(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("classified", C.c_uint64), ("no_hit", C.c_uint64), ("no_common", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 def lib_path():
     return _LIB
 
@@ -129,6 +136,10 @@ ABI = [
     ("niqki_set_taxonomy", _int, [_vp, _vp, _u32, _vp, _u32, _int]),
     ("niqki_query_lca", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _int]),
     ("niqki_staged_query_lca", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _int]),
+    ("niqki_tally_begin", _int, [_vp]),
+    ("niqki_tally_add", _int, [_vp, _vp, _vp, _vp, _u32, _int]),
+    ("niqki_tally_read", _int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(TallyTotals), _int]),
+    ("niqki_tally_end", _int, [_vp]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
@@ -714,6 +725,33 @@ class Engine:
         return self._lca(lambda t, bc, bg, co: self.L.niqki_staged_query_lca(
             self.h, int(top_permille), t, bc, bg, co, MEM_HOST), self._staged.n_entry, details)
 
+    def tally_begin(self):
+        """niqki_tally_begin: opens (or clears and reopens) the handle's taxon tally; it needs a taxonomy.  While it is
+        open every query_lca / staged_query_lca adds the rows it returns."""
+        self._ck(self.L.niqki_tally_begin(self.h))
+
+    def tally_add(self, taxon, best_count=None, considered=None):
+        """niqki_tally_add: rows (taxon, best_count, considered) as numpy arrays into the open tally; best_count None
+        counts as zeros, considered None counts every TAXON_NONE row as a row without a hit."""
+        t = np.ascontiguousarray(taxon, dtype=np.uint32).reshape(-1)
+        rest = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (best_count, considered)]
+        if any(x is not None and x.size != t.size for x in rest):
+            raise ValueError("tally_add: the arrays differ in length")
+        self._ck(self.L.niqki_tally_add(self.h, _p(t) if t.size else None, *[_p(x) if t.size else None for x in rest], t.size, MEM_HOST))
+
+    def tally_read(self):
+        """niqki_tally_read: (direct, clade, direct_best, clade_best, totals), four uint64 arrays of one entry per taxon
+        and totals as a dict (queries, classified, no_hit, no_common).  The tally stays open."""
+        n = self.stat("taxa")
+        outs = [np.zeros(n, dtype=np.uint64) for _ in range(4)]
+        totals = TallyTotals()
+        self._ck(self.L.niqki_tally_read(self.h, *[_p(a) if n else None for a in outs], C.byref(totals), MEM_HOST))
+        return outs[0], outs[1], outs[2], outs[3], totals.as_dict()
+
+    def tally_end(self):
+        """niqki_tally_end: discards the tally; fine when none is open."""
+        self._ck(self.L.niqki_tally_end(self.h))
+
     def retain(self, keep):
         """Drops the genomes whose keep flag (bool or uint8 array, one per genome) is zero: (n_kept, new_ids),
         new_ids[g] = the new id of old genome g (the kept genomes below it), 0xFFFFFFFF for a dropped one.  The handle
@@ -884,6 +922,17 @@ class Engine:
         """niqki_query_lca on device arrays (each of the last three may be None), written in stream order."""
         self._ck(self.L.niqki_query_lca(self.h, _p(sketches), nq, int(top_permille), _p(taxon), _p(best_count), _p(best_gid),
                                         _p(considered), MEM_DEVICE))
+
+    def tally_add_dev(self, taxon, best_count, considered, n):
+        """niqki_tally_add on device arrays of 32-bit elements (the last two may be None), read in stream order; bad
+        rows among them are reported by the next read."""
+        self._ck(self.L.niqki_tally_add(self.h, _p(taxon), _p(best_count), _p(considered), n, MEM_DEVICE))
+
+    def tally_read_dev(self, direct=None, clade=None, direct_best=None, clade_best=None):
+        """niqki_tally_read into device tensors of 64-bit elements, one per taxon (each may be None); returns totals."""
+        totals = TallyTotals()
+        self._ck(self.L.niqki_tally_read(self.h, _p(direct), _p(clade), _p(direct_best), _p(clade_best), C.byref(totals), MEM_DEVICE))
+        return totals.as_dict()
 
     def query_sequences_dev(self, seqs, rec_off, n, hit_off, hc, hg, capacity):
         self._ck(self.L.niqki_query_sequences(self.h, _p(seqs), _p(rec_off), n, None, n, _p(hit_off),

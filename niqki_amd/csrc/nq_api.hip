@@ -382,7 +382,7 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_raw, &ix->ws_wire[0], &ix->ws_wire[1], &ix->ws_redo[0], &ix->ws_redo[1], &ix->ws_fmeta, &ix->ws_summ, &ix->ws_chunk, &ix->ws_fkept, &ix->ws_fnrec,
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
                  &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
-                 &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info,
+                 &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info, &ix->tally_acc, &ix->ws_tally_rows,
                  &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
@@ -619,6 +619,11 @@ const StatKey kCallStats[] = {
     NQ_STAT("lca_no_common", ix->lca_stats.no_common),
     NQ_STAT("lca_us_hits", us(ix->lca_stats.ms[0])),
     NQ_STAT("lca_us_fold", us(ix->lca_stats.ms[1])),
+    // niqki_tally_*
+    NQ_STAT("tally", (uint64_t)ix->tally_state),
+    NQ_STAT("tally_queries", ix->tally_state ? ix->tally_queries : 0),
+    NQ_STAT("tally_us_add", us(ix->tally_ms[0])),
+    NQ_STAT("tally_us_clade", us(ix->tally_ms[1])),
 };
 #undef NQ_STAT
 }  // namespace

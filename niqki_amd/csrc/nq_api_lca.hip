@@ -15,16 +15,18 @@ void drop_taxonomy(niqki_index *ix) {
   ix->tax_set = false;
   ix->n_taxa = 0;
   ix->tax_depth = 0;
+  end_tally(ix);   // (niqki_tally_begin: the tally belongs to the taxonomy)
 }
 
 namespace {
 
 struct Lca {
   niqki_index *ix;
-  PhaseTimer ev;   // events of a leaf: 0-1 hits, 1-2 fold
+  PhaseTimer ev;   // events of a leaf: 0-1 hits, 1-2 fold, 2-3 the rows into an open tally
+  bool tally = false;   // a tally is open: every leaf's rows go into it (out[0], out[1] and out[3] are all there)
   uint32_t top_permille = 0;
   uint32_t *out[4] = {nullptr, nullptr, nullptr, nullptr};   // device rows of the batch: taxon, best_count, best_gid, considered
-  explicit Lca(niqki_index *ix_) : ix(ix_), ev(ix_, 3, ix_->lca_stats.ms) {}
+  explicit Lca(niqki_index *ix_) : ix(ix_), ev(ix_, 4, ix_->lca_stats.ms) {}
 };
 
 // The consumer of a leaf (HitLists): the full lists `hits` of queries [q_at, q_at + n) of the batch; one launch that
@@ -52,9 +54,24 @@ int lca_consume(Lca &c, const HitOut &hits, uint32_t q_at, uint32_t n) {
   a.info = (uint32_t *)ix->ws_lca_info.p;
   NQ_HIP(ix, nq::launch_lca(a, ix->stream));
   if ((rc = c.ev.mark(2))) return rc;
+  if (c.tally) {   // the rows the caller gets, exactly once: a halved batch comes here leaf by leaf
+    if ((rc = tally_rows_dev(ix, c.out[0] + q_at, c.out[1] + q_at, c.out[3] + q_at, n))) return rc;
+    if ((rc = c.ev.mark(3))) return rc;
+  }
   if ((rc = c.ev.add(0, 1, 0)) || (rc = c.ev.add(1, 2, 1))) return rc;
+  if (c.tally && (rc = c.ev.add(2, 3, 2))) return rc;
   return NIQKI_OK;
 }
+
+// an open tally that a failing call leaves with part of its rows is broken; a call that ends well disarms it
+struct TallyGuard {
+  niqki_index *ix;
+  const char *who;
+  bool armed = false;
+  ~TallyGuard() {
+    if (armed) break_tally(ix, std::string(who) + " failed after its first batch had begun");
+  }
+};
 
 // rows [0, n) of a query without a hit
 int lca_no_hit(niqki_index *ix, uint32_t *const out[4], uint32_t n, bool dev) {
@@ -77,23 +94,45 @@ int lca_run(niqki_index *ix, const char *who, const SketchSource &src, uint32_t 
   if (N && !ix->tax_set)
     return fail(ix, NIQKI_E_STATE, std::string(who) + ": no taxonomy on this genome set: call niqki_set_taxonomy (again, after genomes were added or dropped)");
   uint32_t *const user[4] = {taxon, best_count, best_gid, considered};
-  if (nq == 0 || N == 0) return lca_no_hit(ix, user, nq, dev);
+  const bool tally = ix->tally_state == 1;
+  if (tally) ix->tally_ms[0] = 0;
+  if (nq == 0 || N == 0) {   // (no genomes under a taxonomy of taxa alone: every row is a no-hit row)
+    if (!tally || !nq) return lca_no_hit(ix, user, nq, dev);
+    // the rows go into the tally from a workspace of the library's (the caller's may be host memory or left out), after
+    // they were written: rows that were not returned are not added
+    int rc = ensure(ix, ix->ws_tally_rows, (size_t)nq * 4);
+    if (rc || (rc = lca_no_hit(ix, user, nq, dev))) return rc;
+    const auto add = [&]() -> int {
+      NQ_HIP(ix, hipMemsetAsync(ix->ws_tally_rows.p, 0xFF, (size_t)nq * 4, ix->stream));
+      return tally_rows_dev(ix, (const uint32_t *)ix->ws_tally_rows.p, nullptr, nullptr, nq);
+    };
+    if ((rc = add())) break_tally(ix, std::string(who) + " failed while its rows were added");
+    return rc;
+  }
   CallParams guard(ix, ix->d.min_score, 0);   // the query path at the handle's threshold and no top-k
   int rc = build_if_needed(ix);
   if (rc) return rc;
   Lca c(ix);
   c.top_permille = top_permille;
+  c.tally = tally;
   if ((rc = c.ev.create())) return rc;
   const uint32_t qb = dev ? nq : std::max<uint32_t>(ix->query_batch, 1);
   const uint32_t rows = std::min(qb, nq);
   if ((rc = ensure(ix, ix->ws_lca_info, nq::kLcaInfoWords * 4))) return rc;
   NQ_HIP(ix, hipMemsetAsync(ix->ws_lca_info.p, 0, nq::kLcaInfoWords * 4, ix->stream));
+  const auto wanted = [&](int j) { return user[j] || (tally && (j == 1 || j == 3)); };   // (the tally reads best_count and considered)
   if (dev) {
     for (int j = 0; j < 4; ++j) c.out[j] = user[j];
+    if (tally && (!user[1] || !user[3])) {   // ... in a workspace of the library's where the caller left them out
+      if ((rc = ensure(ix, ix->ws_tally_rows, (size_t)nq * 8))) return rc;
+      if (!user[1]) c.out[1] = (uint32_t *)ix->ws_tally_rows.p;
+      if (!user[3]) c.out[3] = (uint32_t *)ix->ws_tally_rows.p + nq;
+    }
   } else {   // a batch's rows: four arrays of `rows` words, the ones nobody asked for left out
     if ((rc = ensure(ix, ix->ws_lca_out, (size_t)rows * 16))) return rc;
-    for (int j = 0; j < 4; ++j) c.out[j] = user[j] ? (uint32_t *)ix->ws_lca_out.p + (size_t)j * rows : nullptr;
+    for (int j = 0; j < 4; ++j) c.out[j] = wanted(j) ? (uint32_t *)ix->ws_lca_out.p + (size_t)j * rows : nullptr;
   }
+  TallyGuard guard_tally{ix, who, tally};
   HitLists hl{ix, who, c.ev, 0, ix->lca_stats.splits, false};
   hl.consume = [&](const HitOut &hits, const int32_t *, uint32_t q_at, uint32_t n) { return lca_consume(c, hits, q_at, n); };
   if (!dev)   // (device memory: one batch, its rows are the caller's)
@@ -110,6 +149,8 @@ int lca_run(niqki_index *ix, const char *who, const SketchSource &src, uint32_t 
   if (info[nq::kLcaInfoBad]) return fail(ix, NIQKI_E_STATE, std::string(who) + ": a hit outside the index or a taxon outside the taxonomy (a bug)");
   ix->lca_stats.long_lists = info[nq::kLcaInfoLong];
   ix->lca_stats.no_common = info[nq::kLcaInfoNoCommon];
+  guard_tally.armed = false;
+  if (tally) ix->tally_ms[0] = ix->lca_stats.ms[2];
   return NIQKI_OK;
 }
 
@@ -204,6 +245,7 @@ int niqki_set_taxonomy(niqki_index *ix, const uint32_t *genome_taxon, uint32_t n
   ix->n_taxa = n_taxa;
   ix->tax_depth = deepest;
   ix->tax_set = true;
+  end_tally(ix);   // (a tally counted under the taxonomy this one replaces)
   return NIQKI_OK;
 }
 

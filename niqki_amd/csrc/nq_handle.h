@@ -59,7 +59,7 @@ struct LcaStats {
   uint64_t splits = 0;       // batches the call had to halve
   uint64_t long_lists = 0;   // queries whose considered prefix the whole workgroup folded
   uint64_t no_common = 0;    // queries with two or more considered hits and no common taxon
-  double ms[2] = {0, 0};     // while profiling is on: hits, fold
+  double ms[3] = {0, 0, 0};  // while profiling is on: hits, fold, the rows into an open tally
 };
 
 void shared_free(struct ::niqki_index *ix);   // nq_shared.hip
@@ -183,6 +183,15 @@ struct niqki_index {
   nqi::LcaStats lca_stats;
   // niqki_query_lca: a host call's result rows of a batch, the info words of a call
   nqi::Buf ws_lca_out, ws_lca_info;
+  // niqki_tally_*: kTallyWords 64-bit words, then direct, direct_best, clade and clade_best of tally_taxa entries each
+  // (device); the rows a caller left out of an LCA call or a host call's staged rows.  The tally belongs to the
+  // taxonomy: whatever sets, removes or drops that ends it (end_tally).
+  nqi::Buf tally_acc, ws_tally_rows;
+  int tally_state = 0;            // stat "tally": 0 none, 1 open, 2 broken (tally_why says how)
+  uint32_t tally_taxa = 0;
+  std::string tally_why;
+  uint64_t tally_queries = 0;     // stat "tally_queries": rows added as of the last read
+  double tally_ms[2] = {0, 0};    // while profiling is on: the row kernel of the last LCA or add call, the clade kernel of the last read
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
 
@@ -353,6 +362,11 @@ struct HitLists {
 void drop_labels(niqki_index *ix);   // the genome set changes: the labelling of niqki_set_labels goes
 // ---- nq_api_lca.hip ----
 void drop_taxonomy(niqki_index *ix);   // the genome set changes: the taxonomy of niqki_set_taxonomy goes
+// ---- nq_api_tally.hip ----
+void end_tally(niqki_index *ix);       // the taxonomy is replaced or goes: so does the tally (the buffers stay the handle's)
+void break_tally(niqki_index *ix, const std::string &why);   // an open tally holds part of a call's rows
+// rows [0, n) in device memory into the open tally, in stream order (best_count, considered: may be null)
+int tally_rows_dev(niqki_index *ix, const uint32_t *taxon, const uint32_t *best_count, const uint32_t *considered, uint32_t n);
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);

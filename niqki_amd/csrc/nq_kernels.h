@@ -417,6 +417,29 @@ struct LcaArgs {
 };
 hipError_t launch_lca(const LcaArgs &a, hipStream_t stream);
 
+// ---- taxon tally: the LCA rows counted per taxon and clade (nq_tally.hip; the calls: nq_api_tally.hip) ----
+// A workgroup of tally_rows_kernel combines a pass of kTallyPassRows rows in an LDS table of kTallySlots slots
+// {key u32, count u32, best sum u64} (32 KiB) before anything reaches global memory.
+constexpr uint32_t kTallyPassRows = 1024, kTallySlots = 2048;
+// the 64-bit words beside the accumulators: rows with a taxon, rows without a hit, rows without a common taxon, bad rows
+enum : uint32_t { kTallyClassified = 0, kTallyNoHit = 1, kTallyNoCommon = 2, kTallyBad = 3, kTallyWords = 4 };
+struct TallyArgs {
+  const uint32_t *taxon;               // n rows
+  const uint32_t *best_count;          // n, or null: all zeros
+  const uint32_t *considered;          // n, or null: a row without a taxon has no hit
+  uint32_t n, n_taxa;
+  unsigned long long *direct, *direct_best;   // n_taxa each; the launch adds to them
+  unsigned long long *words;           // kTallyWords; the launch adds to them
+};
+hipError_t launch_tally_rows(const TallyArgs &a, hipStream_t stream);
+struct TallyCladeArgs {
+  const TaxNode *nodes;                // n_taxa
+  uint32_t n_taxa, max_depth;
+  const unsigned long long *direct, *direct_best;
+  unsigned long long *clade, *clade_best;   // n_taxa each, zeroed by the caller
+};
+hipError_t launch_tally_clade(const TallyCladeArgs &a, hipStream_t stream);
+
 // ---- FASTA / FASTQ framing (nq_ingest.hip) --------------------------------------
 constexpr uint32_t kIngestBlock = 256;
 constexpr uint32_t kIngestChunk = 8192;  // bytes per workgroup; chunks never span two files

@@ -27,6 +27,7 @@
 #include "file_reader.h"
 #include "label_file.h"
 #include "taxonomy_file.h"
+#include "report_file.h"
 #include "linkage_text.h"
 #include "piece_reader.h"
 #include "seqio.h"
@@ -94,6 +95,7 @@ const struct {
     {{"niqki_set_taxonomy", "niqki_staged_query_lca"}, "this engine has no LCA query"},
     {{"niqki_staged_cover"}, "this engine has no cover"},
     {{"niqki_set_labels", "niqki_staged_query_collapsed"}, "this engine has no collapsed query"},
+    {{"niqki_tally_begin", "niqki_tally_read"}, "this engine has no taxon tally"},
 };
 template <typename Fn>
 Fn engine_call(const char *name) { return (Fn)dlsym(RTLD_DEFAULT, name); }
@@ -478,10 +480,33 @@ void Index::set_lca(const std::string &filestr, uint32_t top_permille, const std
   } catch (const std::exception &e) { err = e.what(); }
   if (!err.empty()) refuse(which + ": " + err);
   taxon_text_ = std::move(tf.texts);
+  taxon_parent_ = std::move(tf.parent);
   if (!lf.label_of.empty())
-    check(call(h_, lf.label_of.data(), (uint32_t)lf.label_of.size(), tf.parent.data(), (uint32_t)tf.parent.size(), NIQKI_MEM_HOST), "niqki_set_taxonomy");
+    check(call(h_, lf.label_of.data(), (uint32_t)lf.label_of.size(), taxon_parent_.data(), (uint32_t)taxon_parent_.size(), NIQKI_MEM_HOST), "niqki_set_taxonomy");
+  if (!report.empty() && !lf.label_of.empty()) {   // --report: the queries from here on feed the tally
+    check(NEED(TALLY, niqki_tally_begin)(h_), "niqki_tally_begin");
+    tally_open_ = true;
+  }
   lca_permille_ = top_permille;
   lca_ = true;
+}
+
+void Index::write_report() {
+  const size_t T = taxon_text_.size();
+  std::vector<uint64_t> direct(T, 0), clade(T, 0), direct_best(T, 0), clade_best(T, 0);
+  ReportTotals totals;
+  totals.queries = totals.no_hit = untallied_;
+  if (tally_open_) {
+    niqki_tally_totals t{};
+    check(NEED(TALLY, niqki_tally_read)(h_, direct.data(), clade.data(), direct_best.data(), clade_best.data(), &t, NIQKI_MEM_HOST), "niqki_tally_read");
+    totals.queries = t.queries;
+    totals.classified = t.classified;
+    totals.no_hit = t.no_hit;
+    totals.no_common = t.no_common;
+  }
+  ParallelTextWriter out(report, host_threads());
+  out.write(report_text(taxon_text_, taxon_parent_, direct, clade, direct_best, clade_best, totals, F));
+  out.close();
 }
 
 // hits of the n entries staged on the one GPU
@@ -491,6 +516,7 @@ void Index::query_staged(size_t n, Hits &h) {
     const auto call = NEED(LCA, niqki_staged_query_lca);
     std::vector<uint32_t> taxon(std::max<size_t>(n, 1)), best(std::max<size_t>(n, 1)), considered(std::max<size_t>(n, 1));
     check(call(h_, lca_permille_, taxon.data(), best.data(), nullptr, considered.data(), NIQKI_MEM_HOST), "niqki_staged_query_lca");
+    if (!tally_open_) untallied_ += n;
     h.off.assign(n + 1, 0);
     h.hc.clear();
     h.hg.clear();

@@ -61,7 +61,7 @@ class Index {
   // the long options below are looked up at run time, so the program links against any engine, and a run that needs one
   // the engine lacks is refused with the feature's text.  One table in index_host.cpp holds, per feature, the symbols it
   // needs and that text.  All of these work on a single-GPU index only.
-  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, SELF_JOIN, DEREPLICATION, LINKAGE, LCA, COVER, COLLAPSE };
+  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, SELF_JOIN, DEREPLICATION, LINKAGE, LCA, COVER, COLLAPSE, TALLY };
   // null where the engine has every call of the feature, else the text that says what is missing
   static const char *lacks(Feature f);
 
@@ -111,6 +111,12 @@ class Index {
   // considered hits lie in two trees).  A file error is an error of the run, and then nothing is written, the -O file
   // included.
   void set_lca(const std::string &filestr, uint32_t top_permille, const std::string &label_file);
+  // --report <file> beside --lca (niqki_tally_begin + niqki_tally_read).  With `report` set, set_lca opens the engine's
+  // taxon tally, which every -Q / -l query of the run then feeds; write_report reads it once, after the last of them,
+  // and writes report_file.h's text into `report`, a gzip file like every output of the program.  --neighbors and -M
+  // are not tallied.
+  std::string report;
+  void write_report();
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
@@ -161,6 +167,9 @@ class Index {
   bool lca_ = false;                     // --lca: set_lca has run
   uint32_t lca_permille_ = 0;
   std::vector<std::string> taxon_text_;  // ... per taxon its text (taxonomy_file.h)
+  std::vector<uint32_t> taxon_parent_;   // ... and its parent (--report)
+  bool tally_open_ = false;              // --report: the engine's tally is open (an index without genomes has no taxonomy to open it on)
+  uint64_t untallied_ = 0;               // ... else the entries queried: none of them has a hit
   std::string out_text_;                // write_hits' lines before they go to the writer
   std::string out_path_;                // the -O file (refuse takes it away again)
   // Lines mode.  stage_lines: one niqki_stage_raw of the whole records at raw[0, size) on h -- at most hdr.size()

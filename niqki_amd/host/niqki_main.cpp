@@ -16,6 +16,8 @@
 //                  it, the genome names: the list of every -Q / -q query holds one entry, taxon:jaccard, the lowest taxon
 //                  that contains every hit within --lca-top permille (default 100) of the best hit, and the best hit's
 //                  jaccard (niqki_set_taxonomy + niqki_staged_query_lca); "no_common_taxon" where there is none
+//   --report <f>   with --lca: after the last -Q / -l query the taxon tally of all of them into f, a line per taxon with
+//                  the queries in its clade and on the taxon itself (niqki_tally_begin + niqki_tally_read; report_file.h)
 //   --cluster <f>  single-linkage clusters at the -J threshold into f: representative<TAB>member (niqki_cluster)
 //   --mst <f> / --linkage <f> / --tree <f>   the complete single-linkage hierarchy down to the -J threshold from ONE
 //                  engine call (niqki_linkage): the maximum spanning forest, the merge table, Newick dendrograms
@@ -55,7 +57,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -99,6 +101,7 @@ const Desc kDesc[] = {
     {COLLAPSE, "", "collapse", NONEMPTY, "  --collapse <filename>         Report each -Q / -q query's best hit per label instead of all its hits: the file holds lines label<TAB>member (as --cluster / --derep write them; plain or gzip), a genome no line names is its own label (--top bounds the labels)."},
     {LCA, "", "lca", NONEMPTY, "  --lca <filename>              Report each -Q / -q query's taxon instead of all its hits: the lowest common ancestor of its near-best hits in the taxonomy of the file, lines parent<TAB>child (plain or gzip) over the labels of --collapse or, without it, the genome names; no_common_taxon where the hits share none."},
     {LCA_TOP, "", "lca-top", NONEMPTY, "  --lca-top <permille>          With --lca: consider the hits within <permille> thousandths of the best hit's count, 0..1000 (100); 0: only ties with the best hit."},
+    {REPORT, "", "report", NONEMPTY, "  --report <filename>           With --lca: after the last -Q / -l query, the tally of all their taxa: lines percent<TAB>queries in the clade<TAB>queries on the taxon<TAB>depth<TAB>mean jaccard of their best hits<TAB>taxon, indented by depth, after the two lines unclassified and no_common_taxon."},
 };
 
 struct Parsed {
@@ -282,6 +285,7 @@ const struct { Opt asked_by[3]; Feature feature; } kNeeds[] = {
     {{LCA, LCA, LCA}, Feature::LCA},
     {{COVER, COVER, COVER}, Feature::COVER},
     {{COLLAPSE, COLLAPSE, COLLAPSE}, Feature::COLLAPSE},
+    {{REPORT, REPORT, REPORT}, Feature::TALLY},
 };
 // the text of the first row in [first, last] that the options ask for and the engine lacks, else null (main has
 // refusals of its own between the rows: the loop runs over one stretch of them at a time)
@@ -353,11 +357,14 @@ int main(int argc, char *argv[]) {
     }
     lca_permille = (uint32_t)v;
   }
+  // the report tallies the rows of the LCA query
+  if (o.has(REPORT) && !o.has(LCA)) return refused("--report needs --lca");
   // the taxon is folded on one device from whole counts
   if (o.has(LCA)) {
     if (n_gpus > 1) return refused("--lca needs a single-GPU index (--gpus 1)");
     if (o.has(COVER)) return refused("--lca and --cover both replace a query's list: choose one");
     if (const char *text = engine_lacks(o, Feature::LCA, Feature::LCA)) return refused(text);
+    if (const char *text = engine_lacks(o, Feature::TALLY, Feature::TALLY)) return refused(text);
   }
   if (o.has(COLLAPSE) && o.has(COVER)) return refused("--collapse and --cover both replace a query's list: choose one");
   // the cover reads whole counts and the winner's column of a device-resident sketch store
@@ -381,6 +388,7 @@ int main(int argc, char *argv[]) {
     if (o.has(LOAD)) ix.reset(new nqhost::Index(o.last(LOAD), true, out_file, device, n_gpus, resident_mib, top_k));
     else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib, top_k));
     ix->cover = o.has(COVER);
+    if (o.has(REPORT)) ix->report = o.last(REPORT);
     if (const unsigned expect = (unsigned)int_opt(o, GENOME_SIZE, 0)) ix->select_best_H(expect);   // src/niqki.cpp:303-305
 
     const uint32_t n_loaded = (uint32_t)ix->getNbGenomes();   // --novel: the genomes of -L are given (none without -L)
@@ -431,6 +439,7 @@ int main(int argc, char *argv[]) {
     else if (o.has(COLLAPSE)) ix->set_collapse(o.last(COLLAPSE));
     if (o.has(NEIGHBORS)) ix->query_neighbors();
     for (const Phase &ph : kQueryPhases) run_phase(*ix, o, ph);
+    if (o.has(REPORT)) ix->write_report();
     ix->outfile->close();
     const RunClock::tp done = system_clock::now();
     RunClock::row("| Query lasted (s)                  |", clk.index_end, done);
