@@ -769,6 +769,38 @@ int niqki_tally_end(niqki_index *ix);
  * (microseconds, the last call; tools/bench_retain.py). */
 int niqki_retain(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32_t *n_kept, int mem);
 
+/* Unites the indexed genomes by label: one entry per label, its sketch the sketch of the members' pooled k-mers (a pan
+ * index, one sketch per species).  labels: one uint32_t per indexed genome with the value rules of niqki_set_labels --
+ * arbitrary, not necessarily dense, 0 and 0xFFFFFFFF ordinary labels; n must equal niqki_genome_count(ix), else
+ * NIQKI_E_INVALID and nothing changes.  new_ids (may be NULL; length n, same `mem` space) receives the number of every
+ * genome's label; *n_labels (may be NULL, host memory whatever mem is) the number of distinct labels L.  mem as in
+ * niqki_retain: NIQKI_MEM_DEVICE takes labels / new_ids in stream order; the call may synchronise once.
+ * Definition: let c_g[s] be what niqki_get_sketches returns for genome g and slot s before the call.  The distinct
+ * labels are numbered 0 .. L - 1 by the smallest genome id that carries them.  U_l[s] is the minimum of c_g[s] over the
+ * members g of label l with c_g[s] >= 0, and -1 when no member has a valid cell there.  After the call the handle is
+ * indistinguishable, through every call of this header, from a fresh handle with the same parameters and options into
+ * which U_0 .. U_{L-1} were inserted in that order.  A cell holds the smallest fingerprint seen in its slot, so U_l is
+ * what niqki_sketch makes of the members' records when they share one entry through entry_rec (before densification
+ * fills a cell that no member has).  new_ids[g] is the number of g's label; genomes inserted afterwards get ids from L
+ * on; min_score, top_k and all options are untouched.
+ * All labels distinct: nothing changes (a built index stays built, new_ids is the identity).  One label for all: one
+ * entry.  No genomes: NIQKI_OK, *n_labels = 0.
+ * A labelling (niqki_set_labels) and a taxonomy (niqki_set_taxonomy) on the handle are removed whatever the labels are,
+ * as niqki_retain removes them; the labels given here are consumed, not installed.  Handles as niqki_retain:
+ * whole-range single-GPU handles, resident or paged, with or without a delta segment, S <= 16; NIQKI_E_STATE on a
+ * slot-range shard and while an append is pending.  Groups have no such call (out of scope: unite on a single-GPU
+ * handle).  NIQKI_E_NOMEM (the new store could not be allocated): the genome set is unchanged, the handle stays
+ * consistent.  Staged batches and batches sketched ahead are untouched.
+ * How: the host numbers the labels and lists every label's members, one-off work as in niqki_set_labels.  One kernel
+ * then writes a new store of L columns: an empty cell is the largest 16-bit value, so a label's cell is the plain
+ * unsigned minimum of its members' cells.  A wavefront owns 64 consecutive new columns of 16 rows; a label of few
+ * members is folded by its own lane, a larger one by the whole wavefront, and every cell is written once by a plain
+ * store (no atomics).  The inverted index (both segments) is dropped: the next use builds one main segment ("store_bytes"
+ * shrinks, "delta_genomes" reads 0).  A paged handle's store is host memory; the host takes the minima in place.
+ * While profiling is on: "unite_us_prepare" (the host's part and its copies), "unite_us_min" (the minimum pass), in
+ * microseconds for the last call (tools/bench_unite.py).  DESIGN.md 4.6h. */
+int niqki_unite(niqki_index *ix, const uint32_t *labels, uint32_t n, uint32_t *new_ids, uint32_t *n_labels, int mem);
+
 /* dump_index_disk payload (src/niqki_index.cpp:42-55), before gzip and
  * without the trailing names: 6 x u32 header {lF,K,H,W,min_score,N} then per
  * bucket u32 size + size x u32 gid, buckets in fp + slot*2^W order, gids

@@ -141,6 +141,7 @@ ABI = [
     ("niqki_tally_read", _int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(TallyTotals), _int]),
     ("niqki_tally_end", _int, [_vp]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
+    ("niqki_unite", _int, [_vp, _vp, _u32, _vp, C.POINTER(_u32), _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
     ("niqki_export_dump_header", _int, [_vp, _vp]),
@@ -762,6 +763,25 @@ class Engine:
         ids = np.empty(k.size, dtype=np.uint32)
         n = _u32(0)
         self._ck(self.L.niqki_retain(self.h, _p(k) if k.size else None, _p(ids) if k.size else None, C.byref(n), MEM_HOST))
+        return int(n.value), ids
+
+    def unite(self, labels):
+        """niqki_unite: one entry per label, its sketch the per-slot minimum of the members' valid cells: (n_labels,
+        new_ids), new_ids[g] = the number of g's label, labels numbered by first appearance.  labels: a uint32 per
+        indexed genome as a numpy array, or a device tensor of 32-bit elements as in set_labels; new_ids is then a
+        device tensor (int32, holding the same bits).  The handle then equals a fresh one holding the labels' sketches."""
+        n = _u32(0)
+        if hasattr(labels, "data_ptr"):
+            if labels.element_size() != 4 or not labels.is_contiguous():
+                raise ValueError("unite: a device tensor must be contiguous and hold 32-bit labels")
+            import torch
+            ids = torch.empty(int(labels.numel()), dtype=torch.int32, device=labels.device)
+            self._ck(self.L.niqki_unite(self.h, _p(labels), int(labels.numel()), _p(ids), C.byref(n), MEM_DEVICE))
+            return int(n.value), ids
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        ids = np.empty(lab.size, dtype=np.uint32)
+        self._ck(self.L.niqki_unite(self.h, _p(lab) if lab.size else None, lab.size, _p(ids) if lab.size else None,
+                                    C.byref(n), MEM_HOST))
         return int(n.value), ids
 
     def get_sketches(self, begin, n):

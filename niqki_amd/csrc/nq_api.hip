@@ -646,6 +646,9 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   // the last niqki_retain call while profiling was on: the rank pass and the store compaction, microseconds
   if (!std::strcmp(key, "retain_us_rank")) { *value = us(ix->retain_ms[0]); return NIQKI_OK; }
   if (!std::strcmp(key, "retain_us_compact")) { *value = us(ix->retain_ms[1]); return NIQKI_OK; }
+  // the last niqki_unite call while profiling was on: the host's preparation and the minimum pass, microseconds
+  if (!std::strcmp(key, "unite_us_prepare")) { *value = us(ix->unite_ms[0]); return NIQKI_OK; }
+  if (!std::strcmp(key, "unite_us_min")) { *value = us(ix->unite_ms[1]); return NIQKI_OK; }
   if (!std::strcmp(key, "inflate_files_in_flight") || !std::strcmp(key, "inflate_files_in_flight_8k")) {
     // how many files a launch of the device inflate runs at once (workgroups the device keeps resident), by kernel form
     (void)hipSetDevice(ix->device);

@@ -9,8 +9,6 @@
 
 namespace nqi {
 
-namespace {
-
 // both segments' index buffers back to the device: nothing of them describes the genomes that are left
 void release_segments(niqki_index *ix) {
   auto &a = ix->alt;
@@ -27,6 +25,8 @@ void release_segments(niqki_index *ix) {
   ix->built_n = 0;
   ix->delta_n = ix->seg_n = ix->g_base = 0;
 }
+
+namespace {
 
 // paged handle: every row of the host store, forward and in place (a kept column's destination is at or below it)
 void compact_host_store(niqki_index *ix, const std::vector<uint64_t> &words, uint32_t n, uint32_t n_kept) {

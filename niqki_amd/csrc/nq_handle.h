@@ -194,6 +194,9 @@ struct niqki_index {
   double tally_ms[2] = {0, 0};    // while profiling is on: the row kernel of the last LCA or add call, the clade kernel of the last read
   // the last niqki_retain call while profiling was on (stats "retain_us_rank", "retain_us_compact"): rank pass, compaction
   double retain_ms[2] = {0, 0};
+  // the last niqki_unite call while profiling was on (stats "unite_us_prepare", "unite_us_min"): the host's numbering and
+  // member lists with their copies, the minimum pass
+  double unite_ms[2] = {0, 0};
 
   nqi::Buf ws_seq, ws_recoff, ws_entry, ws_sk, ws_counts, ws_blk, ws_hitoff, ws_hc, ws_hg, ws_tc, ws_tg,
       ws_misc, ws_stash, ws_hl, ws_parent;
@@ -367,6 +370,9 @@ void end_tally(niqki_index *ix);       // the taxonomy is replaced or goes: so d
 void break_tally(niqki_index *ix, const std::string &why);   // an open tally holds part of a call's rows
 // rows [0, n) in device memory into the open tally, in stream order (best_count, considered: may be null)
 int tally_rows_dev(niqki_index *ix, const uint32_t *taxon, const uint32_t *best_count, const uint32_t *considered, uint32_t n);
+// ---- nq_api_retain.hip ----
+// both segments' index buffers back to the device: the genome set has changed, the next use builds one main segment
+void release_segments(niqki_index *ix);
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);

@@ -3,6 +3,7 @@
 #pragma once
 #include "nq_common.h"
 #include "nq_retain_blocks.h"
+#include "nq_unite_blocks.h"
 
 namespace nq {
 
@@ -129,6 +130,11 @@ hipError_t launch_retain_ranks(const uint8_t *keep, uint32_t n, unsigned long lo
 // kept total; both capacities multiples of 8 columns, both stores 16-byte aligned)
 hipError_t launch_store_compact(const uint16_t *src, uint64_t src_cap, uint32_t n_src, uint16_t *dst, uint64_t dst_cap,
                                 uint32_t f_local, const unsigned long long *words, const uint32_t *blk_dst, hipStream_t stream);
+// niqki_unite (nq_unite.hip; launch shape in nq_unite_blocks.h): dst(s, l) = the minimum of row s of src over the columns
+// members[off[l] .. off[l + 1]) for the n_labels labels, empty in the columns [n_labels, dst_cap) (off: n_labels + 1
+// entries; every member below src_cap; ANOTHER store than src)
+hipError_t launch_store_unite(const uint16_t *src, uint64_t src_cap, uint16_t *dst, uint64_t dst_cap, uint32_t f_local, uint32_t n_labels,
+                              const uint32_t *off, const uint32_t *members, hipStream_t stream);
 // Build, phase 1: units per (tile, slot) -> exclusive prefix per tile in
 // slot_units, tile totals as a prefix (in ids) in tile_base.
 hipError_t launch_build_sizes(const IndexView &v, uint32_t *slot_units, uint64_t *tile_base,

@@ -89,6 +89,7 @@ const struct {
     {{"niqki_append_begin", "niqki_append_slots", "niqki_append_cancel"}, "this engine cannot merge dumps"},
     {{"niqki_dereplicate_from"}, "this engine has no dereplication"},
     {{"niqki_retain"}, "this engine cannot drop genomes"},
+    {{"niqki_unite"}, "this engine cannot unite genomes"},
     {{"niqki_neighbors_range", "niqki_cluster"}, "this engine has no self-join"},
     {{"niqki_dereplicate"}, "this engine has no dereplication"},
     {{"niqki_linkage"}, "this engine has no linkage"},
@@ -1102,6 +1103,29 @@ void Index::remove_listed(const std::string &filestr) {
   for (const std::string &name : in_order)
     if (!seen.count(name)) refuse("--remove: no indexed genome is named '" + name + "'");
   if (!listed.empty()) retain(keep);
+}
+
+// ---- one entry per label -------------------------------------------------------------
+
+void Index::unite_listed(const std::string &filestr) {
+  const auto call = NEED(UNITE, niqki_unite);
+  LabelFile lf;
+  std::string err;
+  try {
+    PinnedBuf bytes;
+    read_file_bytes(filestr, bytes);
+    lf = parse_label_file((const char *)bytes.p, bytes.size, filenames);
+    err = lf.error;
+  } catch (const std::exception &e) { err = e.what(); }
+  if (!err.empty()) refuse("--pan '" + filestr + "': " + err);
+  const uint32_t N = (uint32_t)lf.label_of.size();
+  std::vector<uint32_t> entry_of(N);
+  uint32_t n_entries = 0;
+  check(call(h_, N ? lf.label_of.data() : nullptr, N, N ? entry_of.data() : nullptr, &n_entries, NIQKI_MEM_HOST), "niqki_unite");
+  if (n_entries != lf.texts.size()) throw std::runtime_error("niqki_unite made another number of entries than the file has labels");
+  std::vector<std::string> names(n_entries);
+  for (uint32_t g = 0; g < N; ++g) names[entry_of[g]] = lf.texts[lf.label_of[g]];
+  filenames = std::move(names);
 }
 
 // ---- dump ------------------------------------------------------------------------

@@ -61,7 +61,7 @@ class Index {
   // the long options below are looked up at run time, so the program links against any engine, and a run that needs one
   // the engine lacks is refused with the feature's text.  One table in index_host.cpp holds, per feature, the symbols it
   // needs and that text.  All of these work on a single-GPU index only.
-  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, SELF_JOIN, DEREPLICATION, LINKAGE, LCA, COVER, COLLAPSE, TALLY };
+  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, LCA, COVER, COLLAPSE, TALLY };
   // null where the engine has every call of the feature, else the text that says what is missing
   static const char *lacks(Feature f);
 
@@ -82,6 +82,11 @@ class Index {
   // genome carries is an error, and then nothing is written, the -O file included.
   void retain(const std::vector<uint8_t> &keep);
   void remove_listed(const std::string &filestr);
+  // --pan <file> (niqki_unite).  Reads the label file (label_file.h; plain or gzip, the format and the rules of
+  // --collapse) against `filenames`; the engine's index then holds one entry per label, its sketch the union of the
+  // members' sketches, and `filenames` the label texts in entry order.  A file error is an error of the run, and then
+  // nothing is written, the -O file included.
+  void unite_listed(const std::string &filestr);
   // --merge (niqki_append_begin / _slots / _cancel).  The dump file is streamed through the readers of the loading
   // constructor, whole slots go to the engine's pending append, and its names follow `filenames` (duplicates are kept as
   // they are).  A dump the engine refuses (other lF / K / W / H, a broken payload) leaves the index as it was and is an

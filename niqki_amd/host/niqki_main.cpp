@@ -24,6 +24,9 @@
 //   --derep <f>    greedy representatives at the -J threshold, in index order, into f: representative<TAB>member
 //                  (niqki_dereplicate); the lines whose two names are equal are the dereplicated list
 //   --remove <f>   drop every indexed genome named in f (one name per line) before -D and the queries (niqki_retain)
+//   --pan <f>      f holds lines label<TAB>member, as for --collapse: after every index input, --merge, --novel and
+//                  --remove the index holds one entry per label, named by the label, whose sketch is the union of the
+//                  members' sketches (niqki_unite); -D, the self-join options, -M and the queries see that index
 //   --derep-dump <f>  dereplicate at the -J threshold, keep the representatives only and dump that index into f (as -D);
 //                  the rest of the run (-M, --neighbors, -Q, -l) is answered by the dereplicated index
 //   --merge <f>    append the genomes of the dump f to the index (niqki_append_*); may be repeated, ALL occurrences are
@@ -57,7 +60,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -91,6 +94,7 @@ const Desc kDesc[] = {
     {CLUSTER, "", "cluster", NONEMPTY, "  --cluster <filename>          Single-linkage clusters at the -J threshold: lines representative<TAB>member."},
     {DEREP, "", "derep", NONEMPTY, "  --derep <filename>            Dereplication at the -J threshold: greedy representatives in index order, lines representative<TAB>member."},
     {REMOVE, "", "remove", NONEMPTY, "  --remove <filename>           Drop the indexed genomes named in the file (one name per line) before -D and the queries."},
+    {PAN, "", "pan", NONEMPTY, "  --pan <filename>              Unite the indexed genomes by label before -D and the queries: the file holds lines label<TAB>member (as for --collapse); the index then holds one entry per label, named by the label."},
     {DEREP_DUMP, "", "derep-dump", NONEMPTY, "  --derep-dump <filename>       Dereplicate at the -J threshold and dump the index of the representatives (as -D); the rest of the run is answered by that index."},
     {MERGE, "", "merge", NONEMPTY, "  --merge <filename>            Append the genomes of a dump to the index, after -L / -I / -i; may be repeated: every occurrence is taken, in order (of all other options only the last one counts)."},
     {NOVEL, "", "novel", NONEMPTY, "  --novel <filename>            After all index inputs and merges: of the genomes behind those of -L keep only the representatives at the -J threshold (the -L genomes are given); lines representative<TAB>member."},
@@ -279,6 +283,7 @@ const struct { Opt asked_by[3]; Feature feature; } kNeeds[] = {
     {{MERGE, MERGE, MERGE}, Feature::APPEND},
     {{NOVEL, NOVEL, NOVEL}, Feature::DEREPLICATION_FROM},
     {{NOVEL, REMOVE, DEREP_DUMP}, Feature::RETAIN},
+    {{PAN, PAN, PAN}, Feature::UNITE},
     {{NEIGHBORS, CLUSTER, CLUSTER}, Feature::SELF_JOIN},
     {{DEREP, DEREP_DUMP, DEREP_DUMP}, Feature::DEREPLICATION},
     {{MST, LINKAGE, TREE}, Feature::LINKAGE},
@@ -341,6 +346,8 @@ int main(int argc, char *argv[]) {
   const bool linkage = o.has(MST) || o.has(LINKAGE) || o.has(TREE);
   if (n_gpus > 1 && (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL) || linkage))
     return refused("the self-join (--neighbors, --cluster, --derep), dropping genomes and merging dumps (--merge, --novel) need a single-GPU index (--gpus 1)");
+  // the union is taken over the whole sketches of one device's store
+  if (n_gpus > 1 && o.has(PAN)) return refused("--pan needs a single-GPU index (--gpus 1)");
   if (const char *text = engine_lacks(o, Feature::APPEND, Feature::LINKAGE)) return refused(text);
 
   // --lca-top: thousandths of the best count, a plain integer
@@ -397,7 +404,7 @@ int main(int argc, char *argv[]) {
     if (o.has(DOWNLAD)) cout << "--indexdownload needs network access and is not part of this build" << endl;
     if (o.has(MERGE))   // the one option of which every occurrence counts
       for (const string &dump : o.opts.at(MERGE)) ix->merge_dump(dump);
-    RunClock::tp novel_begin, novel_end, remove_begin, remove_end;
+    RunClock::tp novel_begin, novel_end, remove_begin, remove_end, pan_begin, pan_end;
     if (o.has(NOVEL)) {
       novel_begin = system_clock::now();
       // the -J of THIS run where it is given: an index that -L loaded carries the min_score of its dump
@@ -409,10 +416,16 @@ int main(int argc, char *argv[]) {
       ix->remove_listed(o.last(REMOVE));
       remove_end = system_clock::now();
     }
+    if (o.has(PAN)) {   // ... and after the genomes that leave: -L db.dump --pan species.tsv -D species.dump
+      pan_begin = system_clock::now();
+      ix->unite_listed(o.last(PAN));
+      pan_end = system_clock::now();
+    }
     if (o.has(DUMP)) ix->dump_index_disk(o.last(DUMP));
     clk.index_done();
     if (o.has(NOVEL)) RunClock::row("| Novelty filter lasted (s)         |", novel_begin, novel_end);
     if (o.has(REMOVE)) RunClock::row("| Remove lasted (s)                 |", remove_begin, remove_end);
+    if (o.has(PAN)) RunClock::row("| Pan sketches lasted (s)           |", pan_begin, pan_end);
     if (o.has(CLUSTER)) {   // a phase of its own between indexing and the queries
       ix->cluster_to_file(o.last(CLUSTER));
       const RunClock::tp now = system_clock::now();
