@@ -135,28 +135,28 @@ int derive(const niqki_params &p, nq::Derived &d, std::string &why) {
   return NIQKI_OK;
 }
 
-nq::IndexView view(const niqki_index *ix) {
+nq::IndexView view(const niqki_index *ix, const niqki_index::Seg &seg) {
   nq::IndexView v;
   v.d = ix->d;
-  v.n_genomes = ix->seg_n;
-  v.g_base = ix->g_base;
-  v.tile = ix->tile;
-  v.n_tiles = ix->n_tiles;
+  v.n_genomes = seg.n;
+  v.g_base = seg.g_base;
+  v.tile = seg.tile;
+  v.n_tiles = seg.n_tiles;
   v.f_local = ix->d.slot_end - ix->d.slot_begin;
-  v.align_log2 = ix->align_log2;
-  v.padded = ix->padded;
-  v.stripe = ix->stripe;
+  v.align_log2 = seg.align_log2;
+  v.padded = seg.padded;
+  v.stripe = seg.stripe;
   v.cap = ix->cap;
   v.store = ix->store;
   v.q_stride = ix->d.F;
   v.q_off = ix->d.slot_begin;
   v.accumulate = 0;
-  v.entries = ix->entries;
-  v.gids = ix->gids;
-  v.tile_base = ix->tile_base;
-  v.slot_units = ix->slot_units;
-  v.ptab = ix->ptab_ok ? ix->ptab : nullptr;
-  v.hmask = ix->hmask_ok ? ix->hmask : nullptr;
+  v.entries = seg.entries;
+  v.gids = seg.gids;
+  v.tile_base = seg.tile_base;
+  v.slot_units = seg.slot_units;
+  v.ptab = seg.ptab_ok ? seg.ptab : nullptr;
+  v.hmask = seg.hmask_ok ? seg.hmask : nullptr;
   v.hmask_shift = ix->d.W > 4 ? ix->d.W - 4 : 0;
   return v;
 }
@@ -389,13 +389,7 @@ void niqki_destroy(niqki_index *ix) {
     if (b->p) (void)hipFree(b->p);
   if (ix->store && !ix->resident_bytes) (void)hipFree(ix->store);
   if (ix->host_store) (void)hipHostFree(ix->host_store);
-  for (void *p : {(void *)ix->alt.entries, (void *)ix->alt.gids, (void *)ix->alt.tile_base, (void *)ix->alt.slot_units,
-                  (void *)ix->alt.ptab, (void *)ix->ptab, (void *)ix->alt.hmask, (void *)ix->hmask})
-    if (p) (void)hipFree(p);
-  if (ix->entries) (void)hipFree(ix->entries);
-  if (ix->gids) (void)hipFree(ix->gids);
-  if (ix->tile_base) (void)hipFree(ix->tile_base);
-  if (ix->slot_units) (void)hipFree(ix->slot_units);
+  nqi::release_segments(ix);
   for (auto &s : ix->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
   for (auto e : ix->ev_pool) (void)hipEventDestroy(e);
   if (ix->aux_stream) { (void)hipStreamSynchronize(ix->aux_stream); (void)hipStreamDestroy(ix->aux_stream); }
@@ -422,7 +416,7 @@ int niqki_get_params(const niqki_index *ix, niqki_params *out) {
   out->slot_begin = ix->resident_bytes ? ix->full_begin : ix->d.slot_begin;
   out->slot_end = ix->resident_bytes ? ix->full_end : ix->d.slot_end;
   out->device = ix->device;
-  out->tile_genomes = ix->tile ? ix->tile : ix->p.tile_genomes;
+  out->tile_genomes = ix->main.tile ? ix->main.tile : ix->p.tile_genomes;
   return NIQKI_OK;
 }
 
@@ -453,7 +447,7 @@ int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
     ix->gather_variant = (int)value;
     return NIQKI_OK;
   }
-  if (!std::strcmp(key, "tile_stripe")) { ix->stripe_opt = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 64); ix->built = false; ix->seg_n = 0; return NIQKI_OK; }
+  if (!std::strcmp(key, "tile_stripe")) { ix->stripe_opt = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 64); ix->built = false; ix->main.n = 0; return NIQKI_OK; }
   if (!std::strcmp(key, "query_order")) { ix->query_order = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2); return NIQKI_OK; }
   if (!std::strcmp(key, "incremental_build")) { ix->incremental = value != 0; return NIQKI_OK; }
   if (!std::strcmp(key, "lookup_prepass")) {
@@ -492,14 +486,14 @@ int niqki_set_option(niqki_index *ix, const char *key, int64_t value) {
     if (value < 0 || value > 65536 || (value & 63)) return fail(ix, NIQKI_E_INVALID, "tile_genomes must be a multiple of 64, <= 65536");
     ix->p.tile_genomes = (uint32_t)value;
     ix->built = false;
-    ix->seg_n = 0;   // the next build is a full one
+    ix->main.n = 0;   // the next build is a full one
     return NIQKI_OK;
   }
   if (!std::strcmp(key, "bucket_align_log2")) {
     if (value < -1 || value > 6) return fail(ix, NIQKI_E_INVALID, "bucket_align_log2 must be -1 (choose) .. 6");
     ix->bucket_align = (int)value;
     ix->built = false;
-    ix->seg_n = 0;
+    ix->main.n = 0;
     return NIQKI_OK;
   }
   if (!std::strcmp(key, "resident_bytes")) {
@@ -632,14 +626,14 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   if (!ix || !key || !value) return NIQKI_E_INVALID;
   const uint32_t f_all = ix->resident_bytes ? ix->full_end - ix->full_begin : ix->d.slot_end - ix->d.slot_begin;
   if (!std::strcmp(key, "store_bytes")) { *value = (uint64_t)f_all * (ix->resident_bytes ? ix->host_cap : ix->cap) * 2; return NIQKI_OK; }
-  if (!std::strcmp(key, "index_bytes")) { *value = ix->built ? (uint64_t)ix->entries_bytes + ix->gids_bytes + ix->ptab_bytes + ix->hmask_bytes + ix->alt.entries_bytes + ix->alt.gids_bytes + ix->alt.ptab_bytes + ix->alt.hmask_bytes : 0; return NIQKI_OK; }
-  if (!std::strcmp(key, "delta_genomes")) { *value = ix->delta_n; return NIQKI_OK; }
-  if (!std::strcmp(key, "tiles")) { *value = ix->n_tiles; return NIQKI_OK; }
-  if (!std::strcmp(key, "class_mask")) { *value = (ix->built && ix->hmask_ok) ? 1 : 0; return NIQKI_OK; }
+  if (!std::strcmp(key, "index_bytes")) { *value = ix->built ? nqi::segment_bytes(ix->main) + nqi::segment_bytes(ix->delta) : 0; return NIQKI_OK; }
+  if (!std::strcmp(key, "delta_genomes")) { *value = ix->delta.n; return NIQKI_OK; }
+  if (!std::strcmp(key, "tiles")) { *value = ix->main.n_tiles; return NIQKI_OK; }
+  if (!std::strcmp(key, "class_mask")) { *value = (ix->built && ix->main.hmask_ok) ? 1 : 0; return NIQKI_OK; }
   if (!std::strcmp(key, "last_gather_form")) { *value = ix->last_form; return NIQKI_OK; }
   if (!std::strcmp(key, "last_densify_form")) { *value = ix->last_densify_form; return NIQKI_OK; }
   if (!std::strcmp(key, "last_gather_kernel")) { *value = ix->last_kernel; return NIQKI_OK; }
-  if (!std::strcmp(key, "bucket_align_log2")) { *value = ix->align_log2; return NIQKI_OK; }
+  if (!std::strcmp(key, "bucket_align_log2")) { *value = ix->main.align_log2; return NIQKI_OK; }
   if (!std::strcmp(key, "last_hits_form")) { *value = ix->last_hits_form; return NIQKI_OK; }
   for (const StatKey &s : kCallStats)
     if (!std::strcmp(key, s.key)) { *value = s.get(ix); return NIQKI_OK; }

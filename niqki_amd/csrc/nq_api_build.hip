@@ -58,6 +58,28 @@ int reserve_store(niqki_index *ix, uint64_t want) {
   return NIQKI_OK;
 }
 
+// niqki_retain / niqki_unite, resident: the store they have filled on the device replaces the handle's
+int adopt_store(niqki_index *ix, uint16_t *ns, uint64_t cap, uint32_t n) {
+  uint16_t *old = ix->store;
+  ix->store = ns;
+  ix->cap = cap;
+  ix->n_genomes = n;
+  NQ_HIP(ix, hipFree(old));
+  return NIQKI_OK;
+}
+
+// ... paged: the host store was rewritten in place for n genomes.  No page is resident and no dump layout is known;
+// the handle's slots are its whole range again.
+void host_store_rewritten(niqki_index *ix, uint32_t n) {
+  ix->page_begin = ix->page_end = ix->page_n = 0;
+  ix->pg_layout_n = 0xFFFFFFFFu;
+  ix->d.slot_begin = ix->full_begin;
+  ix->d.slot_end = ix->full_end;
+  ix->store = nullptr;
+  ix->cap = 0;
+  ix->n_genomes = n;
+}
+
 // Launches the sketch kernel(s) on device-resident inputs.
 int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, uint32_t n_rec,
                const uint32_t *entry_rec, uint32_t n_entry, int32_t *sketches, uint64_t total_bytes) {
@@ -122,18 +144,23 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
   return NIQKI_OK;
 }
 
-// flat index members <-> alt (nq_handle.h, "Delta segment")
-void swap_segment(niqki_index *ix) {
-  auto &a = ix->alt;
-  std::swap(ix->entries, a.entries); std::swap(ix->gids, a.gids);
-  std::swap(ix->tile_base, a.tile_base); std::swap(ix->slot_units, a.slot_units);
-  std::swap(ix->entries_bytes, a.entries_bytes); std::swap(ix->gids_bytes, a.gids_bytes);
-  std::swap(ix->tile_base_bytes, a.tile_base_bytes); std::swap(ix->slot_units_bytes, a.slot_units_bytes);
-  std::swap(ix->tile, a.tile); std::swap(ix->n_tiles, a.n_tiles); std::swap(ix->seg_n, a.seg_n);
-  std::swap(ix->g_base, a.g_base); std::swap(ix->align_log2, a.align_log2);
-  std::swap(ix->padded, a.padded); std::swap(ix->stripe, a.stripe);
-  std::swap(ix->ptab, a.ptab); std::swap(ix->ptab_bytes, a.ptab_bytes); std::swap(ix->ptab_ok, a.ptab_ok);
-  std::swap(ix->hmask, a.hmask); std::swap(ix->hmask_bytes, a.hmask_bytes); std::swap(ix->hmask_ok, a.hmask_ok);
+// the one list of a segment's device buffers (nq_handle.h, "Delta segment")
+void free_segment(niqki_index::Seg &seg) {
+  for (void *p : {(void *)seg.entries, (void *)seg.gids, (void *)seg.tile_base, (void *)seg.slot_units, (void *)seg.ptab, (void *)seg.hmask})
+    if (p) (void)hipFree(p);
+  seg = niqki_index::Seg();
+}
+
+uint64_t segment_bytes(const niqki_index::Seg &seg) {
+  return (uint64_t)seg.entries_bytes + seg.gids_bytes + seg.ptab_bytes + seg.hmask_bytes;
+}
+
+// nothing of either segment describes the genomes that are left
+void release_segments(niqki_index *ix) {
+  free_segment(ix->main);
+  free_segment(ix->delta);
+  ix->built = false;
+  ix->built_n = 0;
 }
 
 int build_if_needed(niqki_index *ix) {
@@ -145,16 +172,12 @@ int build_if_needed(niqki_index *ix) {
   // Genomes inserted after a build: a delta segment for them while they are few (the fixed part of a
   // build -- one table row per slot -- is ~10 ms at the north-star shape, a full rebuild of 100 000
   // genomes 65 ms), a full rebuild once the delta would pass an eighth of the main index.
-  const uint32_t main_n = ix->seg_n;
+  const uint32_t main_n = ix->main.n;
   if (ix->incremental && main_n >= 4096 && ix->n_genomes > main_n &&
       ix->n_genomes - main_n <= std::min<uint32_t>(main_n / 8, nq::kPadMaxTile)) {
-    swap_segment(ix);
-    int rc = build_range(ix, main_n, ix->n_genomes - main_n);
-    swap_segment(ix);
-    if (rc) { ix->built = false; return rc; }
-    ix->delta_n = ix->n_genomes - main_n;
+    int rc = build_range(ix, ix->delta, main_n, ix->n_genomes - main_n);   // (a failed one leaves delta.n = 0, main.n as it is)
+    if (rc) return rc;
     ix->built_n = ix->n_genomes;
-    ix->built = true;
     return NIQKI_OK;
   }
   return niqki_build(ix);
@@ -162,7 +185,7 @@ int build_if_needed(niqki_index *ix) {
 
 // before anything that needs ONE index over all genomes (dump export, per-bucket statistics)
 int build_single(niqki_index *ix) {
-  if (ix->resident_bytes || (ix->built && ix->built_n == ix->n_genomes && ix->delta_n == 0)) return build_if_needed(ix);
+  if (ix->resident_bytes || (ix->built && ix->built_n == ix->n_genomes && ix->delta.n == 0)) return build_if_needed(ix);
   return niqki_build(ix);
 }
 
@@ -202,8 +225,8 @@ int insert_dev(niqki_index *ix, const int32_t *sketches, uint32_t sk_stride, uin
   return NIQKI_OK;
 }
 
-// the index of store columns [g_base, g_base + N) into the current segment's buffers
-int build_range(niqki_index *ix, uint32_t g_base, uint32_t N) {
+// the index of store columns [g_base, g_base + N) into seg's buffers
+int build_range(niqki_index *ix, niqki_index::Seg &seg, uint32_t g_base, uint32_t N) {
   const uint32_t f_local = ix->d.slot_end - ix->d.slot_begin;
   uint32_t tile = ix->p.tile_genomes;
   // genomes are dealt to the tiles round-robin in blocks (option "tile_stripe": 0 = ranges, B = block size)
@@ -235,66 +258,67 @@ int build_range(niqki_index *ix, uint32_t g_base, uint32_t N) {
     return NIQKI_OK;
   };
   // Nothing of the segment counts as built until the fill has gone through: an error on the way (out of
-  // memory: grow() has freed the old buffer by then) must not leave seg_n naming ids that do not exist --
+  // memory: grow() has freed the old buffer by then) must not leave seg.n naming ids that do not exist --
   // build_if_needed would take such a segment for a main index and put a delta on top of it.
   struct Uncommitted {
     niqki_index *ix;
+    niqki_index::Seg &seg;
     bool ok = false;
     ~Uncommitted() {
-      if (!ok) { ix->seg_n = 0; ix->built = false; }
+      if (!ok) { seg.n = 0; ix->built = false; }
     }
-  } commit{ix};
+  } commit{ix, seg};
   ix->built = false;
   int rc;
-  if ((rc = grow((void **)&ix->entries, ix->entries_bytes, (size_t)f_local * ix->d.R * n_tiles * sizeof(nq::Entry)))) return rc;
-  if ((rc = grow((void **)&ix->slot_units, ix->slot_units_bytes, (size_t)n_tiles * (f_local + 1) * 4))) return rc;
-  if ((rc = grow((void **)&ix->tile_base, ix->tile_base_bytes, (size_t)(n_tiles + 1) * 8))) return rc;
-  ix->tile = tile;
-  ix->n_tiles = n_tiles;
-  ix->ptab_ok = false;
-  ix->hmask_ok = false;
-  ix->seg_n = N;
-  ix->g_base = g_base;
-  ix->align_log2 = (uint32_t)al;
+  if ((rc = grow((void **)&seg.entries, seg.entries_bytes, (size_t)f_local * ix->d.R * n_tiles * sizeof(nq::Entry)))) return rc;
+  if ((rc = grow((void **)&seg.slot_units, seg.slot_units_bytes, (size_t)n_tiles * (f_local + 1) * 4))) return rc;
+  if ((rc = grow((void **)&seg.tile_base, seg.tile_base_bytes, (size_t)(n_tiles + 1) * 8))) return rc;
+  seg.tile = tile;
+  seg.n_tiles = n_tiles;
+  seg.ptab_ok = false;
+  seg.hmask_ok = false;
+  seg.n = N;
+  seg.g_base = g_base;
+  seg.align_log2 = (uint32_t)al;
   // line-aligned buckets carry padding ids behind their last id (see IndexView::padded)
-  ix->padded = (al == 6 && tile <= nq::kPadMaxTile) ? 1u : 0u;
-  ix->stripe = 0;
+  seg.padded = (al == 6 && tile <= nq::kPadMaxTile) ? 1u : 0u;
+  seg.stripe = 0;
   if (stripe > 0 && n_tiles > 1 && n_tiles <= 64) {
     // the fullest tile must fit the tile size (it always does for B = 1)
     while (B > 1 && ((N + B - 1) / B + n_tiles - 1) / n_tiles * B > tile) B /= 2;
-    ix->stripe = B;
+    seg.stripe = B;
   }
   if (n_tiles == 0) { commit.ok = true; ix->built = true; return NIQKI_OK; }
   {
     Span sp(ix, NIQKI_KC_BUILD);
-    NQ_HIP(ix, nq::launch_build_sizes(view(ix), ix->slot_units, ix->tile_base, ix->stream));
+    NQ_HIP(ix, nq::launch_build_sizes(view(ix, seg), seg.slot_units, seg.tile_base, ix->stream));
   }
   std::vector<uint64_t> tb(n_tiles + 1);
-  NQ_HIP(ix, hipMemcpyAsync(tb.data(), ix->tile_base, (size_t)(n_tiles + 1) * 8, hipMemcpyDeviceToHost, ix->stream));
+  NQ_HIP(ix, hipMemcpyAsync(tb.data(), seg.tile_base, (size_t)(n_tiles + 1) * 8, hipMemcpyDeviceToHost, ix->stream));
   NQ_HIP(ix, hipStreamSynchronize(ix->stream));
   for (uint32_t t = 0; t < n_tiles; ++t)
     if (((tb[t + 1] - tb[t]) >> al) >= (1ull << 32))  // bucket starts are 32-bit unit counts
       return fail(ix, NIQKI_E_INVALID, "tile id array too large for 32-bit bucket starts");
   const uint64_t total_ids = tb[n_tiles];
   // + pad: the gather kernel reads up to 64 ids from a bucket's start whatever its length
-  if ((rc = grow((void **)&ix->gids, ix->gids_bytes, (size_t)total_ids * 2 + 512))) return rc;
-  if (ix->padded) {
+  if ((rc = grow((void **)&seg.gids, seg.gids_bytes, (size_t)total_ids * 2 + 512))) return rc;
+  if (seg.padded) {
     Span sp(ix, NIQKI_KC_BUILD);
-    NQ_HIP(ix, nq::launch_pad_fill(ix->gids, total_ids, tile, ix->stream));
+    NQ_HIP(ix, nq::launch_pad_fill(seg.gids, total_ids, tile, ix->stream));
   }
   {
     Span sp(ix, NIQKI_KC_BUILD);
-    NQ_HIP(ix, nq::launch_build_fill(view(ix), ix->entries, ix->gids, ix->stream));
+    NQ_HIP(ix, nq::launch_build_fill(view(ix, seg), seg.entries, seg.gids, ix->stream));
   }
   // single-tile indexes: the per-slot class mask the gather kernel's own look-ups test first (IndexView::hmask;
   // NIQKI_HMASK=0 leaves it out).  One more pass over the table: 32 MB at S = 12 W = 10.
   {
     const char *hv = std::getenv("NIQKI_HMASK");
     if (n_tiles == 1 && !(hv && hv[0] == '0')) {
-      if ((rc = grow((void **)&ix->hmask, ix->hmask_bytes, (size_t)f_local * 2))) return rc;
+      if ((rc = grow((void **)&seg.hmask, seg.hmask_bytes, (size_t)f_local * 2))) return rc;
       Span sp(ix, NIQKI_KC_BUILD);
-      NQ_HIP(ix, nq::launch_hmask(view(ix), ix->hmask, ix->stream));
-      ix->hmask_ok = true;
+      NQ_HIP(ix, nq::launch_hmask(view(ix, seg), seg.hmask, ix->stream));
+      seg.hmask_ok = true;
     }
   }
   commit.ok = true;
@@ -427,15 +451,11 @@ int niqki_build(niqki_index *ix) {
     ix->built_n = ix->n_genomes;
     return NIQKI_OK;
   }
-  ix->delta_n = 0;   // one index over everything inserted so far
-  int rc = build_range(ix, 0, ix->n_genomes);
+  ix->delta.n = 0;   // one index over everything inserted so far
+  int rc = build_range(ix, ix->main, 0, ix->n_genomes);
   if (rc == NIQKI_OK) {
     ix->built_n = ix->n_genomes;
-    // the delta segment's buffers are not needed until genomes arrive again: give their memory back
-    auto &a = ix->alt;
-    for (void *p : {(void *)a.entries, (void *)a.gids, (void *)a.tile_base, (void *)a.slot_units, (void *)a.ptab, (void *)a.hmask})
-      if (p) (void)hipFree(p);
-    a = niqki_index::Seg();
+    free_segment(ix->delta);   // not needed until genomes arrive again: its memory goes back
   }
   return rc;
 }

@@ -91,27 +91,14 @@ int counts_dev(niqki_index *ix, const int32_t *sketches, uint32_t q_stride, uint
   return counts_resident(ix, sketches, q_stride, q_off, nq, counts, stride, false, counts2, co);
 }
 
-int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride, uint32_t q_off, uint32_t nq,
-                    uint16_t *counts, uint64_t stride, bool accumulate, uint16_t *counts2, const nq::CandOut *co) {
-  int rc = ix->resident_bytes ? NIQKI_OK : build_if_needed(ix);
-  if (rc) return rc;
-  if (nq == 0) return NIQKI_OK;
-  if (counts && (stride < ix->built_n || (stride & 1))) return fail(ix, NIQKI_E_INVALID, "stride must be even and >= genome count");
-  if ((uintptr_t)counts & 3) return fail(ix, NIQKI_E_INVALID, "counts must be 4-byte aligned (rows are written as packed u16 pairs)");
-  if (ix->built_n == 0) return NIQKI_OK;
-  if (ix->delta_n && !ix->resident_bytes) {  // the delta segment first (its columns are its own), then the main index below
-    const uint32_t dn = ix->delta_n;
-    ix->delta_n = 0;
-    swap_segment(ix);
-    rc = counts_resident(ix, sketches, q_stride, q_off, nq, counts, stride, accumulate, counts2, co);
-    swap_segment(ix);
-    ix->delta_n = dn;
-    if (rc) return rc;
-  }
+// the counter launches of counts_resident over one segment
+static int counts_segment(niqki_index *ix, niqki_index::Seg &seg, const int32_t *sketches, uint32_t q_stride, uint32_t q_off, uint32_t nq,
+                          uint16_t *counts, uint64_t stride, bool accumulate, uint16_t *counts2, const nq::CandOut *co) {
+  int rc;
   // launches of at most `chunk` queries bound the per-query stash (one Entry per
   // slot and extra tile) whatever the caller's batch size is
   const uint32_t f_local = ix->d.slot_end - ix->d.slot_begin;
-  nq::IndexView v = view(ix);
+  nq::IndexView v = view(ix, seg);
   v.q_stride = q_stride;
   v.q_off = q_off;
   v.accumulate = accumulate ? 1u : 0u;
@@ -130,16 +117,16 @@ int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride,
   // with the look-ups inside the gather kernel -- the default for batches of >= 1024 queries.
   // (not on a paged index: the packed copy would be made again for every page, outside its memory budget)
   if (ix->lookup_prepass < 0)
-    pre = pre && ((ix->n_tiles > 4 && nq >= 256) || (nq::lookup_wants_packed(v) && nq >= 1024 && !ix->resident_bytes && ix->n_tiles <= 2));
+    pre = pre && ((seg.n_tiles > 4 && nq >= 256) || (nq::lookup_wants_packed(v) && nq >= 1024 && !ix->resident_bytes && seg.n_tiles <= 2));
   // locality order of each launch: worth its probe on large indexes and real batches.  It takes ~8 % off
   // the gather kernel and costs 0.1 ms per 4096 queries at 100 000 genomes whatever the slot count:
   // measured even on a slot shard of 4096 slots (1.56 against 1.57 ms per 4096 queries), +4 % at 8192.
-  const bool ordered = ix->query_order && nq >= 64 && ix->seg_n < (1u << 20) - 1 &&
-                       (ix->query_order >= 2 || (ix->seg_n >= 16384 && f_local >= 8192));
+  const bool ordered = ix->query_order && nq >= 64 && seg.n < (1u << 20) - 1 &&
+                       (ix->query_order >= 2 || (seg.n >= 16384 && f_local >= 8192));
   // launches of at most `chunk` queries: the order kernel sorts <= 4096, and the per-query scratch
   // (stash or pre-pass words) stays <= 128 MiB whatever the caller's batch size is (bigger launches are
   // no faster: 32 768 query shards in one launch take 8 x the time of 4096)
-  const size_t per_query = pre ? nq::lookup_pre_bytes(v, 1) : (size_t)(ix->n_tiles - 1) * f_local * sizeof(nq::Entry);
+  const size_t per_query = pre ? nq::lookup_pre_bytes(v, 1) : (size_t)(seg.n_tiles - 1) * f_local * sizeof(nq::Entry);
   uint32_t chunk = nq;
   if (per_query) chunk = (uint32_t)std::max<size_t>(4096, ((size_t)128 << 20) / per_query);
   if (ordered || pre) chunk = 4096;
@@ -147,21 +134,21 @@ int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride,
   // form reads the table once per launch, so fewer, larger launches halve its traffic on a 500 000-genome index)
   if (pre && per_query * chunk > ((size_t)8 << 30)) chunk = std::max<uint32_t>(256, (uint32_t)((((size_t)8 << 30) / per_query) & ~(size_t)255));
   if (pre) {
-    if (nq::lookup_wants_packed(v) && !ix->ptab_ok) {   // packed copy of the table, once per build
-      const size_t want = (size_t)f_local * ix->d.R * ix->n_tiles * 4;
-      if (want > ix->ptab_bytes) {
-        if (ix->ptab) NQ_HIP(ix, hipFree(ix->ptab));
-        ix->ptab = nullptr; ix->ptab_bytes = 0;
-        NQ_HIP(ix, hipMalloc((void **)&ix->ptab, want));
-        ix->ptab_bytes = want;
+    if (nq::lookup_wants_packed(v) && !seg.ptab_ok) {   // packed copy of the table, once per build
+      const size_t want = (size_t)f_local * ix->d.R * seg.n_tiles * 4;
+      if (want > seg.ptab_bytes) {
+        if (seg.ptab) NQ_HIP(ix, hipFree(seg.ptab));
+        seg.ptab = nullptr; seg.ptab_bytes = 0;
+        NQ_HIP(ix, hipMalloc((void **)&seg.ptab, want));
+        seg.ptab_bytes = want;
       }
-      NQ_HIP(ix, nq::launch_pack_entries(v, ix->ptab, ix->stream));
-      ix->ptab_ok = true;
-      v.ptab = ix->ptab;
+      NQ_HIP(ix, nq::launch_pack_entries(v, seg.ptab, ix->stream));
+      seg.ptab_ok = true;
+      v.ptab = seg.ptab;
     }
     if ((rc = ensure(ix, ix->ws_pre, nq::lookup_pre_bytes(v, std::min(nq, chunk))))) return rc;
-  } else if (ix->n_tiles > 1) {
-    rc = ensure(ix, ix->ws_stash, (size_t)std::min(nq, chunk) * (ix->n_tiles - 1) * f_local * sizeof(nq::Entry));
+  } else if (seg.n_tiles > 1) {
+    rc = ensure(ix, ix->ws_stash, (size_t)std::min(nq, chunk) * (seg.n_tiles - 1) * f_local * sizeof(nq::Entry));
     if (rc) return rc;
   }
   if (ordered && (rc = ensure(ix, ix->ws_order, (size_t)chunk * 8))) return rc;
@@ -204,6 +191,21 @@ int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride,
                                  pre, ix->stream, c));
   }
   return NIQKI_OK;
+}
+
+int counts_resident(niqki_index *ix, const int32_t *sketches, uint32_t q_stride, uint32_t q_off, uint32_t nq,
+                    uint16_t *counts, uint64_t stride, bool accumulate, uint16_t *counts2, const nq::CandOut *co) {
+  int rc = ix->resident_bytes ? NIQKI_OK : build_if_needed(ix);
+  if (rc) return rc;
+  if (nq == 0) return NIQKI_OK;
+  if (counts && (stride < ix->built_n || (stride & 1))) return fail(ix, NIQKI_E_INVALID, "stride must be even and >= genome count");
+  if ((uintptr_t)counts & 3) return fail(ix, NIQKI_E_INVALID, "counts must be 4-byte aligned (rows are written as packed u16 pairs)");
+  if (ix->built_n == 0) return NIQKI_OK;
+  // the delta segment first (its columns are its own), then the main one: the stats of the last launch are the main segment's
+  if (ix->delta.n && !ix->resident_bytes &&
+      (rc = counts_segment(ix, ix->delta, sketches, q_stride, q_off, nq, counts, stride, accumulate, counts2, co)))
+    return rc;
+  return counts_segment(ix, ix->main, sketches, q_stride, q_off, nq, counts, stride, accumulate, counts2, co);
 }
 
 int counter_planes(niqki_index *ix, uint32_t n, uint64_t stride, Planes &pl, bool zeroed) {
@@ -316,9 +318,9 @@ static uint32_t hit_list_cap(const niqki_index *ix) {
 // radix passes, tools/bench_hitlists_overflow.py), and such an index keeps them.
 static bool hit_lists_apply(const niqki_index *ix) {
   const uint32_t N = ix->built_n;
-  return ix->hit_lists && N && !ix->resident_bytes && !two_planes(ix) && ix->delta_n == 0 && ix->g_base == 0 &&
+  return ix->hit_lists && N && !ix->resident_bytes && !two_planes(ix) && ix->delta.n == 0 &&
          (ix->d.min_score > 0 || N <= nq::kHitListMaxTile) &&
-         (ix->n_tiles == 1 || N > nq::kHitListMaxTile) && nq::hit_list_lds(ix->tile, hit_list_cap(ix)) <= nq::kGatherMaxLds;
+         (ix->main.n_tiles == 1 || N > nq::kHitListMaxTile) && nq::hit_list_lds(ix->main.tile, hit_list_cap(ix)) <= nq::kGatherMaxLds;
 }
 
 // Index::query_sketch (src/niqki_index.cpp:633-687) for nq device-resident whole sketches into device buffers: counters,

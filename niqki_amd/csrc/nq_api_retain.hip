@@ -1,30 +1,15 @@
 // nq_api_retain.hip -- niqki_retain behind the C ABI: drop genomes from a handle.  The sketch store's kept columns are
 // compacted on the device into a new, smaller store (nq_index.hip: the rank pass and store_compact_kernel; block
-// arithmetic in nq_retain_blocks.h) and every index segment is dropped, so the next use rebuilds ONE main segment from
-// what is left.  A paged handle's store is page-locked host memory: the host compacts its rows in place.  DESIGN.md 4.6d.
+// arithmetic in nq_retain_blocks.h) and both index segments are released (release_segments), so the next use builds ONE
+// main segment from what is left.  A paged handle's store is page-locked host memory: the host compacts its rows in
+// place.  How the handle takes the new store is shared with niqki_unite (nq_api_build.hip: adopt_store,
+// host_store_rewritten).  DESIGN.md 4.6d.
 #include "nq_handle.h"
 
 #include <string>
 #include <vector>
 
 namespace nqi {
-
-// both segments' index buffers back to the device: nothing of them describes the genomes that are left
-void release_segments(niqki_index *ix) {
-  auto &a = ix->alt;
-  for (void *p : {(void *)ix->entries, (void *)ix->gids, (void *)ix->tile_base, (void *)ix->slot_units, (void *)ix->ptab,
-                  (void *)ix->hmask, (void *)a.entries, (void *)a.gids, (void *)a.tile_base, (void *)a.slot_units, (void *)a.ptab,
-                  (void *)a.hmask})
-    if (p) (void)hipFree(p);
-  a = niqki_index::Seg();
-  ix->entries = nullptr; ix->gids = nullptr; ix->tile_base = nullptr; ix->slot_units = nullptr; ix->ptab = nullptr; ix->hmask = nullptr;
-  ix->entries_bytes = ix->gids_bytes = ix->tile_base_bytes = ix->slot_units_bytes = ix->ptab_bytes = ix->hmask_bytes = 0;
-  ix->ptab_ok = ix->hmask_ok = false;
-  ix->tile = ix->n_tiles = ix->align_log2 = ix->padded = ix->stripe = 0;
-  ix->built = false;
-  ix->built_n = 0;
-  ix->delta_n = ix->seg_n = ix->g_base = 0;
-}
 
 namespace {
 
@@ -104,14 +89,7 @@ int retain_run(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32_t
   release_segments(ix);
   if (ix->resident_bytes) {
     compact_host_store(ix, h_words, N, total);
-    // no page is resident and no dump layout is known; the handle's slots are its whole range again
-    ix->page_begin = ix->page_end = ix->page_n = 0;
-    ix->pg_layout_n = 0xFFFFFFFFu;
-    ix->d.slot_begin = ix->full_begin;
-    ix->d.slot_end = ix->full_end;
-    ix->store = nullptr;
-    ix->cap = 0;
-    ix->n_genomes = total;
+    host_store_rewritten(ix, total);
     return NIQKI_OK;
   }
   const uint32_t f_local = ix->d.slot_end - ix->d.slot_begin;
@@ -132,12 +110,7 @@ int retain_run(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32_t
     (void)hipFree(ns);
     return fail(ix, NIQKI_E_HIP, std::string("niqki_retain: store compaction: ") + hipGetErrorString(e));
   }
-  uint16_t *old = ix->store;
-  ix->store = ns;
-  ix->cap = cap;
-  ix->n_genomes = total;
-  NQ_HIP(ix, hipFree(old));
-  return NIQKI_OK;
+  return adopt_store(ix, ns, cap, total);
 }
 
 }  // namespace

@@ -90,14 +90,7 @@ int unite_run(niqki_index *ix, const uint32_t *labels, uint32_t *new_ids, uint32
     NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // a page copy that still reads the host store
     release_segments(ix);
     unite_host_store(ix, g);
-    // no page is resident and no dump layout is known; the handle's slots are its whole range again
-    ix->page_begin = ix->page_end = ix->page_n = 0;
-    ix->pg_layout_n = 0xFFFFFFFFu;
-    ix->d.slot_begin = ix->full_begin;
-    ix->d.slot_end = ix->full_end;
-    ix->store = nullptr;
-    ix->cap = 0;
-    ix->n_genomes = L;
+    host_store_rewritten(ix, L);
     if (ix->prof) ix->unite_ms[1] = ms_since(t1);
     return NIQKI_OK;
   }
@@ -139,12 +132,7 @@ int unite_run(niqki_index *ix, const uint32_t *labels, uint32_t *new_ids, uint32
     return fail(ix, NIQKI_E_HIP, std::string("niqki_unite: minimum pass: ") + hipGetErrorString(e));
   }
   release_segments(ix);
-  uint16_t *old = ix->store;
-  ix->store = ns;
-  ix->cap = cap;
-  ix->n_genomes = L;
-  NQ_HIP(ix, hipFree(old));
-  return NIQKI_OK;
+  return adopt_store(ix, ns, cap, L);
 }
 
 }  // namespace

@@ -96,43 +96,29 @@ struct niqki_index {
   std::vector<uint64_t> pg_layout;      // dump word positions of all slots (export of a paged index), for pg_layout_n genomes
   uint32_t pg_layout_n = 0xFFFFFFFFu;
 
-  // inverted index
-  uint32_t tile = 0, n_tiles = 0, built_n = 0, align_log2 = 0, padded = 0;
-  nq::Entry *entries = nullptr;
-  uint16_t *gids = nullptr;
-  uint64_t *tile_base = nullptr;   // n_tiles+1, device
-  uint32_t *slot_units = nullptr;  // n_tiles x (f_local+1), device
-  size_t entries_bytes = 0, gids_bytes = 0, tile_base_bytes = 0, slot_units_bytes = 0;
-  uint32_t *ptab = nullptr;        // packed copy of `entries` for the look-up pre-pass (made at its first launch)
-  size_t ptab_bytes = 0;
-  bool ptab_ok = false;
-  uint16_t *hmask = nullptr;       // per slot: which sixteenths of the fingerprint range hold a bucket (IndexView::hmask)
-  size_t hmask_bytes = 0;
-  bool hmask_ok = false;
-  uint32_t stripe = 0;             // tiles are dealt round-robin
-  int stripe_opt = 32;             // option: block size of the stripes when there are several tiles (0 = ranges)
-  int bucket_align = -1;           // option: log2 ids per bucket alignment unit, -1 = choose
-  bool built = false;
-  // Delta segment: genomes inserted after the last full build get an index of their own (same
-  // layout, over store columns [g_base, g_base + seg_n)) instead of a rebuild of everything; a query
-  // walks both, the counter columns are disjoint.  The flat members above describe the CURRENT
-  // segment -- the main one except while swap_segment() has put the delta there (its build, its
-  // gather launch); `alt` keeps the other one's state.
+  // Inverted index: two segments of the same layout.  `main` is what niqki_build makes, over store columns [0, main.n).
+  // Delta segment: genomes inserted after that build get an index of their own over the columns behind the main
+  // segment's, [delta.g_base, delta.g_base + delta.n), instead of a rebuild of everything (build_if_needed); a query
+  // walks the delta, then the main segment, and their counter columns are disjoint.  delta.n == 0: there is none.
+  // What a segment owns is named in three places: here, view() and free_segment() (nq_api_build.hip).
   struct Seg {
     nq::Entry *entries = nullptr;
     uint16_t *gids = nullptr;
-    uint64_t *tile_base = nullptr;
-    uint32_t *slot_units = nullptr;
-    uint32_t *ptab = nullptr;   // packed copy of `entries` for the look-up pre-pass (made at its first launch)
-    uint16_t *hmask = nullptr;
+    uint64_t *tile_base = nullptr;   // n_tiles+1, device
+    uint32_t *slot_units = nullptr;  // n_tiles x (f_local+1), device
+    uint32_t *ptab = nullptr;        // packed copy of `entries` for the look-up pre-pass (made at its first launch)
+    uint16_t *hmask = nullptr;       // per slot: which sixteenths of the fingerprint range hold a bucket (IndexView::hmask)
     size_t entries_bytes = 0, gids_bytes = 0, tile_base_bytes = 0, slot_units_bytes = 0, ptab_bytes = 0, hmask_bytes = 0;
-    uint32_t tile = 0, n_tiles = 0, seg_n = 0, g_base = 0, align_log2 = 0, padded = 0, stripe = 0;
+    uint32_t tile = 0, n_tiles = 0, align_log2 = 0, padded = 0;
+    uint32_t n = 0, g_base = 0;      // the genomes it covers: how many, and the first
+    uint32_t stripe = 0;             // tiles are dealt round-robin
     bool ptab_ok = false, hmask_ok = false;
-  } alt;
-  uint32_t seg_n = 0;      // genomes of the current segment
-  uint32_t g_base = 0;     // its first genome
-  uint32_t delta_n = 0;    // genomes the delta segment covers (0 = there is none)
-  int incremental = 1;     // option "incremental_build"
+  } main, delta;
+  uint32_t built_n = 0;
+  bool built = false;
+  int stripe_opt = 32;             // option: block size of the stripes when there are several tiles (0 = ranges)
+  int bucket_align = -1;           // option: log2 ids per bucket alignment unit, -1 = choose
+  int incremental = 1;             // option "incremental_build"
 
   // niqki_append_begin .. the last niqki_append_slots: the dump's n_new genomes are being written into the store columns
   // [n_genomes, n_genomes + n_new), which no reader looks at; the commit adds n_new to n_genomes (nq_api_dump.hip)
@@ -259,7 +245,8 @@ int fail(niqki_index *ix, int code, const std::string &msg);
 int ensure(niqki_index *ix, Buf &b, size_t bytes);   // device scratch of at least `bytes`
 // ... whose first `keep` bytes stay what they are (nq_api_lists.hip; grows to twice the need, synchronises when it grows)
 int ensure_keep(niqki_index *ix, Buf &b, size_t keep, size_t bytes);
-nq::IndexView view(const niqki_index *ix);
+nq::IndexView view(const niqki_index *ix, const niqki_index::Seg &seg);
+inline nq::IndexView view(const niqki_index *ix) { return view(ix, ix->main); }   // the main segment
 std::string &create_error();   // thread-local: why the last niqki_create / niqki_import_* of the calling thread failed
 int derive(const niqki_params &p, nq::Derived &d, std::string &why);
 int collect_spans(niqki_index *ix);
@@ -271,8 +258,14 @@ uint32_t first_slot(const niqki_index *ix);
 int reserve_store(niqki_index *ix, uint64_t want);
 int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, uint32_t n_rec, const uint32_t *entry_rec,
                uint32_t n_entry, int32_t *sketches, uint64_t total_bytes);
-void swap_segment(niqki_index *ix);   // flat index members <-> alt ("Delta segment" above)
-int build_range(niqki_index *ix, uint32_t g_base, uint32_t N);
+// the store the device has just filled replaces the handle's, for n genomes; a paged handle's host store was rewritten in place
+int adopt_store(niqki_index *ix, uint16_t *ns, uint64_t cap, uint32_t n);
+void host_store_rewritten(niqki_index *ix, uint32_t n);
+int build_range(niqki_index *ix, niqki_index::Seg &seg, uint32_t g_base, uint32_t N);   // store columns [g_base, g_base + N) into seg
+void free_segment(niqki_index::Seg &seg);              // its device buffers back to the device, seg = Seg()
+uint64_t segment_bytes(const niqki_index::Seg &seg);   // what the stat "index_bytes" counts of it
+// both segments freed: the genome set has changed, the next use builds one main segment
+void release_segments(niqki_index *ix);
 int build_if_needed(niqki_index *ix);
 int build_single(niqki_index *ix);    // ONE index over all genomes (dump export, per-bucket statistics)
 // the stored sketches of genomes [t0, t0 + n) as device query rows (resident store, or zero-copy from the paged host store)
@@ -370,9 +363,6 @@ void end_tally(niqki_index *ix);       // the taxonomy is replaced or goes: so d
 void break_tally(niqki_index *ix, const std::string &why);   // an open tally holds part of a call's rows
 // rows [0, n) in device memory into the open tally, in stream order (best_count, considered: may be null)
 int tally_rows_dev(niqki_index *ix, const uint32_t *taxon, const uint32_t *best_count, const uint32_t *considered, uint32_t n);
-// ---- nq_api_retain.hip ----
-// both segments' index buffers back to the device: the genome set has changed, the next use builds one main segment
-void release_segments(niqki_index *ix);
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);

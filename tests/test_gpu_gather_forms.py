@@ -356,6 +356,56 @@ def test_delta_segment_per_block_size(native, n_main, align):
     e.close()
 
 
+def test_delta_segment_transitions(native):
+    """what resets a segment while a delta exists, other than retain / unite / export: an explicit build and the
+    options that ask for a full rebuild.  The stats "tiles" and "bucket_align_log2" are the main segment's."""
+    S, W, tile, n_main, n_delta, ms = 8, 8, 1024, 4097, 500, 80
+    if not _DELTA:
+        sk, fam = gr.families(4097 + n_delta, S, W, seed=8)
+        q, where = gr.family_queries(sk, fam, W)
+        _DELTA.update(sk=sk, q=q, ref=gr.reference_counts(sk, q, W))
+    n = n_main + n_delta
+    sk, q, ref = _DELTA["sk"][:n], _DELTA["q"], _DELTA["ref"][:, :n]
+    lists = gr.reference_hits(ref, ms)
+    capacity = int(lists[0][-1]) + 1
+    assert np.any(lists[2] >= n_main)                                # hits in the delta too
+    # 1: a main segment alone
+    e = engine(native, S, W, sk[:n_main], tile, 0, 0, ms)
+    e.build()
+    assert e.stat("tiles") == 5 and e.stat("delta_genomes") == 0
+    b0 = e.stat("index_bytes")
+    assert b0 > 0
+    # 2: genomes after the build get a delta
+    e.insert(sk[n_main:])
+    same_counts(e.query_counts(q), ref, "delta")
+    assert e.stat("delta_genomes") == n_delta and e.stat("tiles") == 5
+    b1 = e.stat("index_bytes")
+    assert b1 > b0
+    # 3: an explicit build folds it into the main segment and gives its buffers back: the main table keeps its five
+    # tiles, its ids grow by at most 500 x 256 x 2 B, the delta held a table of 256 x 256 x 8 B besides its ids
+    e.build()
+    assert e.stat("delta_genomes") == 0 and e.stat("tiles") == 5
+    assert e.stat("index_bytes") < b1
+    same_counts(e.query_counts(q), ref, "rebuilt")
+    same_hits(e.query(q, capacity=capacity), lists, "rebuilt")
+    e.close()
+    # 4: a tile size set while a delta exists
+    e = engine(native, S, W, sk[:n_main], tile, 0, 0, ms)
+    e.build()
+    e.insert(sk[n_main:])
+    same_counts(e.query_counts(q), ref, "second delta")
+    assert e.stat("delta_genomes") == n_delta
+    e.set_option("tile_genomes", 2048)
+    same_counts(e.query_counts(q), ref, "tile_genomes")
+    assert e.stat("delta_genomes") == 0 and e.stat("tiles") == 3     # 4597 genomes in tiles of 2048
+    same_hits(e.query(q, capacity=capacity), lists, "tile_genomes")
+    # 5: an alignment set with nothing inserted
+    e.set_option("bucket_align_log2", 6)
+    same_counts(e.query_counts(q), ref, "bucket_align_log2")
+    assert e.stat("bucket_align_log2") == 6 and e.stat("delta_genomes") == 0
+    e.close()
+
+
 @pytest.mark.parametrize("align", [0, 2, 6])
 def test_two_planes_per_block_size(native, align):
     """S = 16, two tiles: the slots are walked in two passes into two counter planes; a stored sketch without empty
