@@ -43,7 +43,7 @@
  *   NIQKI_HMASK=0           builds single-tile indexes without their per-slot class mask (stat "class_mask")
  *   NIQKI_SKETCH_WAVE=0     short records take the workgroup sketch kernel instead of the one-wavefront one;
  *   NIQKI_SKETCH_FILTER     0 = long records are sketched without the candidate filter, n >= 2 = with a fixed filter
- *                           strength (default: chosen per sketch).  Test switches of nq_sketch.hip's launch shapes.
+ *                           strength (default: chosen per sketch).  Test switches of the sketch launch rule (nq_sketch_plan.h).
  * The `niqki` host program reads NIQKI_HOST_THREADS (reader threads; default: the CPUs the process may use),
  * NIQKI_HOST_TIMING (phase times on stderr), NIQKI_HOST_NO_PACK (plain FASTA files travel as their bytes),
  * NIQKI_HOST_NO_GPU_INFLATE (gzip files are always inflated by the reader threads), NIQKI_HOST_GPU_INFLATE_MIN (how many

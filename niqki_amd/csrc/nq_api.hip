@@ -116,7 +116,7 @@ int collect_spans(niqki_index *ix) {
 }
 
 int derive(const niqki_params &p, nq::Derived &d, std::string &why) {
-  // (K <= 31 is also what nq_sketch.hip's min62() rests on: both k-mer words stay below 2^62)
+  // (K <= 31 is also what min62() (nq_sketch_ops.h) rests on: both k-mer words stay below 2^62)
   if (p.K < 1 || p.K > 31) { why = "K must be in 1..31"; return NIQKI_E_INVALID; }
   if (p.S < 1 || p.S > 16) { why = "S must be in 1..16"; return NIQKI_E_INVALID; }
   if (p.W < 1 || p.W > 15 || p.H > p.W) { why = "need H <= W <= 15"; return NIQKI_E_INVALID; }

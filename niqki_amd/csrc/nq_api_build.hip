@@ -97,6 +97,7 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
   a.redo = nullptr;
   a.redo_only = a.redo_mark = 0;
   const uint64_t avg = total_bytes / n_entry;
+  const nq::SketchSwitches sw = nq::sketch_switches();
   if (avg >= 16384 && !entry_rec && n_entry < 128 && avg >= (1u << 20))
     a.splits = std::min<uint32_t>(32, 512 / n_entry);
   if (a.splits > 1 || nq::sketch_needs_merge(ix->d)) {  // partial sketches merged in global memory, then densified
@@ -105,7 +106,7 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
       NQ_HIP(ix, nq::launch_fill_u32((uint32_t *)sketches, (uint64_t)n_entry * ix->d.F, nq::kEmpty32,
                                      ix->stream));
       a.densify = 0;
-      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg / a.splits, ix->stream));
+      NQ_HIP(ix, nq::launch_sketch(a, n_entry, nq::sketch_plan(ix->d, avg / a.splits, a.splits, true, false, false, sw), ix->stream));
     }
     Span sp(ix, NIQKI_KC_DENSIFY);
     nq::SketchArgs b = a;
@@ -113,8 +114,14 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
     b.splits = 1;
     b.accumulate = 1;
     b.densify = 1;
-    NQ_HIP(ix, nq::launch_sketch(b, n_entry, (uint64_t)1 << 22, ix->stream, &ix->last_densify_form));
-  } else if (const uint32_t list = nq::sketch_read_list(ix->d, avg)) {
+    const nq::SketchPlan merged = nq::sketch_plan_densify_only(ix->d, sw);
+    ix->last_densify_form = merged.form;
+    NQ_HIP(ix, nq::launch_sketch(b, n_entry, merged, ix->stream));
+    return NIQKI_OK;
+  }
+  const nq::SketchPlan plan = nq::sketch_plan(ix->d, avg, 1, true, false, true, sw);
+  ix->last_densify_form = plan.form;
+  if (plan.shape == nq::kShapeWave) {
     // Short records: the one-wavefront kernel, with its 192-entry list (nine sketches per CU) where the average record
     // has at most 200 bases.  A record with more occupied cells than the list holds -- far longer than the batch's
     // average -- is flagged instead of taking the plain pass over all cells (fifty reads' time) and sketched by the
@@ -125,20 +132,22 @@ int sketch_dev(niqki_index *ix, const uint8_t *seqs, const uint64_t *rec_off, ui
     NQ_HIP(ix, hipMemsetAsync(flags.p, 0, (size_t)n_entry * 4, ix->stream));
     Span sp(ix, NIQKI_KC_SKETCH);
     a.redo = (uint32_t *)flags.p;
-    if (list < 384) {
+    const nq::SketchPlan long_list = nq::sketch_plan_long_list(ix->d, true, false, true, sw);
+    const nq::SketchPlan workgroup = nq::sketch_plan_workgroup(ix->d, true, sw);
+    if (plan.read_entries < nq::kReadMaxEntries) {
       a.redo_only = 0; a.redo_mark = 1;
-      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream, &ix->last_densify_form));
+      NQ_HIP(ix, nq::launch_sketch(a, n_entry, plan, ix->stream));
       a.redo_only = 1; a.redo_mark = 2;
-      NQ_HIP(ix, nq::launch_sketch(a, n_entry, 400, ix->stream));   // (an average that takes the long list)
+      NQ_HIP(ix, nq::launch_sketch(a, n_entry, long_list, ix->stream));
     } else {
       a.redo_only = 0; a.redo_mark = 2;
-      NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream, &ix->last_densify_form));
+      NQ_HIP(ix, nq::launch_sketch(a, n_entry, plan, ix->stream));
     }
     a.redo_only = 2; a.redo_mark = 0;
-    NQ_HIP(ix, nq::launch_sketch(a, n_entry, nq::kSketchWorkgroupLen, ix->stream));
+    NQ_HIP(ix, nq::launch_sketch(a, n_entry, workgroup, ix->stream));
   } else {
     Span sp(ix, NIQKI_KC_SKETCH);
-    NQ_HIP(ix, nq::launch_sketch(a, n_entry, avg, ix->stream, &ix->last_densify_form));
+    NQ_HIP(ix, nq::launch_sketch(a, n_entry, plan, ix->stream));
   }
   (void)n_rec;
   return NIQKI_OK;
@@ -415,8 +424,9 @@ int niqki_densify(niqki_index *ix, int32_t *sketches, uint32_t n, int mem) {
   a.redo_only = a.redo_mark = 0;
   {
     Span sp(ix, NIQKI_KC_DENSIFY);
-    // (an average that picks the one-wavefront kernel with its long entry list)
-    NQ_HIP(ix, nq::launch_sketch(a, n, ix->d.F <= 4096 ? 256 : ((uint64_t)1 << 22), ix->stream, &ix->last_densify_form));
+    const nq::SketchPlan plan = nq::sketch_plan_densify_rows(ix->d, nq::sketch_switches());
+    ix->last_densify_form = plan.form;
+    NQ_HIP(ix, nq::launch_sketch(a, n, plan, ix->stream));
   }
   if (mem == NIQKI_MEM_HOST) {
     NQ_HIP(ix, hipMemcpyAsync(sketches, d_sk, bytes, hipMemcpyDeviceToHost, ix->stream));

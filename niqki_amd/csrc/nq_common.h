@@ -3,10 +3,15 @@
 // by SURVEY.md appendix C; reference lines are cited per function.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// (the plain host headers -- nq_sketch_plan.h -- take Derived from here and compile without HIP)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define NQ_HD __host__ __device__ __forceinline__
+#else
+#define NQ_HD inline
+#endif
 
 namespace nq {
 

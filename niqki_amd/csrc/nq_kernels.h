@@ -3,11 +3,14 @@
 #pragma once
 #include "nq_common.h"
 #include "nq_retain_blocks.h"
+#include "nq_sketch_plan.h"
 #include "nq_unite_blocks.h"
 
 namespace nq {
 
-// ---- sketch (nq_sketch.hip) -------------------------------------------------
+// ---- sketch (nq_sketch.hip, nq_sketch_reads.hip, nq_densify.hip) ------------
+// What the sketch kernels receive.  A caller fills its own fields; the four marked "plan" are written by launch_sketch
+// from the SketchPlan it carries out.
 struct SketchArgs {
   Derived d;
   const uint8_t *seqs;        // record bytes; nullptr = densify-only launch
@@ -15,39 +18,29 @@ struct SketchArgs {
   const uint32_t *entry_rec;  // n_entry+1 or nullptr (one record per sketch)
   int32_t *sketches;          // n_entry x F
   uint32_t splits;            // workgroups per sketch (>1: partial mins merged in global memory)
-  uint32_t halves;            // set by launch_sketch: 2 when the F cells do not fit LDS (S = 16): every workgroup
+  uint32_t halves;            // plan: 2 when the F cells do not fit LDS (S = 16): every workgroup
                               // keeps one half of the slots and sees all k-mers; results merge in global memory
   uint32_t accumulate;        // start from the sketches already in `sketches`
   uint32_t densify;           // run densification before the store (splits == 1 only)
-  uint32_t distinct;          // set by launch_sketch: densify over distinct values (short-read path)
-  uint32_t filter;            // set by launch_sketch: candidate filter for long inputs
-  uint32_t read_entries;      // set by launch_sketch: capacity of the short-read kernel's entry list (192 or 384)
+  uint32_t distinct;          // plan: densify over distinct values (short-read path)
+  uint32_t filter;            // plan: candidate filter for long inputs
+  uint32_t read_entries;      // plan: capacity of the short-read kernel's entry list (192 or 384)
   uint32_t *redo;             // short records: one flag per sketch, or nullptr (then a sketch with more occupied cells than the
                               // one-wavefront kernel's entry list takes the plain pass over all cells)
   uint32_t redo_only;         // != 0: this launch works only on the sketches whose flag has this value
   uint32_t redo_mark;         // != 0 (one-wavefront kernel): a sketch that exceeds the entry list gets this flag and is left
                               // to a later launch -- nothing of it is stored
 };
-// the densification a launch_sketch call chose (stat "last_densify_form")
-enum DensifyForm : uint32_t {
-  kDensifyNone = 0,          // the launch stores the cells as they are
-  kDensifyWave = 1,          // sketch_reads_kernel: entry windows + closed-form tail, or its pass over all cells
-  kDensifyPlain = 2,         // densify_lds inside sketch_kernel
-  kDensifyDistinct = 3,      // densify_lds_distinct inside sketch_kernel
-  kDensifyDistinctLate = 4,  // densify_distinct_kernel, a launch of its own behind sketch_kernel
-  kDensifyGlobal = 5,        // densify_global_kernel (the cells do not fit LDS)
-};
-// avg_len: average input bytes per sketch (picks the launch shape); form (may be nullptr): receives the DensifyForm chosen
-hipError_t launch_sketch(const SketchArgs &a, uint32_t n_entry, uint64_t avg_len,
-                         hipStream_t stream, uint32_t *form = nullptr);
+// Carries out a plan (nq_sketch_plan.h) on n_entry sketches: writes the plan's fields of SketchArgs and launches the
+// plan's kernel, and densify_distinct_kernel behind it where the plan says so.  A refused plan: hipErrorInvalidValue.
+hipError_t launch_sketch(const SketchArgs &a, uint32_t n_entry, const SketchPlan &plan, hipStream_t stream);
+// NIQKI_SKETCH_WAVE and NIQKI_SKETCH_FILTER as they are now (read per call: tests change them between engines of one process)
+SketchSwitches sketch_switches();
 hipError_t launch_fill_u32(uint32_t *p, uint64_t n, uint32_t v, hipStream_t stream);
-// 0: launch_sketch would not take the one-wavefront short-record kernel for this average length; else the capacity of
-// the entry list it would take (192 or 384)
-uint32_t sketch_read_list(const Derived &d, uint64_t avg_len);
-constexpr uint64_t kSketchWorkgroupLen = 4097;   // an average length that makes launch_sketch take the workgroup kernel
-// true: launch_sketch cannot densify inside the kernel for these parameters -- the caller fills the
-// output with "empty" first, launches with densify = 0, then a densify-only launch (seqs = nullptr)
-bool sketch_needs_merge(const Derived &d);
+// the kernels of the other units, launched by launch_sketch with the arguments it has completed
+hipError_t launch_sketch_reads(const SketchArgs &a, uint32_t n_entry, size_t lds, hipStream_t stream);        // nq_sketch_reads.hip
+hipError_t launch_densify_distinct(const SketchArgs &a, uint32_t n_entry, size_t lds, hipStream_t stream);   // nq_densify.hip
+hipError_t launch_densify_global(const SketchArgs &a, uint32_t n_entry, hipStream_t stream);
 
 // ---- sketch store + inverted index (nq_index.hip) ---------------------------
 // Sketch store: u16 [F_local][cap], slot major; 0xFFFF = empty/invalid cell.
@@ -520,7 +513,7 @@ hipError_t launch_synth_reads(uint64_t seed, const uint32_t *family, const uint3
                               const uint64_t *offset, const uint32_t *read_id, uint32_t read_rate14, uint32_t n,
                               uint32_t len, uint64_t stride, uint8_t *out, hipStream_t stream);
 
-// ---- integer-ALU ceiling probes (nq_sketch.hip; measurement support) ----------------------------
+// ---- integer-ALU ceiling probes (nq_probe.hip; measurement support) -----------------------------
 // what = 0: independent 32-bit adds; 1: 32-bit multiplies (v_mul_lo_u32); 2: the sketch kernel's
 // per-k-mer arithmetic alone (roll, canonical choice, high word of the filter hash, K = 31) with no
 // LDS, memory or compaction; 3: v_lshl_add_u32 (the issue class of most vector opcodes).

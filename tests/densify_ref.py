@@ -2,7 +2,7 @@
 cell sets and the case table that tests/test_densify_ref_cpu.py and tests/test_gpu_densify_designed.py share.  CPU only.
 
 The loop every form must reproduce is the serial one of src/niqki_index.cpp:313-331 (oracle/niqki_oracle.c,
-nqo_densify).  model_wave() restates what sketch_reads_kernel does with a row of cells (niqki_amd/csrc/nq_sketch.hip:
+nqo_densify).  model_wave() restates what sketch_reads_kernel does with a row of cells (niqki_amd/csrc/nq_sketch_reads.hip:
 densify_wave_entries_window, densify_tail, densify_wave_cells) in plain Python over the oracle's rev64 / unrev64, and
 names the path the row took:
 
@@ -32,7 +32,7 @@ if ROOT not in sys.path:
 from oracle import pyoracle as po  # noqa: E402
 
 M32 = 0xFFFFFFFF
-LIST_ENTRIES = 384      # kReadMaxEntries: niqki_densify takes the long entry list
+LIST_ENTRIES = 384      # kReadMaxEntries (nq_sketch_plan.h): niqki_densify takes the long entry list
 TAIL_CELLS = 16         # kTailCells
 MUTANTS = ("tie_largest", "no_handback", "mk_not_lowered", "idle_half")
 

@@ -1,4 +1,4 @@
-"""The canonical choice of the sketch kernels is one v_min_f64 on the two k-mer words (nq_sketch.hip min62()).
+"""The canonical choice of the sketch kernels is one v_min_f64 on the two k-mer words (nq_sketch_ops.h min62()).
 That is exact as long as the instruction keeps subnormal bit patterns: a k-mer word below 2^52 is one, and a
 kernel that flushed them to zero would sketch a k-mer of all A instead.  These inputs are rich in such words
 (A and T at 0.4 each, poly-A and poly-T runs longer than K; for K <= 26 EVERY word is below 2^52), and every

@@ -225,7 +225,7 @@ def test_mid_length_records_at_the_default_sketch_size(native, po, seed):
 
 @pytest.mark.parametrize("S,W", [(12, 10), (15, 12), (14, 12)])
 def test_launch_shape_boundaries(native, po, S, W):
-    """Batches of ONE record length on either side of every length at which launch_sketch changes the kernel shape, the
+    """Batches of ONE record length on either side of every length at which the launch rule (nq_sketch_plan.h) changes the kernel shape, the
     entry list or the densification (200 / 201: the entry list of the one-wavefront kernel; 415 / 416: one-wavefront or
     workgroup kernel; 16 383 / 16 384: 256 or 1024 threads; 2^18, 2^19 - 1 / 2^19: the distinct-value launch of its own;
     2^21: the chunk length) -- every sketch against the oracle."""

@@ -17,7 +17,7 @@ N_CASES = len(_meta["cases"])
 
 
 def length_class(n):
-    """Batches of one class take one form of launch_sketch: the one-wavefront kernel with its 192- or 384-entry list,
+    """Batches of one class take one shape of the sketch launch rule (nq_sketch_plan.h): the one-wavefront kernel with its 192- or 384-entry list,
     the 256-thread workgroup kernel, 1024 threads with 128 or 512 k-mers per lane."""
     return 0 if n <= 200 else 1 if n <= 415 else 2 if n < 16384 else 3 if n < (1 << 18) else 4
 

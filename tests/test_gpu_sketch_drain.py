@@ -4,7 +4,7 @@ planted k-mers whose hash is tiny.  canon = unrev(h) for a small h has hash h: p
 and hashes with a zero high word, which take the whole-wave clz64 branch of the fingerprint.
 
 S = 12, W = 12, H = 4; candidate filter automatic ("1") and forced to three leading zeros ("4").  Three cases, each on
-the loop it names (asserted from the shape rule of sketch_dev / launch_sketch, restated in _shape()):
+the loop it names (asserted from the shape rule of sketch_dev / sketch_plan, restated in _shape()):
   * one 2^18-base record: the chunked fast loop of sketch_kernel<1024, 8, 31>, whose last round of chunks is partial
     and takes the generic steps beside it;
   * one 2^21-base entry passed with entry_rec: the line loop of sketch_kernel<1024, 32, 31>;
@@ -98,7 +98,7 @@ def _ref(po, K, n):
 
 def _shape(K, total, n_entry, entry_rec):
     """(BLOCK, GROUPS, KFIX, line loop) of the sketch launch: sketch_dev's cut into parts (nq_api_build.hip) and
-    launch_sketch's thresholds on the average bases per workgroup (nq_sketch.hip)."""
+    sketch_plan's thresholds on the average bases per workgroup (nq_sketch_plan.h)."""
     avg = total // n_entry
     splits = min(32, 512 // n_entry) if (not entry_rec and n_entry < 128 and avg >= (1 << 20)) else 1
     avg //= splits

@@ -1,4 +1,4 @@
-"""The arithmetic identities behind the 64-bit-wide forms of the sketch kernel's hot step (nq_sketch.hip: min62(),
+"""The arithmetic identities behind the 64-bit-wide forms of the sketch kernel's hot step (nq_sketch_ops.h: min62(),
 shl2_add64(), mix_round_hi()), restated with exact integers on the host.  No GPU: the kernels themselves are held to
 the oracle by the GPU suite (tests/test_gpu_canonical_min.py for the subnormal words)."""
 import numpy as np

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Model of the short-read kernel's closed-form densification tail (nq_sketch.hip, densify_tail) against a plain
+"""Model of the short-read kernel's closed-form densification tail (nq_sketch_reads.hip, densify_tail) against a plain
 simulation of the passes (src/niqki_index.cpp:313-331 in its pass-parallel form): random reads are densified by
 windows of 8 passes until at most 16 cells are empty, then once by the passes to the end and once in closed form with
 the kernel's rule for ties (a cell that several entries reach in its pass goes to the smallest index at the START of

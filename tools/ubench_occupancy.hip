@@ -10,6 +10,8 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude tools/ubench_occupancy.hip -o tools/bin/ubench_occupancy
 // (Includes the product source for its helpers; nothing here is part of the product.)
 #include "../niqki_amd/csrc/nq_sketch.hip"
+#include "../niqki_amd/csrc/nq_sketch_reads.hip"   // (launch_sketch reaches the other units' kernels)
+#include "../niqki_amd/csrc/nq_densify.hip"
 
 #include <cstdio>
 

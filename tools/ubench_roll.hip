@@ -23,6 +23,8 @@
 // Prints ns per k-mer step and CU, SIMD cycles per step at the clock measured inside the kernel, and each form
 // relative to form 1.  (Includes the product source for its helpers; nothing here is part of the product.)
 #include "../niqki_amd/csrc/nq_sketch.hip"
+#include "../niqki_amd/csrc/nq_sketch_reads.hip"   // (launch_sketch reaches the other units' kernels)
+#include "../niqki_amd/csrc/nq_densify.hip"
 
 #include <cstdio>
 #include <vector>

@@ -5,6 +5,8 @@
 //   tools/bin/ubench_sketch [n_genomes=1024] [len=5000000] [reps=3] [S=15]
 #define NQ_SKETCH_CLOCK 1
 #include "../niqki_amd/csrc/nq_sketch.hip"
+#include "../niqki_amd/csrc/nq_sketch_reads.hip"   // (launch_sketch reaches the other units' kernels)
+#include "../niqki_amd/csrc/nq_densify.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -41,18 +43,19 @@ int main(int argc, char **argv) {
   for (uint32_t i = 0; i <= n; ++i) h[i] = i * L;
   CK(hipMemcpy(ro, h.data(), (n + 1) * 8, hipMemcpyHostToDevice));
   nq::SketchArgs a{};
-  a.d = d; a.seqs = seq; a.rec_off = ro; a.entry_rec = nullptr; a.sketches = sk; a.splits = 1; a.halves = 1;
+  a.d = d; a.seqs = seq; a.rec_off = ro; a.entry_rec = nullptr; a.sketches = sk; a.splits = 1;
   a.accumulate = 0; a.densify = 1;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  CK(nq::launch_sketch(a, n, L, 0));
+  const nq::SketchPlan plan = nq::sketch_plan(d, L, 1, true, false, true, nq::sketch_switches());
+  CK(nq::launch_sketch(a, n, plan, 0));
   CK(hipDeviceSynchronize());
   {   // (no tick of an earlier launch may pass for one of the last launch's: a workgroup that records none reads as zeros)
     const std::vector<unsigned long long> zero(18 * nq::kWaveTraceWgs, 0ull);
     CK(hipMemcpyToSymbol(HIP_SYMBOL(nq::nq_sketch_wave), zero.data(), zero.size() * 8));
   }
   CK(hipEventRecord(e0));
-  for (int r = 0; r < reps; ++r) CK(nq::launch_sketch(a, n, L, 0));
+  for (int r = 0; r < reps; ++r) CK(nq::launch_sketch(a, n, plan, 0));
   CK(hipEventRecord(e1));
   CK(hipEventSynchronize(e1));
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));
@@ -118,7 +121,7 @@ int main(int argc, char **argv) {
   const uint32_t nc = n < 8 ? n : 8;
   setenv("NIQKI_SKETCH_FILTER", "0", 1);
   a.sketches = sk2;
-  CK(nq::launch_sketch(a, nc, L, 0));
+  CK(nq::launch_sketch(a, nc, nq::sketch_plan(d, L, 1, true, false, true, nq::sketch_switches()), 0));
   CK(hipDeviceSynchronize());
   std::vector<int32_t> x((size_t)nc * d.F), y((size_t)nc * d.F);
   CK(hipMemcpy(x.data(), sk, x.size() * 4, hipMemcpyDeviceToHost));
