@@ -971,8 +971,9 @@ int niqki_group_staged_query(niqki_group *g, uint32_t per, const uint32_t *n_ent
  * the built index or resident page), "tiles", "pages" / "page_slots" (pages a query walks and
  * slots per page; 1 / all slots unless the index is paged), "delta_genomes" (genomes indexed by
  * the delta segment, see option "incremental_build"), "last_gather_form" (launch form the last
- * counter call used: bit 0 look-up pre-pass, bit 1 its streamed-rows kernel, bit 2 locality
- * order), "last_gather_kernel" (the gather kernel instantiation the last counter call launched:
+ * counter call used: bit 0 look-up pre-pass, bit 1 the packed copy of the table was prepared
+ * for it -- its launches of at least 512 queries take the streamed-rows kernel, smaller ones
+ * the random look-ups --, bit 2 locality order), "last_gather_kernel" (the gather kernel instantiation the last counter call launched:
  * BLOCK | UNROLL << 12 | (NT + 1) << 20 | PAD << 24 -- threads per workgroup, bucket lines per round trip,
  * NT = -1 look-ups from the pre-pass, 2..4 the stash form of that many tiles, 1 one look-up per tile; PAD = 1
  * the padded walk was launched, which takes "bucket_align_log2" 6 and a 1024-thread shape; option

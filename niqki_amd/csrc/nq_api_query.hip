@@ -95,71 +95,38 @@ int counts_dev(niqki_index *ix, const int32_t *sketches, uint32_t q_stride, uint
 static int counts_segment(niqki_index *ix, niqki_index::Seg &seg, const int32_t *sketches, uint32_t q_stride, uint32_t q_off, uint32_t nq,
                           uint16_t *counts, uint64_t stride, bool accumulate, uint16_t *counts2, const nq::CandOut *co) {
   int rc;
-  // launches of at most `chunk` queries bound the per-query stash (one Entry per
-  // slot and extra tile) whatever the caller's batch size is
-  const uint32_t f_local = ix->d.slot_end - ix->d.slot_begin;
   nq::IndexView v = view(ix, seg);
   v.q_stride = q_stride;
   v.q_off = q_off;
   v.accumulate = accumulate ? 1u : 0u;
-  // Table look-ups: inside the gather kernel (one random table line per query and slot), or
-  // by the slot-major pre-pass, which walks the table once per launch for all its queries.
-  bool pre = ix->lookup_prepass != 0 && nq::launch_lookup_usable(v) && (((uintptr_t)(sketches + q_off)) & 15) == 0 && (q_stride & 3) == 0;
-  // Measured at the north-star shape (profiles/r02_*): with random 16-byte look-ups (lookup_kernel) the
-  // pre-pass takes 16 % of the HBM traffic off a launch but not its time -- both forms are bound by the
-  // number of random line requests a CU keeps in flight, and inside the gather kernel the look-ups
-  // overlap with the bucket walk.  The default (-1) therefore takes the pre-pass only where it wins:
-  // An index of more than 4 tiles (> 261 632 genomes) is different: inside the kernel only 4 tiles'
-  // entries can be parked per look-up, so every further tile would cost its own random table line
-  // per query and slot; there the pre-pass is the default for real batches.
-  // Up to 2 tiles of W <= 12 the pre-pass has a form that streams whole table rows through LDS from a
-  // packed copy of the table (lookup_rows_kernel): 0.75 ms per 4096 queries, the launch 8 % faster than
-  // with the look-ups inside the gather kernel -- the default for batches of >= 1024 queries.
-  // (not on a paged index: the packed copy would be made again for every page, outside its memory budget)
-  if (ix->lookup_prepass < 0)
-    pre = pre && ((seg.n_tiles > 4 && nq >= 256) || (nq::lookup_wants_packed(v) && nq >= 1024 && !ix->resident_bytes && seg.n_tiles <= 2));
-  // locality order of each launch: worth its probe on large indexes and real batches.  It takes ~8 % off
-  // the gather kernel and costs 0.1 ms per 4096 queries at 100 000 genomes whatever the slot count:
-  // measured even on a slot shard of 4096 slots (1.56 against 1.57 ms per 4096 queries), +4 % at 8192.
-  const bool ordered = ix->query_order && nq >= 64 && seg.n < (1u << 20) - 1 &&
-                       (ix->query_order >= 2 || (seg.n >= 16384 && f_local >= 8192));
-  // launches of at most `chunk` queries: the order kernel sorts <= 4096, and the per-query scratch
-  // (stash or pre-pass words) stays <= 128 MiB whatever the caller's batch size is (bigger launches are
-  // no faster: 32 768 query shards in one launch take 8 x the time of 4096)
-  const size_t per_query = pre ? nq::lookup_pre_bytes(v, 1) : (size_t)(seg.n_tiles - 1) * f_local * sizeof(nq::Entry);
-  uint32_t chunk = nq;
-  if (per_query) chunk = (uint32_t)std::max<size_t>(4096, ((size_t)128 << 20) / per_query);
-  if (ordered || pre) chunk = 4096;
-  // (the pre-pass words of a launch: at most 8 GiB -- a launch of 4096 queries on up to 16 tiles at S = 15; the streamed
-  // form reads the table once per launch, so fewer, larger launches halve its traffic on a 500 000-genome index)
-  if (pre && per_query * chunk > ((size_t)8 << 30)) chunk = std::max<uint32_t>(256, (uint32_t)((((size_t)8 << 30) / per_query) & ~(size_t)255));
-  if (pre) {
-    if (nq::lookup_wants_packed(v) && !seg.ptab_ok) {   // packed copy of the table, once per build
-      const size_t want = (size_t)f_local * ix->d.R * seg.n_tiles * 4;
-      if (want > seg.ptab_bytes) {
-        if (seg.ptab) NQ_HIP(ix, hipFree(seg.ptab));
-        seg.ptab = nullptr; seg.ptab_bytes = 0;
-        NQ_HIP(ix, hipMalloc((void **)&seg.ptab, want));
-        seg.ptab_bytes = want;
-      }
-      NQ_HIP(ix, nq::launch_pack_entries(v, seg.ptab, ix->stream));
-      seg.ptab_ok = true;
-      v.ptab = seg.ptab;
+  // what the launches run, how many queries each takes and the scratch they need: the plan (nq_gather_plan.h)
+  const bool aligned = (((uintptr_t)(sketches + q_off)) & 15) == 0 && (q_stride & 3) == 0;
+  const nq::GatherPlan plan = nq::gather_plan(nq::gather_facts(v), nq::GatherOptions{ix->lookup_prepass, ix->query_order, ix->gather_variant, ix->resident_bytes != 0},
+                                              aligned, nq::gather_pad_at_zero(), nq, co && co->hl ? co->hl_cap : 0u);
+  const uint32_t chunk = plan.chunk;
+  if (plan.stash_bytes && (rc = ensure(ix, ix->ws_stash, plan.stash_bytes))) return rc;
+  if (plan.pre_bytes && (rc = ensure(ix, ix->ws_pre, plan.pre_bytes))) return rc;
+  if (plan.order_bytes && (rc = ensure(ix, ix->ws_order, plan.order_bytes))) return rc;
+  if (plan.packed_table && !seg.ptab_ok) {   // packed copy of the table, once per build
+    const size_t want = (size_t)v.f_local * ix->d.R * seg.n_tiles * 4;
+    if (want > seg.ptab_bytes) {
+      if (seg.ptab) NQ_HIP(ix, hipFree(seg.ptab));
+      seg.ptab = nullptr; seg.ptab_bytes = 0;
+      NQ_HIP(ix, hipMalloc((void **)&seg.ptab, want));
+      seg.ptab_bytes = want;
     }
-    if ((rc = ensure(ix, ix->ws_pre, nq::lookup_pre_bytes(v, std::min(nq, chunk))))) return rc;
-  } else if (seg.n_tiles > 1) {
-    rc = ensure(ix, ix->ws_stash, (size_t)std::min(nq, chunk) * (seg.n_tiles - 1) * f_local * sizeof(nq::Entry));
-    if (rc) return rc;
+    NQ_HIP(ix, nq::launch_pack_entries(v, seg.ptab, ix->stream));
+    seg.ptab_ok = true;
+    v.ptab = seg.ptab;
   }
-  if (ordered && (rc = ensure(ix, ix->ws_order, (size_t)chunk * 8))) return rc;
-  ix->last_form = (pre ? 1u : 0u) | (pre && nq::lookup_wants_packed(v) ? 2u : 0u) | (ordered ? 4u : 0u);
-  ix->last_kernel = nq::gather_shape_code(nq::gather_shape(v, ix->gather_variant, pre));   // what launch_gather launches below
+  ix->last_form = (plan.pre ? 1u : 0u) | (plan.packed_table ? 2u : 0u) | (plan.ordered ? 4u : 0u);
+  ix->last_kernel = nq::gather_shape_code(plan.shape);   // what launch_gather launches below
   for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t n = std::min(chunk, nq - q0);
     Span sp(ix, NIQKI_KC_GATHER);
     const uint32_t *order = nullptr;
-    const bool fork = ordered && n >= 64 && pre;   // probe + order beside the pre-pass (both only read the sketches)
-    if (fork) {
+    const nq::OrderForm of = nq::order_form(plan, n);   // fork: probe + order beside the pre-pass (both only read the sketches)
+    if (of.fork) {
       if (!ix->aux_stream) {
         if (ix->stream_prio_set) NQ_HIP(ix, hipStreamCreateWithPriority(&ix->aux_stream, hipStreamNonBlocking, ix->stream_prio));
         else NQ_HIP(ix, hipStreamCreateWithFlags(&ix->aux_stream, hipStreamNonBlocking));
@@ -169,15 +136,15 @@ static int counts_segment(niqki_index *ix, niqki_index::Seg &seg, const int32_t 
       NQ_HIP(ix, hipEventRecord(ix->ev_fork, ix->stream));
       NQ_HIP(ix, hipStreamWaitEvent(ix->aux_stream, ix->ev_fork, 0));
     }
-    if (ordered && n >= 64) {
+    if (of.ordered) {
       uint32_t *keys = (uint32_t *)ix->ws_order.p;
-      NQ_HIP(ix, nq::launch_order(v, sketches + (size_t)q0 * q_stride, n, keys, keys + chunk, fork ? ix->aux_stream : ix->stream));
+      NQ_HIP(ix, nq::launch_order(v, sketches + (size_t)q0 * q_stride, n, keys, keys + chunk, of.fork ? ix->aux_stream : ix->stream));
       order = keys + chunk;
-      if (fork) NQ_HIP(ix, hipEventRecord(ix->ev_join, ix->aux_stream));
+      if (of.fork) NQ_HIP(ix, hipEventRecord(ix->ev_join, ix->aux_stream));
     }
-    if (pre)
-      NQ_HIP(ix, nq::launch_lookup(v, sketches + (size_t)q0 * q_stride, n, (uint32_t *)ix->ws_pre.p, ix->stream));
-    if (fork) NQ_HIP(ix, hipStreamWaitEvent(ix->stream, ix->ev_join, 0));
+    if (plan.pre)
+      NQ_HIP(ix, nq::launch_lookup(v, sketches + (size_t)q0 * q_stride, n, (uint32_t *)ix->ws_pre.p, nq::lookup_form(plan, n), ix->stream));
+    if (of.fork) NQ_HIP(ix, hipStreamWaitEvent(ix->stream, ix->ev_join, 0));
     nq::CandOut c;
     if (co) {
       c = *co;
@@ -187,8 +154,8 @@ static int counts_segment(niqki_index *ix, niqki_index::Seg &seg, const int32_t 
     }
     NQ_HIP(ix, nq::launch_gather(v, sketches + (size_t)q0 * q_stride, n, counts ? counts + (size_t)q0 * stride : nullptr,
                                  counts2 ? counts2 + (size_t)q0 * stride : nullptr, stride,
-                                 pre ? (nq::Entry *)ix->ws_pre.p : (nq::Entry *)ix->ws_stash.p, order, ix->gather_variant,
-                                 pre, ix->stream, c));
+                                 plan.pre ? (nq::Entry *)ix->ws_pre.p : (nq::Entry *)ix->ws_stash.p, order, plan.shape,
+                                 plan.lds_bytes, ix->stream, c));
   }
   return NIQKI_OK;
 }

@@ -13,21 +13,15 @@
 // u16 genome ids of one 128-byte aligned bucket.  HBM-bound by design:
 // algorithmic bytes per query = 4T + 20F.  On large indexes the
 // queries of a launch are first put into a locality order (probe_kernel,
-// order_kernel): similar queries then run on the same XCD at the same time and
+// order_kernel: nq_order.hip): similar queries then run on the same XCD at the same time and
 // share their table and bucket lines through its L2.  For real batches the table
 // look-ups are taken out of the kernel altogether by a pre-pass (lookup_rows_kernel
-// / lookup_kernel) that walks the table slot block by slot block for all queries of
+// / lookup_kernel: nq_lookup.hip) that walks the table slot block by slot block for all queries of
 // the launch; the gather kernel then reads one packed word per (tile, slot).
-#include "nq_kernels.h"
-
-#include <algorithm>
-#include <cstdlib>
+// Which of these a launch takes, and which gather_kernel instantiation: nq_gather_plan.h; launch_gather carries it out.
+#include "nq_gather_ops.h"
 
 namespace nq {
-
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_cvoid;
 
 __device__ __forceinline__ void bump(uint32_t *cnt, uint32_t g) {
   atomicAdd(&cnt[g >> 1], 1u << ((g & 1u) * 16u));  // ds_add_u32, result unused
@@ -45,8 +39,7 @@ __device__ __forceinline__ void bump_if(uint32_t *cnt, uint32_t g, bool on, uint
 struct Item {
   uint32_t pos, len;
 };
-constexpr uint32_t kQueue = 256;  // items per wave-private LDS work queue
-static_assert(hit_list_lds(0, 0) == kPadWords * 4 + 16 * kQueue * sizeof(Item), "hit_list_lds (nq_kernels.h) counts these queues");
+static_assert(sizeof(Item) == kItemBytes, "gather_lds_bytes (nq_gather_plan.h) counts the queues of kQueue such items");
 
 // Walks 64 chunks held one per lane (pos, len <= 64): all lanes read consecutive
 // u16 ids of one chunk, UNROLL chunks per round trip, two rounds in flight (the
@@ -187,7 +180,7 @@ struct PairWalk {
 // fingerprints two.  Buckets are cut into chunks of <= 64 ids that go through a
 // wave-private LDS queue, so the walk always runs on full batches of 64 chunks
 // whatever the bucket lengths are.
-//   PRE      : entries come from the slot-major look-up pre-pass (lookup_kernel below): one
+//   PRE      : entries come from the slot-major look-up pre-pass (nq_lookup.hip): one
 //              packed word per (query, tile, slot) = bucket start relative to the slot's first
 //              unit << 16 | length, read coalesced; no table access in this kernel at all.
 //   PAD      : padded index (whole-line chunks): batches go through PairWalk (two lines per load), and the four
@@ -405,356 +398,80 @@ __device__ __forceinline__ void walk_tile(const IndexView &v, const int32_t *sk,
   }
 }
 
-// ---- slot-major look-up pre-pass ---------------------------------------------------------
-// In gather_kernel's own look-up every (query, slot) costs one random 128-byte table line of
-// which 8 * n_tiles bytes are used: 4.2 MB of a 14 MB query at the north-star shape.  For a real
-// batch the table is better walked slot block by slot block for all queries of the launch:
-//   lookup_kernel  one workgroup = PS consecutive slots x 256 queries (one per thread).  A thread
-//                  reads its query's PS fingerprints (one whole 128-byte line of the sketch for
-//                  PS = 32), looks each one up with one 8 * n_tiles byte load, 8 slots in flight
-//                  at a time, packs the results and stores, per tile, PS words = one whole line
-//                  of pre[q][t][s].
-// All workgroups of one slot block (nq / 256 of them) are neighbours in one XCD's dispatch order
-// (block ids x, x+8, ...): they run at the same time on that XCD and walk the block's rows in
-// the same order, so a table line is fetched from HBM once and served from the XCD's L2 to the
-// other queries that need it (4096 queries into 512 lines per slot).
-// Packed word: (bucket start - first unit of its slot) << 16 | length; launch_lookup_usable()
-// says whether both halves fit 16 bits for the index at hand.
-// HBM traffic per launch: the table once + 4 bytes per (query, slot) in and 4 * n_tiles out,
-// instead of 128 bytes per (query, slot).
-constexpr uint32_t kXcds = 8;
-constexpr uint32_t kPreBlock = 256;      // queries per lookup workgroup, one per thread
-constexpr uint32_t kPreFlight = 8;       // look-ups in flight per thread
-
-// NT tiles from tile t0 on per launch: an index of more than 4 tiles takes several launches.
-template <int NT, int PS>
-__global__ __launch_bounds__(kPreBlock) void lookup_kernel(IndexView v, const int32_t *sketches, uint32_t nq,
-                                                           uint32_t n_qchunk, uint32_t *pre, uint32_t t0) {
-  const uint32_t tid = threadIdx.x;
-  const uint32_t n_sb = v.f_local / PS;
-  const uint32_t x = blockIdx.x % kXcds, k = blockIdx.x / kXcds;
-  const uint32_t sb = (k / n_qchunk) * kXcds + x;
-  if (sb >= n_sb) return;   // padding block (uniform)
-  const uint32_t q = (k % n_qchunk) * kPreBlock + tid;
-  if (q >= nq) return;      // no barrier below
-  const uint32_t R = v.d.R;
-  // this thread's fingerprints (src/niqki_index.cpp:654: anything outside [0, R) has no bucket)
-  int32_t fp[PS];
-  {
-    const int4 *src = (const int4 *)(sketches + (uint64_t)q * v.q_stride + v.q_off + (uint64_t)sb * PS);
-#pragma unroll
-    for (int u = 0; u < PS / 4; ++u) {
-      const int4 a = src[u];
-      fp[4 * u] = a.x; fp[4 * u + 1] = a.y; fp[4 * u + 2] = a.z; fp[4 * u + 3] = a.w;
-    }
-  }
-  uint32_t res[NT][PS];
-#pragma unroll
-  for (int i0 = 0; i0 < PS; i0 += kPreFlight) {
-    Entry en[kPreFlight][NT];
-#pragma unroll
-    for (int j = 0; j < (int)kPreFlight; ++j) {   // all loads of the group first
-      const int i = i0 + j;
-      const bool ok = fp[i] >= 0 && (uint32_t)fp[i] < R;
-      const Entry *e = v.entries + ((uint64_t)(sb * PS + i) * R + (ok ? (uint32_t)fp[i] : 0u)) * v.n_tiles + t0;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) en[j][t] = e[t];
-    }
-#pragma unroll
-    for (int j = 0; j < (int)kPreFlight; ++j) {
-      const int i = i0 + j;
-      const bool ok = fp[i] >= 0 && (uint32_t)fp[i] < R;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const uint32_t base = v.slot_units[(uint64_t)(t0 + t) * (v.f_local + 1) + sb * PS + i];
-        res[t][i] = ok ? (((en[j][t].start - base) << 16) | en[j][t].len) : 0u;
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    uint4 *dst = (uint4 *)(pre + ((uint64_t)q * v.n_tiles + t0 + t) * v.f_local + (uint64_t)sb * PS);
-#pragma unroll
-    for (int u = 0; u < PS / 4; ++u) dst[u] = make_uint4(res[t][4 * u], res[t][4 * u + 1], res[t][4 * u + 2], res[t][4 * u + 3]);
-  }
-}
-
-// The same pre-pass with the table rows staged in LDS (1 or 2 tiles, R * tiles * 4 = 16 or 32 KB),
-// from the PACKED copy of the table (IndexView::ptab: the 4-byte word of every entry): one workgroup
-// = 32 consecutive slots x 1024 queries (one per thread).  Slot by slot the 1024 threads copy the
-// slot's whole row (coalesced 16-byte loads straight into LDS: the table is streamed, not hit at
-// random), three rows ahead, and every thread picks its query's word(s) with one LDS read.  At the end the 32 words per (query, tile) go through LDS once more so that
-// eight neighbouring lanes store one 128-byte line of pre[q][t][s] together.  The workgroups of one
-// slot block (nq / 1024) are neighbours in one XCD's dispatch order: the row comes from HBM once.
-constexpr uint32_t kRowSlots = 32, kRowBlock = 1024;
-// The packed table (IndexView::ptab, one word per entry) keeps the tiles in GROUPS of two: the words of tiles
-// t0, t0 + 1 (t0 even) of all slots lie together as [f_local][R][2] from this word on ([f_local][R][1] for a last
-// odd tile) -- a launch over one group streams exactly its own rows.  With <= 2 tiles this is the whole table.
-__host__ __device__ inline uint64_t packed_table_offset(const IndexView &v, uint32_t t0) { return (uint64_t)v.f_local * v.d.R * t0; }
-__device__ __forceinline__ void wave_lds_fence() {   // this wave's LDS traffic so far has completed
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-__device__ __forceinline__ void lds_barrier() {   // a workgroup barrier that waits for LDS traffic only:
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the row loads in flight stay in flight
-}
-// NT tiles from tile t0 on per launch (a tile GROUP: the packed table keeps the rows of a group together, see
-// packed_table_offset): an index of more than 2 tiles takes ceil(n_tiles / 2) launches, each streaming its group's
-// part of the table once.
-template <int NT, int PER>   // PER: 16-byte pieces of a packed row per thread (R * NT / 4096)
-__global__ __launch_bounds__(kRowBlock) void lookup_rows_kernel(IndexView v, const int32_t *sketches, uint32_t nq,
-                                                                uint32_t n_qchunk, uint32_t *pre, uint32_t t0) {
-  extern __shared__ __align__(16) uint32_t rows[];   // 4 buffers of R * NT words; at the end 1024 x 17 words
-  const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  const uint32_t n_sb = v.f_local / kRowSlots;
-  const uint32_t x = blockIdx.x % kXcds, k = blockIdx.x / kXcds;
-  const uint32_t sb = (k / n_qchunk) * kXcds + x;
-  if (sb >= n_sb) return;   // padding block (uniform)
-  const uint32_t q0 = (k % n_qchunk) * kRowBlock, q = q0 + tid;
-  const bool live = q < nq;   // the others still help to stage the rows
-  const uint32_t R = v.d.R, RW = R * NT;
-  int32_t fp[kRowSlots];
-  {
-    const int4 *src = (const int4 *)(sketches + (uint64_t)(live ? q : 0u) * v.q_stride + v.q_off + (uint64_t)sb * kRowSlots);
-#pragma unroll
-    for (int u = 0; u < (int)kRowSlots / 4; ++u) {
-      const int4 a = src[u];
-      fp[4 * u] = a.x; fp[4 * u + 1] = a.y; fp[4 * u + 2] = a.z; fp[4 * u + 3] = a.w;
-    }
-  }
-  // Rows travel memory -> LDS directly (global_load_lds_dwordx4: a wave's 64 lanes fill 1 KB of LDS from
-  // the wave-uniform base on, no registers, no ds_write).  The compiler would wait for ALL such loads in
-  // flight before any LDS read it can see, so the pipeline's waits and the look-up read are written by
-  // hand: loads of one kind retire in issue order (vmcnt), and a wave passes the row's barrier only when
-  // its own pieces of that row have landed.
-  const uint4 *row0 = (const uint4 *)(v.ptab + packed_table_offset(v, t0) + (uint64_t)sb * kRowSlots * RW) + tid;
-  const uint32_t row_u4 = RW / 4;   // 16-byte pieces per row
-  const uint32_t wbase = tid & ~63u;
-  auto request = [&](int i) {
-    uint32_t *dst = rows + (uint32_t)(i & 3) * RW;
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-      __builtin_amdgcn_global_load_lds((glb_cvoid *)(row0 + (uint64_t)i * row_u4 + (uint32_t)j * kRowBlock),
-                                       (lds_void *)(dst + ((uint32_t)j * kRowBlock + wbase) * 4u), 16, 0, 0);
-  };
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void *)rows;   // LDS byte address of the row buffers
-  uint32_t res[NT][kRowSlots];
-  request(0);
-  request(1);
-  request(2);
-  // step I: own pieces of row I landed (only the 2 newer rows' loads may be outstanding) -> barrier: the
-  // whole row is in LDS and everybody is done with row I - 1, whose buffer row I + 3 may now overwrite
-#define NQ_ROW_STEP(I)                                                                                \
-  {                                                                                                   \
-    if ((I) + 2 < (int)kRowSlots) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");      \
-    else if ((I) + 1 < (int)kRowSlots) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");     \
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                             \
-    lds_barrier();                                                                                    \
-    if ((I) + 3 < (int)kRowSlots) request((I) + 3);                                                   \
-    const bool ok = fp[(I)] >= 0 && (uint32_t)fp[(I)] < R; /* src/niqki_index.cpp:654 */              \
-    const uint32_t at = lds0 + ((uint32_t)((I) & 3) * RW + (ok ? (uint32_t)fp[(I)] : 0u) * NT) * 4u;   \
-    uint32_t w0, w1 = 0;                                                                              \
-    if (NT == 2) {                                                                                    \
-      uint2 w;                                                                                        \
-      asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(at) : "memory");      \
-      w0 = w.x; w1 = w.y;                                                                             \
-    } else {                                                                                          \
-      asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w0) : "v"(at) : "memory");     \
-    }                                                                                                 \
-    res[0][(I)] = ok ? w0 : 0u;                                                                       \
-    res[NT - 1][(I)] = ok ? (NT == 2 ? w1 : w0) : 0u;                                                 \
-  }
-#define NQ_ROW_STEP8(B) NQ_ROW_STEP((B)) NQ_ROW_STEP((B) + 1) NQ_ROW_STEP((B) + 2) NQ_ROW_STEP((B) + 3) \
-                        NQ_ROW_STEP((B) + 4) NQ_ROW_STEP((B) + 5) NQ_ROW_STEP((B) + 6) NQ_ROW_STEP((B) + 7)
-  NQ_ROW_STEP8(0) NQ_ROW_STEP8(8) NQ_ROW_STEP8(16) NQ_ROW_STEP8(24)
-#undef NQ_ROW_STEP8
-#undef NQ_ROW_STEP
-  static_assert(kRowSlots == 32, "the steps above are written out");
-  // Out: thread q holds 32 words per tile = one 128-byte line of pre[q][t][s]; lanes 8j .. 8j + 7 of a
-  // wave store the eight 16-byte pieces of query (wave base + 8 r + j)'s line, r = 0 .. 7, so one store
-  // instruction writes 8 whole lines.  The transposition goes through LDS (33-word rows: no bank conflicts).
-  lds_barrier();   // all look-ups of the last row are done: the row buffers are free
-  uint32_t *mine = rows + tid * (kRowSlots + 1u);
-#define NQ_STORE_TILE(T)                                                                                             \
-  {                                                                                                                  \
-    _Pragma("unroll") for (int i = 0; i < (int)kRowSlots; ++i) mine[i] = res[(T)][i];                               \
-    wave_lds_fence(); /* (one wave reads what its own lanes wrote) */                                                \
-    _Pragma("unroll") for (int r = 0; r < 8; ++r) {                                                                  \
-      const uint32_t src_t = (tid & ~63u) + 8u * (uint32_t)r + (lane >> 3); /* whose line this lane helps to store */ \
-      const uint32_t piece = lane & 7u;                                                                              \
-      const uint32_t *sp = rows + src_t * (kRowSlots + 1u) + piece * 4u;                                             \
-      const uint4 w = make_uint4(sp[0], sp[1], sp[2], sp[3]);                                                        \
-      const uint32_t qq = q0 + src_t;                                                                                \
-      if (qq < nq) *(uint4 *)(pre + ((uint64_t)qq * v.n_tiles + t0 + (T)) * v.f_local + (uint64_t)sb * kRowSlots + piece * 4u) = w; \
-    }                                                                                                                \
-    wave_lds_fence(); /* before the next tile overwrites the wave's words */                                         \
-  }
-  NQ_STORE_TILE(0)
-  if (NT == 2) NQ_STORE_TILE(NT - 1)
-#undef NQ_STORE_TILE
-}
-// Packed rows that the LDS buffers hold, dealt to 1024 threads in whole 16-byte loads: tiles are taken two at a
-// time (rows of 2 R words = 32 KB at W = 12), a last odd tile alone.
-bool lookup_wants_packed(const IndexView &v) {
-  if (!launch_lookup_usable(v) || v.f_local % kRowSlots) return false;
-  auto row_ok = [&](uint32_t nt) {   // a group's packed row: within 32 KB, whole 16-byte pieces per thread, 1 or 2 of them
-    const uint32_t rw = v.d.R * nt;
-    if (rw * 4u > 32768u || rw % (4u * kRowBlock)) return false;
-    const uint32_t per = rw / (4u * kRowBlock);
-    return per == 1 || per == 2;
-  };
-  if (v.n_tiles >= 2 && !row_ok(2)) return false;
-  if ((v.n_tiles & 1u) && !row_ok(1)) return false;
-  return true;
-}
-
-__global__ __launch_bounds__(256) void pack_entries_kernel(IndexView v, uint32_t *ptab) {
-  const uint64_t n = (uint64_t)v.f_local * v.d.R * v.n_tiles, step = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const uint32_t t = (uint32_t)(i % v.n_tiles);
-    const uint64_t sf = i / v.n_tiles;   // slot * R + fp
-    const uint32_t s = (uint32_t)(sf / v.d.R);
-    const Entry e = v.entries[i];
-    const uint32_t t0 = t & ~1u, nt = v.n_tiles - t0 >= 2 ? 2u : 1u;   // the tile's group
-    ptab[packed_table_offset(v, t0) + sf * nt + (t - t0)] = ((e.start - v.slot_units[(uint64_t)t * (v.f_local + 1) + s]) << 16) | e.len;
-  }
-}
-hipError_t launch_pack_entries(const IndexView &v, uint32_t *ptab, hipStream_t stream) {
-  const uint64_t n = (uint64_t)v.f_local * v.d.R * v.n_tiles;
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(pack_entries_kernel, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 65536)), dim3(256), 0, stream, v, ptab);
-  return hipGetLastError();
-}
-
-static uint32_t lookup_slots(const IndexView &v) { return v.n_tiles <= 2 ? 32u : 16u; }
-
-// Can the pre-pass serve this index?  Whole slot blocks, and both halves of the packed word
-// within 16 bits (bucket lengths <= tile, starts relative to the slot <= tile / unit + R units).
-bool launch_lookup_usable(const IndexView &v) {
-  if (v.n_tiles < 1 || v.f_local % lookup_slots(v)) return false;
-  if (v.tile > 65535u) return false;
-  return (uint64_t)(v.tile >> v.align_log2) + v.d.R + 1 <= 65535u;
-}
-
-size_t lookup_pre_bytes(const IndexView &v, uint32_t nq) { return (size_t)v.f_local * nq * v.n_tiles * 4; }
-
-hipError_t launch_lookup(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *pre, hipStream_t stream) {
-  if (nq == 0 || !launch_lookup_usable(v)) return hipErrorInvalidValue;
-  if (v.ptab && lookup_wants_packed(v) && nq >= kRowBlock / 2) {
-    const uint32_t n_sb = v.f_local / kRowSlots, n_qchunk = (nq + kRowBlock - 1) / kRowBlock;
-    const uint64_t grid = (uint64_t)((n_sb + kXcds - 1) / kXcds * kXcds) * n_qchunk;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipError_t e = hipSuccess;
-#define NQ_LAUNCH_ROWS(NT, PER)                                                                                        \
-  do {                                                                                                                 \
-    e = hipFuncSetAttribute((const void *)lookup_rows_kernel<NT, PER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) return e;                                                                                     \
-    hipLaunchKernelGGL((lookup_rows_kernel<NT, PER>), dim3((uint32_t)grid), dim3(kRowBlock), lds, stream, v, sketches, nq, n_qchunk, pre, t0); \
-  } while (0)
-    for (uint32_t t0 = 0; t0 < v.n_tiles; t0 += 2) {   // tile groups (packed_table_offset)
-      const uint32_t nt = v.n_tiles - t0 >= 2 ? 2u : 1u;
-      const size_t lds = std::max<size_t>((size_t)v.d.R * nt * 4 * 4, (size_t)kRowBlock * (kRowSlots + 1) * 4);
-      const uint32_t per = v.d.R * nt / (4u * kRowBlock);
-      if (nt == 1) { if (per == 1) NQ_LAUNCH_ROWS(1, 1); else NQ_LAUNCH_ROWS(1, 2); }
-      else { if (per == 1) NQ_LAUNCH_ROWS(2, 1); else NQ_LAUNCH_ROWS(2, 2); }
-    }
-#undef NQ_LAUNCH_ROWS
-    return hipGetLastError();
-  }
-  const uint32_t ps = lookup_slots(v);
-  const uint32_t n_sb = v.f_local / ps, n_qchunk = (nq + kPreBlock - 1) / kPreBlock;
-  const uint64_t grid = (uint64_t)((n_sb + kXcds - 1) / kXcds * kXcds) * n_qchunk;
-  if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-#define NQ_LAUNCH_LOOKUP(NT, PS) \
-  hipLaunchKernelGGL((lookup_kernel<NT, PS>), dim3((uint32_t)grid), dim3(kPreBlock), 0, stream, v, sketches, nq, n_qchunk, pre, t0)
-  for (uint32_t t0 = 0; t0 < v.n_tiles; t0 += 4) {   // (blocks of 16 slots whenever there are more than 2 tiles)
-    const uint32_t nt = v.n_tiles - t0 < 4 ? v.n_tiles - t0 : 4;
-    if (ps == 32) { if (nt == 1) NQ_LAUNCH_LOOKUP(1, 32); else NQ_LAUNCH_LOOKUP(2, 32); }
-    else if (nt == 1) NQ_LAUNCH_LOOKUP(1, 16);
-    else if (nt == 2) NQ_LAUNCH_LOOKUP(2, 16);
-    else if (nt == 3) NQ_LAUNCH_LOOKUP(3, 16);
-    else NQ_LAUNCH_LOOKUP(4, 16);
-  }
-#undef NQ_LAUNCH_LOOKUP
-  return hipGetLastError();
-}
-
-// ---- locality order of a query batch -----------------------------------------------------
-// Queries that hit the same genomes read the same table and bucket lines.  When they run on
-// the same XCD at the same time those lines are fetched from HBM once (measured: 13 % off the
-// launch when the 4 queries of a family sit 8 blocks apart).  So a batch is ordered by its
-// best probable hit: probe_kernel counts the first kProbeSlots slots only and takes the genome
-// with the most hits as the query's key, order_kernel sorts (key, query), and gather_kernel
-// maps sorted neighbours to one XCD.  Only the order of the work changes, never a result.
-constexpr uint32_t kOrderGroup = 8;
-constexpr uint32_t kProbeSlots = 16;
-constexpr uint32_t kOrderMax = 4096;   // queries per launch (12 index bits next to a 20-bit key)
-
-// Counters per block of kProbeBlock consecutive genomes (a key only has to bring the queries of one
-// family together): a few KB of LDS instead of the gather kernel's whole tile, so many probes share
-// a CU and hide each other's three dependent memory round trips (sketch -> entry -> ids).
-constexpr uint32_t kProbeBlock = 64;
+// Hit lists (launch_gather: one plane, one segment, nothing to add to): the query's hits are picked while a tile's
+// counters are in LDS -- count >= min_score, src/niqki_index.cpp:662-666 -- into one LDS list for all tiles, and
+// ordered after the last tile, by rank: the keys count << 32 | gid are distinct, so an entry's place under
+// greater<pair<count, gid>> (:685) is the number of entries with a larger key.  The key holds the global gid (the
+// genomes of striped tiles interleave).  A query with a few dozen hits writes no 2N-byte counter row and reads
+// none again.  A query with more than hl_cap hits (min_score 0: every genome) leaves through its counter row as
+// before, and launch_hitlist_emit orders it.  Its total may pass hl_cap only at a later tile: that tile first
+// writes the row's other tiles -- zeros, then the hits of the tiles before, which the list holds in full -- and it
+// and every tile after it write their counters there as the counter-row form does (below).
+// list: hl_cap keys in LDS; lds_n[0]: its length so far, the hits of the tiles before, hl_total of them.  Returns the
+// list's length with this tile; where that is above hl_cap the caller writes the tile's counters to the row.
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void probe_kernel(IndexView v, const int32_t *sketches, uint32_t *keys) {
-  extern __shared__ __align__(16) uint32_t cnt[];
-  __shared__ uint32_t s_best;
-  const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const int32_t *sk = sketches + (uint64_t)q * v.q_stride + v.q_off;
-  const uint32_t n_probe = v.f_local < kProbeSlots ? v.f_local : kProbeSlots;
-  const uint32_t n_blocks = (v.n_genomes + kProbeBlock - 1) / kProbeBlock;
-  if (tid == 0) s_best = 0;
-  for (uint32_t i = tid; i < n_blocks; i += BLOCK) cnt[i] = 0;
-  __syncthreads();
-  for (uint32_t w = wave; w < n_probe * v.n_tiles; w += BLOCK / 64) {
-    const uint32_t s = w / v.n_tiles, t = w % v.n_tiles;
-    const int32_t fp = sk[s];
-    if (fp < 0 || (uint32_t)fp >= v.d.R) continue;  // wave uniform
-    const Entry e = v.entries[((uint64_t)s * v.d.R + (uint32_t)fp) * v.n_tiles + t];
-    const uint16_t *b = v.gids + v.tile_base[t] + ((uint64_t)e.start << v.align_log2);
-    for (uint32_t o = lane; o < e.len; o += 64) atomicAdd(&cnt[tile_gid(v, t, b[o]) / kProbeBlock], 1u);
+__device__ __forceinline__ uint32_t pick_hits(const IndexView &v, const CandOut &co, uint32_t q, uint32_t t, uint32_t n_t, const uint32_t *cnt,
+                                              uint32_t *lds_n, unsigned long long *list, uint16_t *plane, uint64_t stride, uint32_t hl_total) {
+  const uint32_t tid = threadIdx.x, n_words = (n_t + 1) / 2;
+  const uint32_t cap = co.hl_cap, ms = co.hl_min;
+  // (hits are few: an LDS atomic each; ballot ranking was slower.  The counters are read eight at a time -- the
+  // workgroup's clock showed 2.7 of a read's 14.6 us in this scan when it took them word by word -- and a quad
+  // whose OR-ed halves stay under the threshold holds no hit)
+  auto pick = [&](uint32_t c, uint32_t i) {
+    const uint32_t lo = c & 0xFFFFu, hi = c >> 16;
+    if (lo >= ms) {
+      const uint32_t at = atomicAdd(&lds_n[0], 1u);
+      if (at < cap) list[at] = (unsigned long long)lo << 32 | (v.g_base + tile_gid(v, t, 2 * i));
+    }
+    if (2 * i + 1 < n_t && hi >= ms) {
+      const uint32_t at = atomicAdd(&lds_n[0], 1u);
+      if (at < cap) list[at] = (unsigned long long)hi << 32 | (v.g_base + tile_gid(v, t, 2 * i + 1));
+    }
+  };
+  const uint32_t n_quads = n_words / 4;
+  const uint4 *c4 = (const uint4 *)cnt;   // (the dynamic LDS block is 16-byte aligned)
+  for (uint32_t k = tid; k < n_quads; k += BLOCK) {
+    const uint4 c = c4[k];
+    const uint32_t o = c.x | c.y | c.z | c.w;
+    if ((o & 0xFFFFu) < ms && (o >> 16) < ms) continue;
+    pick(c.x, 4 * k); pick(c.y, 4 * k + 1); pick(c.z, 4 * k + 2); pick(c.w, 4 * k + 3);
   }
-  __syncthreads();
-  uint32_t best = 0;  // count << 20 | block
-  for (uint32_t i = tid; i < n_blocks; i += BLOCK) {
-    const uint32_t c = cnt[i] < 4095u ? cnt[i] : 4095u;
-    const uint32_t a = (c << 20) | i;
-    best = best > a ? best : a;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t y = __shfl_xor(best, o, 64);
-    best = best > y ? best : y;
-  }
-  if (lane == 0) atomicMax(&s_best, best);
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t c = s_best >> 20;
-    const uint32_t key = c >= 2 ? (s_best & 0xFFFFFu) : 0xFFFFFu;  // unrelated queries: one group at the end
-    keys[q] = (key << 12) | q;
-  }
-}
-
-// keys[0..nq) -> order[0..nq): ascending (key, query index); one workgroup, bitonic in LDS
-__global__ __launch_bounds__(1024) void order_kernel(const uint32_t *keys, uint32_t nq, uint32_t *order) {
-  __shared__ uint32_t a[kOrderMax];
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t i = tid; i < kOrderMax; i += 1024) a[i] = i < nq ? keys[i] : 0xFFFFFFFFu;
-  __syncthreads();
-  for (uint32_t k = 2; k <= kOrderMax; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t i = tid; i < kOrderMax; i += 1024) {
-        const uint32_t l = i ^ j;
-        if (l > i) {
-          const uint32_t x = a[i], y = a[l];
-          const bool up = (i & k) == 0;
-          if ((x > y) == up) { a[i] = y; a[l] = x; }
-        }
-      }
-      __syncthreads();
+  for (uint32_t i = 4 * n_quads + tid; i < n_words; i += BLOCK) pick(cnt[i], i);
+  lds_barrier();
+  const uint32_t total = lds_n[0];   // (hl_total: the same in every thread)
+  if (total > cap && hl_total <= cap && t > 0) {
+    uint16_t *row = plane + (uint64_t)q * stride + v.g_base;
+    if (((uintptr_t)row & 3u) == 0) {
+      for (uint32_t i = tid; i < v.n_genomes / 2; i += BLOCK) ((uint32_t *)row)[i] = 0u;
+      if ((v.n_genomes & 1u) && tid == 0) row[v.n_genomes - 1] = 0;
+    } else {
+      for (uint32_t i = tid; i < v.n_genomes; i += BLOCK) row[i] = 0;
+    }
+    __syncthreads();   // (a barrier that waits for the zeros: the counts below are stored over them)
+    for (uint32_t i = tid; i < hl_total; i += BLOCK) {
+      const unsigned long long e = list[i];
+      row[(uint32_t)e - v.g_base] = (uint16_t)(e >> 32);
     }
   }
-  for (uint32_t i = tid; i < nq; i += 1024) order[i] = a[i] & 0xFFFu;
+  if (t + 1 == v.n_tiles) {
+    if (total <= cap) {
+      // (entries are read two at a time; the list was zeroed before the first tile, and key 0 -- the places
+      // behind the last entry -- is larger than no key: a real key 0 is count 0 of genome 0, the smallest there is)
+      const uint32_t t2 = (total + 1u) & ~1u;
+      unsigned long long *out = co.hl + (uint64_t)q * cap;
+      for (uint32_t i = tid; i < total; i += BLOCK) {
+        const unsigned long long key = list[i];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < t2; j += 2) {   // (all lanes read the same two entries: a broadcast)
+          const ulonglong2 o = *(const ulonglong2 *)(list + j);
+          rank += (o.x > key) + (o.y > key);
+        }
+        out[rank] = key;
+      }
+    }
+    if (tid == 0) co.hl_n[q] = total;
+  }
+  return total;
 }
 
 #ifdef NQ_GATHER_CLOCK   // measurement builds only (tools/gather_clock.py): per-workgroup phase times
@@ -779,7 +496,7 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
   extern __shared__ __align__(16) uint32_t cnt[];
   uint32_t q = blockIdx.x;
   if (order) {
-    // Locality order (see order_queries below): block b runs on XCD b % 8 as the (b / 8)-th
+    // Locality order (nq_order.hip): block b runs on XCD b % 8 as the (b / 8)-th
     // workgroup of that XCD; kOrderGroup consecutive entries of the sorted order share an XCD
     // and sit next to each other in its dispatch queue.
     const uint32_t x = blockIdx.x % kXcds, k = blockIdx.x / kXcds;
@@ -797,8 +514,8 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
     g_gclk[(uint64_t)blockIdx.x * 64 + 15] = ((uint64_t)xcc << 32) | hw;
   }
 #endif
-  // (PAD: the padded walk addresses the counters from LDS address 0 -- gather_shape checks that this
-  // instantiation has no static LDS in front of its dynamic block and otherwise launches the form without PAD)
+  // (PAD: the padded walk addresses the counters from LDS address 0 -- gather_pad_at_zero checks that this
+  // instantiation has no static LDS in front of its dynamic block; gather_shape otherwise names the form without PAD)
   const int32_t *sk = NT < 0 ? nullptr : sketches + (uint64_t)q * v.q_stride + v.q_off;
   Item *queue = (Item *)(cnt + (v.tile + 1) / 2 + (PAD ? kPadWords : 0u));  // behind the counters: kQueue items per wave
   const bool want_cand = co.cand != nullptr;
@@ -942,74 +659,10 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
       continue;
     }
     if (co.hl) {
-      // Hit lists (launch_gather: one plane, one segment, nothing to add to): the query's hits are picked while a tile's
-      // counters are in LDS -- count >= min_score, src/niqki_index.cpp:662-666 -- into one LDS list for all tiles, and
-      // ordered after the last tile, by rank: the keys count << 32 | gid are distinct, so an entry's place under
-      // greater<pair<count, gid>> (:685) is the number of entries with a larger key.  The key holds the global gid (the
-      // genomes of striped tiles interleave).  A query with a few dozen hits writes no 2N-byte counter row and reads
-      // none again.  A query with more than hl_cap hits (min_score 0: every genome) leaves through its counter row as
-      // before, and launch_hitlist_emit orders it.  Its total may pass hl_cap only at a later tile: that tile first
-      // writes the row's other tiles -- zeros, then the hits of the tiles before, which the list holds in full -- and it
-      // and every tile after it write their counters there as the counter-row form does (below).
+      // hit lists (pick_hits above); a query over hl_cap goes on to the counter-row forms below
       unsigned long long *list = (unsigned long long *)(queue + (BLOCK / 64) * kQueue);   // hl_cap keys
-      const uint32_t cap = co.hl_cap, ms = co.hl_min;
-      // (hits are few: an LDS atomic each; ballot ranking was slower.  The counters are read eight at a time -- the
-      // workgroup's clock showed 2.7 of a read's 14.6 us in this scan when it took them word by word -- and a quad
-      // whose OR-ed halves stay under the threshold holds no hit)
-      auto pick = [&](uint32_t c, uint32_t i) {
-        const uint32_t lo = c & 0xFFFFu, hi = c >> 16;
-        if (lo >= ms) {
-          const uint32_t at = atomicAdd(&lds_n[0], 1u);
-          if (at < cap) list[at] = (unsigned long long)lo << 32 | (v.g_base + tile_gid(v, t, 2 * i));
-        }
-        if (2 * i + 1 < n_t && hi >= ms) {
-          const uint32_t at = atomicAdd(&lds_n[0], 1u);
-          if (at < cap) list[at] = (unsigned long long)hi << 32 | (v.g_base + tile_gid(v, t, 2 * i + 1));
-        }
-      };
-      const uint32_t n_quads = n_words / 4;
-      const uint4 *c4 = (const uint4 *)cnt;   // (the dynamic LDS block is 16-byte aligned)
-      for (uint32_t k = tid; k < n_quads; k += BLOCK) {
-        const uint4 c = c4[k];
-        const uint32_t o = c.x | c.y | c.z | c.w;
-        if ((o & 0xFFFFu) < ms && (o >> 16) < ms) continue;
-        pick(c.x, 4 * k); pick(c.y, 4 * k + 1); pick(c.z, 4 * k + 2); pick(c.w, 4 * k + 3);
-      }
-      for (uint32_t i = 4 * n_quads + tid; i < n_words; i += BLOCK) pick(cnt[i], i);
-      lds_barrier();
-      const uint32_t total = lds_n[0];   // (hl_total: the same in every thread)
-      if (total > cap && hl_total <= cap && t > 0) {
-        uint16_t *row = plane + (uint64_t)q * stride + v.g_base;
-        if (((uintptr_t)row & 3u) == 0) {
-          for (uint32_t i = tid; i < v.n_genomes / 2; i += BLOCK) ((uint32_t *)row)[i] = 0u;
-          if ((v.n_genomes & 1u) && tid == 0) row[v.n_genomes - 1] = 0;
-        } else {
-          for (uint32_t i = tid; i < v.n_genomes; i += BLOCK) row[i] = 0;
-        }
-        __syncthreads();   // (a barrier that waits for the zeros: the counts below are stored over them)
-        for (uint32_t i = tid; i < hl_total; i += BLOCK) {
-          const unsigned long long e = list[i];
-          row[(uint32_t)e - v.g_base] = (uint16_t)(e >> 32);
-        }
-      }
-      if (t + 1 == v.n_tiles) {
-        if (total <= cap) {
-          // (entries are read two at a time; the list was zeroed before the first tile, and key 0 -- the places
-          // behind the last entry -- is larger than no key: a real key 0 is count 0 of genome 0, the smallest there is)
-          const uint32_t t2 = (total + 1u) & ~1u;
-          unsigned long long *out = co.hl + (uint64_t)q * cap;
-          for (uint32_t i = tid; i < total; i += BLOCK) {
-            const unsigned long long key = list[i];
-            uint32_t rank = 0;
-            for (uint32_t j = 0; j < t2; j += 2) {   // (all lanes read the same two entries: a broadcast)
-              const ulonglong2 o = *(const ulonglong2 *)(list + j);
-              rank += (o.x > key) + (o.y > key);
-            }
-            out[rank] = key;
-          }
-        }
-        if (tid == 0) co.hl_n[q] = total;
-      }
+      const uint32_t cap = co.hl_cap;
+      const uint32_t total = pick_hits<BLOCK>(v, co, q, t, n_t, cnt, lds_n, list, plane, stride, hl_total);
       hl_total = total;
       if (total <= cap) {
         lds_barrier();   // (everyone has read lds_n before the next walk takes its words back)
@@ -1084,51 +737,58 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(IndexView v, const int32_
   }
 }
 
-hipError_t launch_order(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *keys,
-                        uint32_t *order, hipStream_t stream) {
-  if (nq == 0 || nq > kOrderMax || v.n_genomes >= (1u << 20) - 1) return hipErrorInvalidValue;
-  const size_t lds = (size_t)((v.n_genomes + kProbeBlock - 1) / kProbeBlock) * 4;   // <= 64 KB (n_genomes < 2^20)
-  hipError_t e = hipFuncSetAttribute((const void *)probe_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(probe_kernel<256>, dim3(nq), dim3(256), lds, stream, v, sketches, keys);
-  hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, stream, keys, nq, order);
-  return hipGetLastError();
-}
-
-bool gather_variant_valid(int variant) {
-  return variant >= 0 && variant <= 5;
-}
-
-GatherShape gather_shape(const IndexView &v, int variant, bool pre) {
-  // The padded walk (PAD = true) takes a counter's LDS address from the genome id alone: the kernel's dynamic
-  // LDS must start at LDS address 0, i.e. the instantiation must have no static LDS in front of it.  Asked of
-  // the runtime once per process; if a toolchain ever puts something there, the form with explicit lengths
-  // (any LDS base, any index layout) is launched instead.
+bool gather_pad_at_zero() {
   static const bool pad_at_zero = [] {
     hipFuncAttributes fa{};
     return hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 32, -1, true>) == hipSuccess && fa.sharedSizeBytes == 0 &&
            hipFuncGetAttributes(&fa, (const void *)gather_kernel<1024, 16, 2, true>) == hipSuccess && fa.sharedSizeBytes == 0;
   }();
-  const bool padded = v.padded && pad_at_zero;
-  // look-ups from the pre-pass: one form for any tile count; else the stash forms for 2..4 tiles
-  const int nt = pre ? -1 : (v.n_tiles >= 2 && v.n_tiles <= 4 ? (int)v.n_tiles : 1);
-  switch (variant) {
-    case 1: return GatherShape{1024, 8, nt, padded};
-    case 2: return GatherShape{1024, 32, nt, padded};
-    case 3: return GatherShape{512, 16, nt, false};
-    case 4: return GatherShape{256, 16, nt, false};
-    case 5: return GatherShape{128, 16, nt, false};
-    default: break;
-  }
-  // small tiles (short-read indexes): counters of <= 24 KB leave room for several
-  // workgroups per CU, and 4 waves per query then beat 16 (tools/bench_reads.py)
-  if (v.tile <= 12288) return GatherShape{256, 16, nt, false};
-  if (padded && pre) return GatherShape{1024, 32, nt, true};   // without look-ups of its own the walk gains from 32 lines per round trip (8.42 against 8.6 ms)
-  return GatherShape{1024, 16, nt, padded};   // padded index: mask-free bucket walk
+  return pad_at_zero;
 }
 
+namespace {
+struct GatherArgs {
+  const IndexView &v;
+  const int32_t *sketches;
+  uint32_t nq;
+  uint16_t *counts, *counts2;
+  uint64_t stride;
+  Entry *stash;
+  const uint32_t *order;
+  size_t lds;
+  hipStream_t stream;
+  const CandOut &co;
+};
+template <int B, int U, int NT, bool PAD>
+hipError_t launch_one(const GatherArgs &a) {
+  static_assert(gather_shape_exists(GatherShape{B, U, NT, PAD}), "nq_gather_plan.h lists the instantiations");
+  auto k = gather_kernel<B, U, NT, PAD>;
+  const hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
+  if (e != hipSuccess) return e;
+  // with a locality order the grid is padded to whole groups on every XCD
+  const uint32_t per_round = kXcds * kOrderGroup;
+  const dim3 grid(a.order ? (a.nq + per_round - 1) / per_round * per_round : a.nq);
+  hipLaunchKernelGGL(k, grid, dim3(B), a.lds, a.stream, a.v, a.sketches, a.counts, a.counts2, a.stride, a.stash, a.order, a.nq, a.co);
+  return hipGetLastError();
+}
+template <int B, int U, bool PAD>
+hipError_t launch_by_tiles(int nt, const GatherArgs &a) {
+  switch (nt) {
+    case -1: return launch_one<B, U, -1, PAD>(a);
+    case 2: return launch_one<B, U, 2, PAD>(a);
+    case 3: return launch_one<B, U, 3, PAD>(a);
+    case 4: return launch_one<B, U, 4, PAD>(a);
+    default: return launch_one<B, U, 1, PAD>(a);
+  }
+}
+template <int U>
+hipError_t launch_wide(const GatherShape &sh, const GatherArgs &a) {   // 1024 threads: with and without the padded walk
+  return sh.pad ? launch_by_tiles<1024, U, true>(sh.nt, a) : launch_by_tiles<1024, U, false>(sh.nt, a);
+}
+}  // namespace
+
 hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t nq, uint16_t *counts, uint16_t *counts2,
-                         uint64_t stride, Entry *stash, const uint32_t *order, int variant, bool pre,
+                         uint64_t stride, Entry *stash, const uint32_t *order, const GatherShape &sh, size_t lds_bytes,
                          hipStream_t stream, const CandOut &co) {
   if (nq == 0 || v.n_tiles == 0) return hipSuccess;
   if (v.f_local > kPassSlots && (!counts2 || v.accumulate)) return hipErrorInvalidValue;
@@ -1138,44 +798,12 @@ hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t n
   if (co.hl && (co.cand || !co.hl_n || !counts || !co.hl_cap || (co.hl_cap & 3u) || co.hl_cap > kHitListMaxCap || v.accumulate ||
                 v.f_local > kPassSlots || hit_list_lds(v.tile, co.hl_cap) > kGatherMaxLds))
     return hipErrorInvalidValue;
-#define NQ_GATHER_LDS(B) ((size_t)((v.tile + 1) / 2 + (v.padded ? kPadWords : 0u)) * 4 + (size_t)(B / 64) * kQueue * sizeof(Item) + (size_t)co.hl_cap * (co.hl ? 8 : 0))
-  // with a locality order the grid is padded to whole groups on every XCD
-  const uint32_t per_round = kXcds * kOrderGroup;
-  dim3 grid(order ? (nq + per_round - 1) / per_round * per_round : nq);
-  hipError_t e;
-#define NQ_LAUNCH_GATHER(B, U, NT, ...)                                                          \
-  do {                                                                                           \
-    auto k = gather_kernel<B, U, NT, ##__VA_ARGS__>;                                             \
-    const size_t lds = NQ_GATHER_LDS(B);                                                         \
-    e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) return e;                                                               \
-    hipLaunchKernelGGL(k, grid, dim3(B), lds, stream, v, sketches, counts, counts2, stride, stash, order, nq, co); \
-  } while (0)
-  const GatherShape sh = gather_shape(v, variant, pre);
-#define NQ_BY_TILES(B, U, ...)                                                                   \
-  do {                                                                                           \
-    if (sh.nt < 0) NQ_LAUNCH_GATHER(B, U, -1, ##__VA_ARGS__);                                     \
-    else if (sh.nt == 2) NQ_LAUNCH_GATHER(B, U, 2, ##__VA_ARGS__);                               \
-    else if (sh.nt == 3) NQ_LAUNCH_GATHER(B, U, 3, ##__VA_ARGS__);                               \
-    else if (sh.nt == 4) NQ_LAUNCH_GATHER(B, U, 4, ##__VA_ARGS__);                               \
-    else NQ_LAUNCH_GATHER(B, U, 1, ##__VA_ARGS__);                                               \
-  } while (0)
-#define NQ_BY_PAD(B, U)                                                                          \
-  do {                                                                                           \
-    if (sh.pad) NQ_BY_TILES(B, U, true); else NQ_BY_TILES(B, U);                                 \
-  } while (0)
-  if (sh.block == 1024 && sh.unroll == 8) NQ_BY_PAD(1024, 8);
-  else if (sh.block == 1024 && sh.unroll == 16) NQ_BY_PAD(1024, 16);
-  else if (sh.block == 1024 && sh.unroll == 32) NQ_BY_PAD(1024, 32);
-  else if (sh.block == 512 && sh.unroll == 16 && !sh.pad) NQ_BY_TILES(512, 16);
-  else if (sh.block == 256 && sh.unroll == 16 && !sh.pad) NQ_BY_TILES(256, 16);
-  else if (sh.block == 128 && sh.unroll == 16 && !sh.pad) NQ_BY_TILES(128, 16);
-  else return hipErrorInvalidValue;   // (gather_shape names an instantiation this file does not have)
-#undef NQ_BY_PAD
-#undef NQ_BY_TILES
-#undef NQ_GATHER_LDS
-#undef NQ_LAUNCH_GATHER
-  return hipGetLastError();
+  if (!gather_shape_exists(sh)) return hipErrorInvalidValue;
+  const GatherArgs a{v, sketches, nq, counts, counts2, stride, stash, order, lds_bytes, stream, co};
+  if (sh.block == 1024) return sh.unroll == 8 ? launch_wide<8>(sh, a) : sh.unroll == 16 ? launch_wide<16>(sh, a) : launch_wide<32>(sh, a);
+  if (sh.block == 512) return launch_by_tiles<512, 16, false>(sh.nt, a);
+  if (sh.block == 256) return launch_by_tiles<256, 16, false>(sh.nt, a);
+  return launch_by_tiles<128, 16, false>(sh.nt, a);
 }
 
 // Sum of touched bucket lengths per query (T of the roofline formula).

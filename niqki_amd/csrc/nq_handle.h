@@ -131,7 +131,7 @@ struct niqki_index {
 
   int gather_variant = 0;
   uint32_t last_densify_form = 0;   // stat "last_densify_form": nq::DensifyForm of the last sketch / densify call
-  uint32_t last_form = 0;        // stat "last_gather_form": 1 = look-up pre-pass, 2 = its streamed-rows form, 4 = locality order
+  uint32_t last_form = 0;        // stat "last_gather_form": 1 = look-up pre-pass, 2 = packed table prepared (streamed rows from 512 queries per launch), 4 = locality order
   uint32_t last_kernel = 0;      // stat "last_gather_kernel": nq::gather_shape_code of the last gather launch
   uint64_t record_len_hint = 0;  // avg bytes per sketch for device-side batches (0 = read it back)
   uint32_t query_batch = 1024;

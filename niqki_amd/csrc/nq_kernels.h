@@ -2,6 +2,7 @@
 // gfx950 kernels.  All pointers are device pointers unless noted.
 #pragma once
 #include "nq_common.h"
+#include "nq_gather_plan.h"
 #include "nq_retain_blocks.h"
 #include "nq_sketch_plan.h"
 #include "nq_unite_blocks.h"
@@ -56,6 +57,7 @@ struct Entry {
   uint32_t start;  // in units of (1 << align_log2) ids
   uint32_t len;
 };
+static_assert(sizeof(Entry) == kEntryBytes, "the stash bytes of a GatherPlan (nq_gather_plan.h) count these");
 struct IndexView {
   Derived d;
   uint32_t n_genomes;   // genomes of this segment
@@ -136,8 +138,7 @@ hipError_t launch_build_sizes(const IndexView &v, uint32_t *slot_units, uint64_t
 hipError_t launch_build_fill(const IndexView &v, Entry *entries, uint16_t *gids, hipStream_t stream);
 // padded layout: the padding pattern over the whole id array (n_ids a multiple of 64), before the fill
 hipError_t launch_pad_fill(uint16_t *gids, uint64_t n_ids, uint32_t tile, hipStream_t stream);
-constexpr uint32_t kPadWords = 64;        // dummy counter words of a padded tile
-constexpr uint32_t kPadMaxTile = 65408;   // tile + 2 * 63 must fit 16 bits
+// (kPadWords, kPadMaxTile: nq_gather_plan.h)
 // dump stream (src/niqki_index.cpp:42-55) of a whole-range index.
 // layout: slot_word[s] (F+1 entries) = word position of bucket (s, 0) in the stream
 // (header excluded); export: the words of slots [s0, s1) into `out` (word 0 = first
@@ -153,16 +154,21 @@ hipError_t launch_import(const Derived &d, const uint32_t *words, const uint64_t
                          uint16_t *store, uint64_t cap, uint32_t n_genomes, uint32_t col_base, uint32_t *bad,
                          uint32_t s0, uint32_t n_slots, hipStream_t stream);
 
-// ---- query: counters (nq_gather.hip) ------------------------------------------
+// ---- query: counters (nq_gather.hip, nq_lookup.hip, nq_order.hip) ---------------
+// Which of these kernels a launch takes, its scratch and its LDS: nq_gather_plan.h.  The launchers here carry a plan out.
+// what the plan reads of a view
+inline GatherFacts gather_facts(const IndexView &v) {
+  return GatherFacts{v.d.R, v.f_local, v.n_tiles, v.tile, v.align_log2, v.padded != 0, v.n_genomes};
+}
 // gather-histogram: counts[q*stride + g] for all genomes (u16), one workgroup
 // per (query, tile).
-// stash: nq x (n_tiles-1) x f_local Entry scratch (unused for n_tiles == 1)
+// stash: nq x (n_tiles-1) x f_local Entry scratch (unused for n_tiles == 1); shape.nt < 0: the packed words of
+//        launch_lookup for ALL tiles (sketches are then unused)
 // order: nullptr, or the locality order of the batch from launch_order (nq <= 4096)
-// pre: `stash` holds the packed words of launch_lookup for ALL tiles (sketches are then unused)
+// shape, lds_bytes: GatherPlan::shape and ::lds_bytes
 // counts2: second counter plane, needed (and used) when the view has more than kPassSlots slots
 // (S = 16 on a whole-range handle): a count can then reach 2^16, so the slots are walked in two
 // passes of <= 2^15 and plane p holds pass p's counters; the true count is the 32-bit sum.
-constexpr uint32_t kPassSlots = 32768;
 // Candidate output of a gather launch (multi-GPU path): while a query's counters leave LDS, the genomes
 // with a count >= thr are appended to cand[q*cap ..] (unordered, at most cap kept) and n[q] grows by how
 // many qualified.  The caller presets n to 0 and cand to -1; launches over further segments of the same
@@ -191,45 +197,23 @@ struct CandOut {
   uint32_t *hl_over = nullptr;   // nq + 1 words: [0] is zeroed by the launch (launch_hitlist_scan lists the overflowing queries there)
   uint32_t hl_cap = 0, hl_min = 0;
 };
-// the 256-thread launch shape's largest tile (counters + queues + list within a CU's LDS several times over): an index
-// of at most this many genomes takes the hit-list form as one tile
-constexpr uint32_t kHitListMaxTile = 12288;
-constexpr uint32_t kHitListMaxCap = 2048;
-// LDS of a gather launch with hit lists at its largest workgroup (1024 threads: the counters of a padded tile, 16 wave
-// queues of 256 8-byte items, the list of cap 8-byte keys); the form takes tiles where that fits a workgroup's 160 KB
-constexpr size_t hit_list_lds(uint32_t tile, uint32_t cap) {
-  return ((size_t)(tile + 1) / 2 + kPadWords) * 4 + (size_t)16 * 256 * 8 + (size_t)cap * 8;
-}
-constexpr size_t kGatherMaxLds = 163840;
 hipError_t launch_gather(const IndexView &v, const int32_t *sketches, uint32_t nq,
                          uint16_t *counts, uint16_t *counts2, uint64_t stride, Entry *stash, const uint32_t *order,
-                         int variant, bool pre, hipStream_t stream, const CandOut &co = CandOut());
+                         const GatherShape &shape, size_t lds_bytes, hipStream_t stream, const CandOut &co = CandOut());
+// true: no gather_kernel instantiation with the padded walk has static LDS in front of its dynamic block (asked of the
+// runtime once per process): an input of the plan
+bool gather_pad_at_zero();
 // out[i] = a[i] + b[i]: as u16 with wrap-around (the reference's uint16 matrix counters, src/niqki_index.cpp:572)
 // or as u32 (the two planes of a launch_gather above; the kernels are in nq_hits.hip)
 hipError_t launch_plane_add16(uint16_t *a, const uint16_t *b, uint64_t n, hipStream_t stream);
 hipError_t launch_plane_sum32(const uint16_t *a, const uint16_t *b, uint32_t *out, uint64_t n, hipStream_t stream);
-// Slot-major look-up pre-pass for the queries of a launch (nq_gather.hip): fills
-// pre[q][tile][slot] (lookup_pre_bytes of scratch) from the table streamed once.
-bool launch_lookup_usable(const IndexView &v);
-// The pre-pass reads a packed copy of the table (4 bytes per entry) where its row-staging kernel applies
-bool lookup_wants_packed(const IndexView &v);
+// Slot-major look-up pre-pass for the queries of a launch (nq_lookup.hip): fills pre[q][tile][slot] (lookup_pre_bytes
+// of scratch) with the kernel that `form` names (lookup_form of the plan and nq); its streamed-rows kernel reads v.ptab,
+// the packed copy of the table that launch_pack_entries makes.
 hipError_t launch_pack_entries(const IndexView &v, uint32_t *ptab, hipStream_t stream);
-size_t lookup_pre_bytes(const IndexView &v, uint32_t nq);
-hipError_t launch_lookup(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *pre, hipStream_t stream);
-// launch shapes selectable through the "gather_variant" option (0 = choose)
-bool gather_variant_valid(int variant);
-// The gather_kernel<BLOCK, UNROLL, NT, PAD> instantiation launch_gather launches for (view, variant, pre): the one place
-// where the shape is chosen.  pad is the form actually launched (the padded walk needs its dynamic LDS at address 0).
-struct GatherShape {
-  int block, unroll, nt;
-  bool pad;
-};
-GatherShape gather_shape(const IndexView &v, int variant, bool pre);
-// stat "last_gather_kernel": BLOCK | UNROLL << 12 | (NT + 1) << 20 | PAD << 24
-constexpr uint32_t gather_shape_code(const GatherShape &s) {
-  return (uint32_t)s.block | (uint32_t)s.unroll << 12 | (uint32_t)(s.nt + 1) << 20 | (s.pad ? 1u : 0u) << 24;
-}
-// keys / order: nq words of scratch each
+hipError_t launch_lookup(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *pre, const LookupForm &form,
+                         hipStream_t stream);
+// Locality order of a launch (nq_order.hip).  keys / order: nq words of scratch each
 hipError_t launch_order(const IndexView &v, const int32_t *sketches, uint32_t nq, uint32_t *keys,
                         uint32_t *order, hipStream_t stream);
 hipError_t launch_gathered(const IndexView &v, const int32_t *sketches, uint32_t nq,
