@@ -537,6 +537,54 @@ int niqki_dereplicate_from(niqki_index *ix, uint32_t first, uint32_t threshold, 
 int niqki_linkage(niqki_index *ix, uint32_t floor, uint32_t *merge_into, uint32_t *merge_count,
                   uint32_t *edge_lo, uint32_t *edge_hi, uint32_t *edge_count, uint32_t *n_roots, int mem);
 
+/* Label audit: every indexed genome's nearest neighbours read against the labelling of niqki_set_labels -- the
+ * leave-one-out k-nearest-neighbour check of a curated collection, in ONE self-join.  A label file is trusted by
+ * niqki_query_collapsed, niqki_unite and, as the leaves of a taxonomy, niqki_query_lca; this call says which genomes
+ * the index itself would have labelled otherwise, before the file is acted on.
+ * Definition.  label[g] is the labelling of niqki_set_labels.  t = max(threshold, 1).  H(g) is exactly what
+ * niqki_neighbors_range(ix, g, g + 1, ...) returns at min_score = t and top_k = 0: ordered by count descending, then
+ * gid descending.  H'(g) is H(g) without the entry whose gid is g; that entry is absent when g's own valid cells are
+ * fewer than t, and it is not the first one when an exact duplicate with a larger id ties it.  For every g in
+ * [0, n_genomes):
+ *   own_count[g], own_gid[g]      the first entry of H'(g) whose label equals label[g]; none: 0, 0xFFFFFFFF.
+ *   other_count[g], other_gid[g]  the first entry of H'(g) whose label differs from label[g]; none: 0, 0xFFFFFFFF.
+ *   vote_gid[g], vote_n[g]        V is the first min(k, |H'(g)|) entries of H'(g).  The winning label is the one with
+ *                                 the most entries in V, among equal numbers the one whose first entry in V comes
+ *                                 first; vote_gid is that first entry's gid, vote_n the label's number of entries in
+ *                                 V.  V empty: 0xFFFFFFFF, 0.  k = 1: simply the nearest neighbour.
+ *   verdict[g]                    set by the two counts alone:
+ *                                 NIQKI_AUDIT_ALONE      both counts 0
+ *                                 NIQKI_AUDIT_AGREES     own_count > other_count
+ *                                 NIQKI_AUDIT_TIED       own_count == other_count > 0
+ *                                 NIQKI_AUDIT_MISPLACED  other_count > own_count > 0
+ *                                 NIQKI_AUDIT_STRAY      other_count > 0 == own_count
+ * Each of the seven arrays may be NULL.  k must be in 1..63, else NIQKI_E_INVALID (the first k + 1 entries of a list
+ * are one wavefront's load).  Without a labelling the call returns NIQKI_E_STATE and niqki_last_error says to call
+ * niqki_set_labels (again); no genomes: NIQKI_OK, also without a labelling.  The result is a function of the index, the
+ * labels, t and k only: it does not depend on batch sizes, options, splits, top_k (ignored here) or the order in which
+ * the device works.  The handle's min_score and top_k are unchanged when the call returns, also when it fails.
+ * Handles as niqki_cluster: whole-range single-GPU handles, resident or paged, any tile count, hit lists or counter
+ * rows, with or without a delta segment; NIQKI_E_STATE on a slot-range shard.  Groups have no audit.  mem as in
+ * niqki_cluster: with NIQKI_MEM_DEVICE the arrays are device arrays of n_genomes words, written in place in stream
+ * order; host results go through one device workspace of 7 x n_genomes words and cross once, at the end.  The call
+ * synchronises.
+ * One self-join: the batches, the hit buffers, their budget (option "cluster_ws_mib") and the halving rule are
+ * niqki_cluster's.  Per batch the audit kernel takes a list per wavefront, 64 entries a step: it drops g's own entry
+ * with a ballot and a prefix count of lanes, lets the first k lanes' labels be compared by all lanes (a popcount a
+ * label) and finds the first own-label and the first foreign entry by ballots, until both are known or the list ends;
+ * the verdict is computed there and nowhere else.  Nothing is sorted, nothing spins.
+ * niqki_get_stat, the last call: "audit_splits", "audit_pairs" (hits the batches held); while profiling is on, with
+ * one synchronisation per batch: "audit_us_read", "audit_us_hits", "audit_us_scan" (microseconds;
+ * tools/bench_audit.py). */
+#define NIQKI_AUDIT_ALONE 0
+#define NIQKI_AUDIT_AGREES 1
+#define NIQKI_AUDIT_TIED 2
+#define NIQKI_AUDIT_MISPLACED 3
+#define NIQKI_AUDIT_STRAY 4
+int niqki_audit(niqki_index *ix, uint32_t threshold, uint32_t k, uint32_t *verdict, uint32_t *own_count,
+                uint32_t *own_gid, uint32_t *other_count, uint32_t *other_gid, uint32_t *vote_gid, uint32_t *vote_n,
+                int mem);
+
 /* Greedy cover of a query: the non-redundant form of niqki_query's answer.  A sample that holds several genomes, or an
  * index with many close relatives of one genome, makes niqki_query list every relative; the cover lists, pick after
  * pick, the genome that explains the most query slots nothing picked before it explains.

@@ -20,6 +20,9 @@ FILE_GZIP = 0x80
 GROUP_ID_BYTES = 128
 E_CAPACITY = 4
 TAXON_NONE = 0xFFFFFFFF
+# NIQKI_AUDIT_*: the verdicts of niqki_audit, named in the order of their values (the rule is the kernel's alone)
+AUDIT_ALONE, AUDIT_AGREES, AUDIT_TIED, AUDIT_MISPLACED, AUDIT_STRAY = 0, 1, 2, 3, 4
+AUDIT_VERDICTS = ("alone", "agrees", "tied", "misplaced", "stray")
 
 
 class NiqkiError(RuntimeError):
@@ -128,6 +131,7 @@ ABI = [
     ("niqki_dereplicate", _int, [_vp, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_dereplicate_from", _int, [_vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_linkage", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u32), _int]),
+    ("niqki_audit", _int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int]),
     ("niqki_cover", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_staged_cover", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_set_labels", _int, [_vp, _vp, _u32, _int]),
@@ -626,6 +630,16 @@ class Engine:
         n_edges = n_g - int(n.value)
         return into, cnt, (tuple(a[:n_edges].copy() for a in e3) if edges else None), int(n.value)
 
+    def audit(self, threshold, k=1):
+        """niqki_audit: every indexed genome's leave-one-out neighbours at co-occurrence count >= max(threshold, 1)
+        against the labelling of set_labels, in one self-join: (verdict, own_count, own_gid, other_count, other_gid,
+        vote_gid, vote_n), uint32 arrays of one entry per genome.  own / other: the nearest other genome under the
+        genome's label and under another one (0 and 0xFFFFFFFF: none); vote: the label most frequent among the k
+        nearest, as its first member there and its number of members; verdict: AUDIT_* (AUDIT_VERDICTS names them)."""
+        out = tuple(np.empty(self.n_genomes, dtype=np.uint32) for _ in range(7))
+        self._ck(self.L.niqki_audit(self.h, int(threshold), int(k), *[_p(a) for a in out], MEM_HOST))
+        return out
+
     def _cover(self, call, nq, capacity, totals):
         off = np.zeros(nq + 1, dtype=np.uint64)
         while True:
@@ -942,6 +956,12 @@ class Engine:
         """niqki_query_lca on device arrays (each of the last three may be None), written in stream order."""
         self._ck(self.L.niqki_query_lca(self.h, _p(sketches), nq, int(top_permille), _p(taxon), _p(best_count), _p(best_gid),
                                         _p(considered), MEM_DEVICE))
+
+    def audit_dev(self, threshold, k, verdict=None, own_count=None, own_gid=None, other_count=None, other_gid=None,
+                  vote_gid=None, vote_n=None):
+        """niqki_audit on device arrays of n_genomes 32-bit elements (each may be None), written in stream order."""
+        self._ck(self.L.niqki_audit(self.h, int(threshold), int(k), _p(verdict), _p(own_count), _p(own_gid), _p(other_count),
+                                    _p(other_gid), _p(vote_gid), _p(vote_n), MEM_DEVICE))
 
     def tally_add_dev(self, taxon, best_count, considered, n):
         """niqki_tally_add on device arrays of 32-bit elements (the last two may be None), read in stream order; bad

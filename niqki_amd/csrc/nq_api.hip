@@ -383,7 +383,7 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
                  &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
                  &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info, &ix->tally_acc, &ix->ws_tally_rows,
-                 &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
+                 &ix->ws_audit, &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -590,6 +590,12 @@ const StatKey kCallStats[] = {
     NQ_STAT("linkage_us_forest", us(ix->linkage_stats.ms[2])),
     NQ_STAT("linkage_us_finish", us(ix->linkage_stats.ms[3])),
     NQ_STAT("linkage_pairs", ix->linkage_stats.pairs),
+    // niqki_audit
+    NQ_STAT("audit_splits", ix->audit_stats.splits),
+    NQ_STAT("audit_pairs", ix->audit_stats.pairs),
+    NQ_STAT("audit_us_read", us(ix->audit_stats.ms[0])),
+    NQ_STAT("audit_us_hits", us(ix->audit_stats.ms[1])),
+    NQ_STAT("audit_us_scan", us(ix->audit_stats.ms[2])),
     // niqki_cover / niqki_staged_cover
     NQ_STAT("cover_rounds", ix->cover_stats.rounds),
     NQ_STAT("cover_picks", ix->cover_stats.picks),

@@ -4,7 +4,8 @@
 // niqki_dereplicate_from (greedy representatives in index order, the genomes below `first` given: the decide, assign
 // and finish kernels over the same hit lists) and niqki_linkage (the single-linkage forest and hierarchy: the forest
 // kernels over the same hit lists, then a host pass over fewer than N edges).  The kernels are in nq_cluster.hip, the
-// hit lists come from the query path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c, 4.6f, 4.6g.
+// hit lists come from the query path (nq_api_query.hip).  DESIGN.md 4.6b, 4.6c, 4.6f, 4.6g.  The driver of the
+// self-join (SelfJoin, self_join_batches: nq_handle.h) also serves niqki_audit (nq_api_audit.hip).
 #include "nq_handle.h"
 #include "nq_linkage_key.h"
 
@@ -21,34 +22,10 @@ bool whole_range(const niqki_index *ix) {
   return b == 0 && e == ix->d.F;
 }
 
-namespace {
-
-// One self-join with a consumer of the hit buffers: niqki_cluster (the link kernel), niqki_dereplicate (decide +
-// assign) or niqki_linkage (the forest kernels).  The batches go in index order and a halved batch finishes its first
-// half before its second (HitLists): the dereplication relies on that (a batch's earlier genomes are all decided),
-// clustering does not care.
-struct SelfJoin {
-  niqki_index *ix;
-  const char *who;
-  SelfJoinStats &stats;
-  // phases of a batch the stats time (stats.ms): store read, gather + hits, then the consumer's: 3 or 4 in all
-  const int phases;
-  // events: 0-1 the store read of a batch; of a leaf 2-3 gather + hits, then phase k = 2 .. phases - 1 between k + 1
-  // and k + 2
-  PhaseTimer ev;
-  // Enqueues the consumer's kernels on the hits (off, hit_counts, hit_gids) of genomes [t0, t0 + n) and ends each of
-  // its phases k = 2 .. phases - 1 with ev.mark(k + 2).
-  std::function<int(const unsigned long long *, const uint32_t *, const uint32_t *, uint32_t, uint32_t)> consume;
-  bool count_pairs = false;   // stats.pairs also without profiling (the total is read back per batch anyway)
-
-  SelfJoin(niqki_index *ix_, const char *who_, SelfJoinStats &stats_, int phases_)
-      : ix(ix_), who(who_), stats(stats_), phases(phases_), ev(ix_, phases_ + 2, stats_.ms) {}
-};
-
 // The events, then the batches of genomes [begin, n_run) in index order: a batch's stored rows, read once, their hits at
 // the threshold into the fixed hit buffers, then the consumer's kernels.  A split loses the gather and the count of the
 // batch, so the following batches start from the size that fitted and stay there (HitLists::shrink).
-int self_join_batches(SelfJoin &r, uint32_t n_run, uint32_t begin = 0) {
+int self_join_batches(SelfJoin &r, uint32_t n_run, uint32_t begin) {
   niqki_index *ix = r.ix;
   int rc = r.ev.create();
   if (rc) return rc;
@@ -69,6 +46,8 @@ int self_join_batches(SelfJoin &r, uint32_t n_run, uint32_t begin = 0) {
   hl.after = [&](uint32_t, uint32_t) { return r.ev.add(0, 1, 0); };
   return hl.run(timed_rows, n_run - begin, std::max<uint32_t>(ix->query_batch, 1));
 }
+
+namespace {
 
 int cluster_run(niqki_index *ix, uint32_t *labels, uint32_t *n_clusters, int mem) {
   const uint32_t N = ix->n_genomes;

@@ -3,7 +3,7 @@
 // Private to libniqki_hip.so.
 //
 // Full hit lists: what the calls that consume a query's full hit lists on the device share -- niqki_cluster,
-// niqki_dereplicate and niqki_linkage (nq_api_selfjoin.hip), niqki_query_collapsed (nq_api_collapse.hip),
+// niqki_dereplicate and niqki_linkage (nq_api_selfjoin.hip), niqki_audit (nq_api_audit.hip), niqki_query_collapsed (nq_api_collapse.hip),
 // niqki_query_lca (nq_api_lca.hip) and, without the halving, niqki_cover (nq_api_cover.hip).  Bodies: nq_api_lists.hip.
 //   CallParams    the call's min_score / top_k on the handle, the handle's own back on every exit
 //   PhaseTimer    HIP events around the phases of a call while the handle is profiling
@@ -144,7 +144,10 @@ struct niqki_index {
   // the last niqki_cluster / niqki_dereplicate call (stats "cluster_*", "derep_*").  ms, while profiling is on: store
   // read, gather + hits, then link and flatten (cluster) or decide and assign (derep)
   // niqki_linkage (stats "linkage_*"): store read, gather + hits, forest rounds, then sort + hierarchy + copies
-  nqi::SelfJoinStats cluster_stats, derep_stats, linkage_stats;
+  // niqki_audit (stats "audit_*"): store read, gather + hits, the scan of the lists
+  nqi::SelfJoinStats cluster_stats, derep_stats, linkage_stats, audit_stats;
+  // niqki_audit: the info words of a call, then a host call's seven result arrays of n_genomes words each
+  nqi::Buf ws_audit;
   nqi::CoverStats cover_stats;
   // niqki_cover: two buffers of masked rows with their query numbers, the per-row and per-query words, the pick log, a
   // batch's picks on their way to the host
@@ -366,6 +369,29 @@ int tally_rows_dev(niqki_index *ix, const uint32_t *taxon, const uint32_t *best_
 // ---- nq_api_selfjoin.hip ----
 // the handle counts whole sketches (no slot-range shard): what the self-join calls need
 bool whole_range(const niqki_index *ix);
+// One self-join with a consumer of the hit buffers: niqki_cluster (the link kernel), niqki_dereplicate (decide +
+// assign), niqki_linkage (the forest kernels) or niqki_audit (nq_api_audit.hip: the audit kernel).  The batches go in
+// index order and a halved batch finishes its first half before its second (HitLists): the dereplication relies on
+// that (a batch's earlier genomes are all decided), the others do not care.
+struct SelfJoin {
+  niqki_index *ix;
+  const char *who;
+  SelfJoinStats &stats;
+  // phases of a batch the stats time (stats.ms): store read, gather + hits, then the consumer's: 3 or 4 in all
+  const int phases;
+  // events: 0-1 the store read of a batch; of a leaf 2-3 gather + hits, then phase k = 2 .. phases - 1 between k + 1
+  // and k + 2
+  PhaseTimer ev;
+  // Enqueues the consumer's kernels on the hits (off, hit_counts, hit_gids) of genomes [t0, t0 + n) and ends each of
+  // its phases k = 2 .. phases - 1 with ev.mark(k + 2).
+  std::function<int(const unsigned long long *, const uint32_t *, const uint32_t *, uint32_t, uint32_t)> consume;
+  bool count_pairs = false;   // stats.pairs also without profiling (the total is read back per batch anyway)
+
+  SelfJoin(niqki_index *ix_, const char *who_, SelfJoinStats &stats_, int phases_)
+      : ix(ix_), who(who_), stats(stats_), phases(phases_), ev(ix_, phases_ + 2, stats_.ms) {}
+};
+// the self-join of genomes [begin, n_run) at the handle's min_score (the caller's CallParams) and top_k 0
+int self_join_batches(SelfJoin &r, uint32_t n_run, uint32_t begin = 0);
 // sketches of the handle's staged batch (niqki_stage_raw) into ix->ws_stsk, once per batch
 int staged_sketch_ws(niqki_index *ix);
 // appends n device-resident sketches (same addressing as counts_dev) to the sketch store

@@ -400,6 +400,22 @@ struct LcaArgs {
 };
 hipError_t launch_lca(const LcaArgs &a, hipStream_t stream);
 
+// ---- label audit: a genome's neighbours against its label (nq_audit.hip; the self-join: nq_api_audit.hip) ----
+// info words of a call: gids outside the index or lists longer than it (a bug: the host ends the call)
+enum : uint32_t { kAuditInfoBad = 0, kAuditInfoWords = 1 };
+constexpr uint32_t kAuditMaxK = 63;   // the first k + 1 entries of a list are one wavefront's load
+struct AuditArgs {
+  const unsigned long long *hit_off;   // nq + 1: the full ordered lists (top_k = 0) of genomes t0 .. t0 + nq
+  const uint32_t *hit_counts, *hit_gids;
+  const uint32_t *labels;              // n_genomes: any label values (the kernel only compares them)
+  uint32_t n_genomes, t0, nq;
+  uint32_t k;                          // 1 .. kAuditMaxK: the entries that vote
+  // out, n_genomes rows each, written at t0 .. t0 + nq; each may be null
+  uint32_t *verdict, *own_count, *own_gid, *other_count, *other_gid, *vote_gid, *vote_n;
+  uint32_t *info;                      // kAuditInfoWords, zeroed by the caller; the launch adds to them
+};
+hipError_t launch_audit(const AuditArgs &a, hipStream_t stream);
+
 // ---- taxon tally: the LCA rows counted per taxon and clade (nq_tally.hip; the calls: nq_api_tally.hip) ----
 // A workgroup of tally_rows_kernel combines a pass of kTallyPassRows rows in an LDS table of kTallySlots slots
 // {key u32, count u32, best sum u64} (32 KiB) before anything reaches global memory.

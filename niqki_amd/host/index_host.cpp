@@ -93,6 +93,7 @@ const struct {
     {{"niqki_neighbors_range", "niqki_cluster"}, "this engine has no self-join"},
     {{"niqki_dereplicate"}, "this engine has no dereplication"},
     {{"niqki_linkage"}, "this engine has no linkage"},
+    {{"niqki_set_labels", "niqki_audit"}, "this engine has no label audit"},
     {{"niqki_set_taxonomy", "niqki_staged_query_lca"}, "this engine has no LCA query"},
     {{"niqki_staged_cover"}, "this engine has no cover"},
     {{"niqki_set_labels", "niqki_staged_query_collapsed"}, "this engine has no collapsed query"},
@@ -440,8 +441,7 @@ void Index::group_query_staged(const Share &s, Hits &h) {
     }
 }
 
-void Index::set_collapse(const std::string &filestr) {
-  const auto call = NEED(COLLAPSE, niqki_set_labels);
+void Index::read_labels(const char *option, const std::string &filestr, std::vector<uint32_t> &label_of, std::vector<std::string> &texts) {
   LabelFile lf;
   std::string err;
   try {
@@ -450,9 +450,14 @@ void Index::set_collapse(const std::string &filestr) {
     lf = parse_label_file((const char *)bytes.p, bytes.size, filenames);
     err = lf.error;
   } catch (const std::exception &e) { err = e.what(); }
-  if (!err.empty()) refuse("--collapse '" + filestr + "': " + err);
-  label_of_ = std::move(lf.label_of);
-  label_text_ = std::move(lf.texts);
+  if (!err.empty()) refuse(std::string(option) + " '" + filestr + "': " + err);
+  label_of = std::move(lf.label_of);
+  texts = std::move(lf.texts);
+}
+
+void Index::set_collapse(const std::string &filestr) {
+  const auto call = NEED(COLLAPSE, niqki_set_labels);
+  read_labels("--collapse", filestr, label_of_, label_text_);
   check(call(h_, label_of_.empty() ? nullptr : label_of_.data(), (uint32_t)label_of_.size(), NIQKI_MEM_HOST), "niqki_set_labels");
   collapse_ = true;
 }
@@ -1025,6 +1030,57 @@ void Index::linkage_to_files(const std::string &mst_file, const std::string &lin
   to_file(tree_file, [&](auto &&sink) { write_tree(into, count, filenames, F, sink); });
 }
 
+// ---- label audit ---------------------------------------------------------------------
+
+const char *const Index::kAuditVerdicts[5] = {"alone", "agrees", "tied", "misplaced", "stray"};
+static_assert(NIQKI_AUDIT_ALONE == 0 && NIQKI_AUDIT_AGREES == 1 && NIQKI_AUDIT_TIED == 2 && NIQKI_AUDIT_MISPLACED == 3 &&
+                  NIQKI_AUDIT_STRAY == 4,
+              "kAuditVerdicts is indexed by the verdict");
+
+std::vector<uint64_t> Index::audit_to_file(const std::string &filestr, uint32_t k, const std::string &label_file, const char *option) {
+  const auto set_labels = NEED(AUDIT, niqki_set_labels);
+  const auto call = NEED(AUDIT, niqki_audit);
+  LabelFile lf;
+  read_labels(option, label_file, lf.label_of, lf.texts);
+  const uint32_t N = (uint32_t)lf.label_of.size();
+  niqki_params p{};
+  check(niqki_get_params(h_, &p), "niqki_get_params");
+  check(set_labels(h_, N ? lf.label_of.data() : nullptr, N, NIQKI_MEM_HOST), "niqki_set_labels");
+  std::vector<uint32_t> verdict(N), own_c(N), own_g(N), oth_c(N), oth_g(N), vote_g(N), vote_n(N);
+  check(call(h_, p.min_score, k, verdict.data(), own_c.data(), own_g.data(), oth_c.data(), oth_g.data(), vote_g.data(), vote_n.data(),
+             NIQKI_MEM_HOST), "niqki_audit");
+  std::vector<uint64_t> totals(5, 0);
+  ParallelTextWriter out(filestr, host_threads());
+  std::string text;
+  // name:jaccard of neighbour g at `count`, "-" where there is none
+  const auto neighbour = [&](uint32_t g, uint32_t count) {
+    if (g >= N) return std::string("-");
+    return filenames[g] + ':' + fmt_double((double)count / F);
+  };
+  for (uint32_t g = 0; g < N; ++g) {
+    if (verdict[g] >= 5) throw std::runtime_error("niqki_audit gave a verdict the program does not know");
+    totals[verdict[g]] += 1;
+    text += filenames[g];
+    text += '\t';
+    text += lf.texts[lf.label_of[g]];
+    text += '\t';
+    text += kAuditVerdicts[verdict[g]];
+    text += '\t';
+    text += neighbour(own_g[g], own_c[g]);
+    text += '\t';
+    text += neighbour(oth_g[g], oth_c[g]);
+    text += '\t';
+    text += oth_g[g] < N ? lf.texts[lf.label_of[oth_g[g]]] : std::string("-");
+    text += '\t';
+    text += vote_g[g] < N ? lf.texts[lf.label_of[vote_g[g]]] + ':' + std::to_string(vote_n[g]) : std::string("-");
+    text += '\n';
+    if (text.size() >= (size_t(4) << 20)) { out.write(text); text.clear(); }
+  }
+  out.write(text);
+  out.close();
+  return totals;
+}
+
 // ---- merging dumps ------------------------------------------------------------------
 
 void Index::merge_dump(const std::string &dump_file) {
@@ -1110,14 +1166,7 @@ void Index::remove_listed(const std::string &filestr) {
 void Index::unite_listed(const std::string &filestr) {
   const auto call = NEED(UNITE, niqki_unite);
   LabelFile lf;
-  std::string err;
-  try {
-    PinnedBuf bytes;
-    read_file_bytes(filestr, bytes);
-    lf = parse_label_file((const char *)bytes.p, bytes.size, filenames);
-    err = lf.error;
-  } catch (const std::exception &e) { err = e.what(); }
-  if (!err.empty()) refuse("--pan '" + filestr + "': " + err);
+  read_labels("--pan", filestr, lf.label_of, lf.texts);
   const uint32_t N = (uint32_t)lf.label_of.size();
   std::vector<uint32_t> entry_of(N);
   uint32_t n_entries = 0;

@@ -61,7 +61,7 @@ class Index {
   // the long options below are looked up at run time, so the program links against any engine, and a run that needs one
   // the engine lacks is refused with the feature's text.  One table in index_host.cpp holds, per feature, the symbols it
   // needs and that text.  All of these work on a single-GPU index only.
-  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, LCA, COVER, COLLAPSE, TALLY };
+  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, AUDIT, LCA, COVER, COLLAPSE, TALLY };
   // null where the engine has every call of the feature, else the text that says what is missing
   static const char *lacks(Feature f);
 
@@ -99,6 +99,17 @@ class Index {
   // --mst / --linkage / --tree: ONE niqki_linkage call at min_score as the floor serves the three files (an empty name:
   // not written); the texts are linkage_text.h's, gzip files like every output of the program.
   void linkage_to_files(const std::string &mst_file, const std::string &linkage_file, const std::string &tree_file);
+  // --audit <file>, --audit-k <n> (niqki_set_labels + niqki_audit at min_score).  Reads the run's label file
+  // (label_file.h; `option` is --pan or --collapse, whichever supplied it) against `filenames` as they are at that
+  // moment, hands the labels to the engine and writes a line per indexed genome, in index order, a gzip file like every
+  // output of the program:
+  //   name<TAB>label<TAB>verdict<TAB>ownName:jaccard<TAB>otherName:jaccard<TAB>otherLabel<TAB>voteLabel:votes
+  // the nearest other genome under the genome's label, the nearest under another label and that label, the label most
+  // frequent among the k nearest; "-" where there is no such neighbour; verdict as the engine gives it.  Returns the
+  // number of genomes per verdict.  A file error is an error of the run, and then nothing is written, the -O file
+  // included.
+  std::vector<uint64_t> audit_to_file(const std::string &filestr, uint32_t k, const std::string &label_file, const char *option);
+  static const char *const kAuditVerdicts[5];   // the texts of NIQKI_AUDIT_ALONE .. NIQKI_AUDIT_STRAY
 
   // The three that replace the list of every -Q / -l query; --neighbors and -M are not affected.
   // --cover (niqki_staged_cover; resident index): with `cover` set the list is the query's greedy cover: per pick the
@@ -133,6 +144,9 @@ class Index {
   Fn need(Feature f, const char *name) const;
   // a run refused before anything is written: the output file the constructor made goes away again, `text` is thrown
   [[noreturn]] void refuse(const std::string &text);
+  // the label file of `option` (--collapse, --pan; label_file.h, plain or gzip) read against `filenames`: per genome its
+  // label, per label its text; a file error refuses the run with the option, the file and the line
+  void read_labels(const char *option, const std::string &filestr, std::vector<uint32_t> &label_of, std::vector<std::string> &texts);
   void open_group_and_output(const std::string &out_filename);   // the tail of both constructors
   struct Batch;
   // The entries of a batch dealt to the GPUs in order: n_entry[r] of them on rank r, at most `per` on any (one GPU:

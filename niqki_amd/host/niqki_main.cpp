@@ -27,6 +27,11 @@
 //   --pan <f>      f holds lines label<TAB>member, as for --collapse: after every index input, --merge, --novel and
 //                  --remove the index holds one entry per label, named by the label, whose sketch is the union of the
 //                  members' sketches (niqki_unite); -D, the self-join options, -M and the queries see that index
+//   --audit <f>    with --pan or --collapse: the leave-one-out neighbours of every indexed genome at the -J threshold read
+//                  against that label file, into f (niqki_set_labels + niqki_audit): name, label, verdict (alone, agrees,
+//                  tied, misplaced, stray), the nearest other genome under the label, the nearest under another label
+//                  and that label, the label most frequent among the --audit-k (default 1) nearest; with --pan the
+//                  audit runs immediately before the index is united, with --collapse where that file is applied
 //   --derep-dump <f>  dereplicate at the -J threshold, keep the representatives only and dump that index into f (as -D);
 //                  the rest of the run (-M, --neighbors, -Q, -l) is answered by the dereplicated index
 //   --merge <f>    append the genomes of the dump f to the index (niqki_append_*); may be repeated, ALL occurrences are
@@ -60,7 +65,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, AUDIT, AUDIT_K, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -106,6 +111,8 @@ const Desc kDesc[] = {
     {LCA, "", "lca", NONEMPTY, "  --lca <filename>              Report each -Q / -q query's taxon instead of all its hits: the lowest common ancestor of its near-best hits in the taxonomy of the file, lines parent<TAB>child (plain or gzip) over the labels of --collapse or, without it, the genome names; no_common_taxon where the hits share none."},
     {LCA_TOP, "", "lca-top", NONEMPTY, "  --lca-top <permille>          With --lca: consider the hits within <permille> thousandths of the best hit's count, 0..1000 (100); 0: only ties with the best hit."},
     {REPORT, "", "report", NONEMPTY, "  --report <filename>           With --lca: after the last -Q / -l query, the tally of all their taxa: lines percent<TAB>queries in the clade<TAB>queries on the taxon<TAB>depth<TAB>mean jaccard of their best hits<TAB>taxon, indented by depth, after the two lines unclassified and no_common_taxon."},
+    {AUDIT, "", "audit", NONEMPTY, "  --audit <filename>            With --pan or --collapse: check that label file against the index at the -J threshold, a line per indexed genome: name<TAB>label<TAB>verdict<TAB>ownName:jaccard<TAB>otherName:jaccard<TAB>otherLabel<TAB>voteLabel:votes (its nearest other genome under its label, the nearest under another label, the vote of its nearest genomes; - where there is none); verdict is alone, agrees, tied, misplaced or stray."},
+    {AUDIT_K, "", "audit-k", NONEMPTY, "  --audit-k <n>                 With --audit: the nearest genomes that vote, 1..63 (1)."},
 };
 
 struct Parsed {
@@ -287,6 +294,7 @@ const struct { Opt asked_by[3]; Feature feature; } kNeeds[] = {
     {{NEIGHBORS, CLUSTER, CLUSTER}, Feature::SELF_JOIN},
     {{DEREP, DEREP_DUMP, DEREP_DUMP}, Feature::DEREPLICATION},
     {{MST, LINKAGE, TREE}, Feature::LINKAGE},
+    {{AUDIT, AUDIT, AUDIT}, Feature::AUDIT},
     {{LCA, LCA, LCA}, Feature::LCA},
     {{COVER, COVER, COVER}, Feature::COVER},
     {{COLLAPSE, COLLAPSE, COLLAPSE}, Feature::COLLAPSE},
@@ -344,11 +352,31 @@ int main(int argc, char *argv[]) {
   // the self-join asks one index about itself: a slot shard of a --gpus group sees partial counts; and only a
   // single-GPU index can drop genomes or take the genomes of a dump
   const bool linkage = o.has(MST) || o.has(LINKAGE) || o.has(TREE);
-  if (n_gpus > 1 && (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL) || linkage))
+  if (n_gpus > 1 && (o.has(NEIGHBORS) || o.has(CLUSTER) || o.has(DEREP) || o.has(REMOVE) || o.has(DEREP_DUMP) || o.has(MERGE) || o.has(NOVEL) || linkage || o.has(AUDIT)))
     return refused("the self-join (--neighbors, --cluster, --derep), dropping genomes and merging dumps (--merge, --novel) need a single-GPU index (--gpus 1)");
   // the union is taken over the whole sketches of one device's store
   if (n_gpus > 1 && o.has(PAN)) return refused("--pan needs a single-GPU index (--gpus 1)");
   if (const char *text = engine_lacks(o, Feature::APPEND, Feature::LINKAGE)) return refused(text);
+
+  // --audit-k: how many of a genome's nearest neighbours vote, a plain integer
+  uint32_t audit_k = 1;
+  if (o.has(AUDIT_K)) {
+    const string &a = o.last(AUDIT_K);
+    char *end = nullptr;
+    errno = 0;
+    const long long v = strtoll(a.c_str(), &end, 10);
+    if (a.empty() || a[0] == '+' || a[0] == ' ' || end == a.c_str() || *end != 0 || errno || v < 1 || v > 63) {
+      fprintf(stderr, "Option 'audit-k' requires an integer in 1..63\n");
+      cout << "Bad usage!!!" << endl;
+      return EXIT_FAILURE;
+    }
+    audit_k = (uint32_t)v;
+  }
+  // the audit checks the label file the run acts on
+  if (o.has(AUDIT)) {
+    if (!o.has(COLLAPSE) && !o.has(PAN)) return refused("--audit needs --collapse or --pan");
+    if (const char *text = engine_lacks(o, Feature::AUDIT, Feature::AUDIT)) return refused(text);
+  }
 
   // --lca-top: thousandths of the best count, a plain integer
   uint32_t lca_permille = 100;
@@ -404,7 +432,15 @@ int main(int argc, char *argv[]) {
     if (o.has(DOWNLAD)) cout << "--indexdownload needs network access and is not part of this build" << endl;
     if (o.has(MERGE))   // the one option of which every occurrence counts
       for (const string &dump : o.opts.at(MERGE)) ix->merge_dump(dump);
-    RunClock::tp novel_begin, novel_end, remove_begin, remove_end, pan_begin, pan_end;
+    RunClock::tp novel_begin, novel_end, remove_begin, remove_end, pan_begin, pan_end, audit_begin, audit_end;
+    vector<uint64_t> audit_totals;
+    // the row of the audit phase and the genomes per verdict
+    const auto audit_done = [&]() {
+      RunClock::row("| Audit lasted (s)                  |", audit_begin, audit_end);
+      cout << "Audit:";
+      for (size_t v = 0; v < audit_totals.size(); ++v) cout << (v ? ", " : " ") << audit_totals[v] << " " << nqhost::Index::kAuditVerdicts[v];
+      cout << endl;
+    };
     if (o.has(NOVEL)) {
       novel_begin = system_clock::now();
       // the -J of THIS run where it is given: an index that -L loaded carries the min_score of its dump
@@ -417,6 +453,11 @@ int main(int argc, char *argv[]) {
       remove_end = system_clock::now();
     }
     if (o.has(PAN)) {   // ... and after the genomes that leave: -L db.dump --pan species.tsv -D species.dump
+      if (o.has(AUDIT)) {   // the file is checked before it is acted on: the union cannot be undone
+        audit_begin = system_clock::now();
+        audit_totals = ix->audit_to_file(o.last(AUDIT), audit_k, o.last(PAN), "--pan");
+        audit_end = system_clock::now();
+      }
       pan_begin = system_clock::now();
       ix->unite_listed(o.last(PAN));
       pan_end = system_clock::now();
@@ -425,6 +466,7 @@ int main(int argc, char *argv[]) {
     clk.index_done();
     if (o.has(NOVEL)) RunClock::row("| Novelty filter lasted (s)         |", novel_begin, novel_end);
     if (o.has(REMOVE)) RunClock::row("| Remove lasted (s)                 |", remove_begin, remove_end);
+    if (o.has(PAN) && o.has(AUDIT)) audit_done();
     if (o.has(PAN)) RunClock::row("| Pan sketches lasted (s)           |", pan_begin, pan_end);
     if (o.has(CLUSTER)) {   // a phase of its own between indexing and the queries
       ix->cluster_to_file(o.last(CLUSTER));
@@ -448,6 +490,13 @@ int main(int argc, char *argv[]) {
     }
     run_matrix(*ix, o, clk);
     // after everything that changes the index in memory (-M may index its list): the names are those of the final index
+    if (o.has(AUDIT) && !o.has(PAN)) {   // a phase of its own, where the --collapse file is applied
+      audit_begin = system_clock::now();
+      audit_totals = ix->audit_to_file(o.last(AUDIT), audit_k, o.last(COLLAPSE), "--collapse");
+      audit_end = system_clock::now();
+      audit_done();
+      clk.index_end += audit_end - audit_begin;   // (the query row does not count it)
+    }
     if (o.has(LCA)) ix->set_lca(o.last(LCA), lca_permille, o.has(COLLAPSE) ? o.last(COLLAPSE) : string());
     else if (o.has(COLLAPSE)) ix->set_collapse(o.last(COLLAPSE));
     if (o.has(NEIGHBORS)) ix->query_neighbors();
