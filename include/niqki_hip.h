@@ -849,6 +849,38 @@ int niqki_retain(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32
  * microseconds for the last call (tools/bench_unite.py).  DESIGN.md 4.6h. */
 int niqki_unite(niqki_index *ix, const uint32_t *labels, uint32_t n, uint32_t *new_ids, uint32_t *n_labels, int mem);
 
+/* Register histograms: what a genome's size is estimated from.  The top H bits of a cell are a HyperLogLog register
+ * (get_fingerprint, src/niqki_index.cpp:277-287: max(0, 2^H - 1 - leading zeros of the hash); a slot keeps its smallest
+ * fingerprint, so the most leading zeros), and a sketch's F registers give its number of distinct k-mers with standard
+ * error 1.04 / sqrt(F).  These calls count the registers; the estimate itself is host arithmetic on the counts
+ * (niqki_amd/host/size_estimate.h), so every device result is an integer that can be checked bit for bit.
+ * Definition: let B = NIQKI_REGISTER_BINS(H) = 2^H + 1 and M = W - H.  A cell c is valid when 0 <= c < 2^W, the rule of
+ * Index::query_sketch.  hist is uint32_t [rows][B] in `mem`: hist[j * B + (c >> M)] counts the valid cells of row j with
+ * that register value, hist[j * B + 2^H] its cells that are not valid; every row sums to 2^S.
+ * niqki_registers: row j is genome begin + j, its cells what niqki_get_sketches(ix, begin, end - begin) returns -- a
+ * function of the genome set alone, whatever the tile count, paging, a delta segment, or an earlier niqki_retain,
+ * niqki_unite or append.  niqki_sketch_registers: the n x 2^S cells given (same `mem`).  niqki_staged_registers: the
+ * sketches of the staged batch (niqki_stage_raw), n_entry rows; the batch stays usable, as after niqki_staged_cover.
+ * Refused: begin > end or end > niqki_genome_count (NIQKI_E_INVALID); H > 6 (NIQKI_E_INVALID: select_best_H picks 2..6,
+ * and 65 bins are the most a lane's table should hold); fingerprint parts that are not regular, that is H changed by
+ * niqki_select_best_H after construction (NIQKI_E_STATE: the top H bits are no register then); a slot-range shard
+ * (NIQKI_E_STATE).  niqki_last_error says which.  An empty range, n = 0, an empty staged batch or an index without
+ * genomes: NIQKI_OK, nothing is written.  Groups, the _shared and the _ahead calls have no such call.
+ * mem as in niqki_cluster: NIQKI_MEM_DEVICE writes hist in stream order and does not synchronise (unless profiling is
+ * on); NIQKI_MEM_HOST goes through one device workspace and crosses once.
+ * How: the store is u16 [2^S][capacity], slot-major.  A wavefront takes 64 consecutive genome columns -- one row of them
+ * is one 128-byte line -- and a chunk of the rows; each lane owns one genome and keeps its B 32-bit counters in LDS, laid
+ * out [bin][lane], so no two lanes share a counter or, within a step, a bank.  The rows are cut into chunks so that a
+ * small index still fills the device, and a chunk's counters leave with one global atomic add per (genome, bin),
+ * contiguous in hist.  The row pass gives a wavefront one sketch (or a chunk of it), 64 cells a step, the same counters,
+ * and sums them over the lanes at the end.  A paged handle's store is host memory: the host counts it.
+ * While profiling is on: "registers_us_store", "registers_us_rows", the last call of each kernel in microseconds
+ * (tools/bench_sizes.py).  DESIGN.md 4.6j. */
+#define NIQKI_REGISTER_BINS(H) ((1u << (H)) + 1u)
+int niqki_registers(niqki_index *ix, uint32_t begin, uint32_t end, uint32_t *hist, int mem);
+int niqki_sketch_registers(niqki_index *ix, const int32_t *sketches, uint32_t n, uint32_t *hist, int mem);
+int niqki_staged_registers(niqki_index *ix, uint32_t *hist, int mem);
+
 /* dump_index_disk payload (src/niqki_index.cpp:42-55), before gzip and
  * without the trailing names: 6 x u32 header {lF,K,H,W,min_score,N} then per
  * bucket u32 size + size x u32 gid, buckets in fp + slot*2^W order, gids

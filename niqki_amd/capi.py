@@ -146,6 +146,9 @@ ABI = [
     ("niqki_tally_end", _int, [_vp]),
     ("niqki_retain", _int, [_vp, _vp, _vp, C.POINTER(_u32), _int]),
     ("niqki_unite", _int, [_vp, _vp, _u32, _vp, C.POINTER(_u32), _int]),
+    ("niqki_registers", _int, [_vp, _u32, _u32, _vp, _int]),
+    ("niqki_sketch_registers", _int, [_vp, _vp, _u32, _vp, _int]),
+    ("niqki_staged_registers", _int, [_vp, _vp, _int]),
     ("niqki_export_dump", _int, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("niqki_import_dump", _int, [C.POINTER(Params), _vp, _u64, C.POINTER(_u64), C.POINTER(_vp)]),
     ("niqki_export_dump_header", _int, [_vp, _vp]),
@@ -797,6 +800,44 @@ class Engine:
         self._ck(self.L.niqki_unite(self.h, _p(lab) if lab.size else None, lab.size, _p(ids) if lab.size else None,
                                     C.byref(n), MEM_HOST))
         return int(n.value), ids
+
+    @property
+    def register_bins(self):
+        """NIQKI_REGISTER_BINS(H): 2^H register values and one bin for the cells that are not valid."""
+        return (1 << self.H) + 1
+
+    def registers(self, begin=0, end=None):
+        """niqki_registers: the register histograms of genomes [begin, end) (end None: all), uint32 (end - begin,
+        2^H + 1): column r counts the genome's valid cells whose top H bits are r, the last one its cells that are not
+        valid.  size_estimate.estimate() turns a row into a number of distinct k-mers."""
+        end = self.n_genomes if end is None else end
+        out = np.zeros((max(end - begin, 0), self.register_bins), dtype=np.uint32)
+        self._ck(self.L.niqki_registers(self.h, begin, end, _p(out) if out.size else None, MEM_HOST))
+        return out
+
+    def sketch_registers(self, sketches):
+        """niqki_sketch_registers: the same histograms of the sketches given, int32 (n, 2^S)."""
+        sk = np.ascontiguousarray(sketches, dtype=np.int32).reshape(-1, self.F)
+        out = np.zeros((sk.shape[0], self.register_bins), dtype=np.uint32)
+        self._ck(self.L.niqki_sketch_registers(self.h, _p(sk) if sk.size else None, sk.shape[0], _p(out) if out.size else None,
+                                               MEM_HOST))
+        return out
+
+    def staged_registers(self):
+        """niqki_staged_registers: the same histograms of the staged batch's sketches; the batch stays usable."""
+        out = np.zeros((self._staged.n_entry, self.register_bins), dtype=np.uint32)
+        self._ck(self.L.niqki_staged_registers(self.h, _p(out) if out.size else None, MEM_HOST))
+        return out
+
+    def registers_dev(self, hist, begin=0, end=None, sketches=None, n=None, staged=False):
+        """The three register calls on device arrays, written in stream order.  hist: 32-bit elements, rows x (2^H + 1).
+        sketches (with n): niqki_sketch_registers; staged: niqki_staged_registers; else niqki_registers of [begin, end)."""
+        if sketches is not None:
+            self._ck(self.L.niqki_sketch_registers(self.h, _p(sketches), int(n), _p(hist), MEM_DEVICE))
+        elif staged:
+            self._ck(self.L.niqki_staged_registers(self.h, _p(hist), MEM_DEVICE))
+        else:
+            self._ck(self.L.niqki_registers(self.h, begin, self.n_genomes if end is None else end, _p(hist), MEM_DEVICE))
 
     def get_sketches(self, begin, n):
         out = np.empty((n, self.F), dtype=np.int32)

@@ -383,7 +383,7 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
                  &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
                  &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info, &ix->tally_acc, &ix->ws_tally_rows,
-                 &ix->ws_audit, &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
+                 &ix->ws_audit, &ix->ws_reg, &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -649,6 +649,9 @@ int niqki_get_stat(const niqki_index *ix, const char *key, uint64_t *value) {
   // the last niqki_unite call while profiling was on: the host's preparation and the minimum pass, microseconds
   if (!std::strcmp(key, "unite_us_prepare")) { *value = us(ix->unite_ms[0]); return NIQKI_OK; }
   if (!std::strcmp(key, "unite_us_min")) { *value = us(ix->unite_ms[1]); return NIQKI_OK; }
+  // the last store pass / row pass of the niqki_*registers calls while profiling was on, microseconds
+  if (!std::strcmp(key, "registers_us_store")) { *value = us(ix->registers_ms[0]); return NIQKI_OK; }
+  if (!std::strcmp(key, "registers_us_rows")) { *value = us(ix->registers_ms[1]); return NIQKI_OK; }
   if (!std::strcmp(key, "inflate_files_in_flight") || !std::strcmp(key, "inflate_files_in_flight_8k")) {
     // how many files a launch of the device inflate runs at once (workgroups the device keeps resident), by kernel form
     (void)hipSetDevice(ix->device);

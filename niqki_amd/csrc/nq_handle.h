@@ -186,6 +186,10 @@ struct niqki_index {
   // the last niqki_unite call while profiling was on (stats "unite_us_prepare", "unite_us_min"): the host's numbering and
   // member lists with their copies, the minimum pass
   double unite_ms[2] = {0, 0};
+  // niqki_registers / niqki_sketch_registers / niqki_staged_registers: a host call's histograms on the device; the last
+  // call of each kernel while profiling was on (stats "registers_us_store", "registers_us_rows")
+  nqi::Buf ws_reg;
+  double registers_ms[2] = {0, 0};
 
   nqi::Buf ws_seq, ws_recoff, ws_entry, ws_sk, ws_counts, ws_blk, ws_hitoff, ws_hc, ws_hg, ws_tc, ws_tg,
       ws_misc, ws_stash, ws_hl, ws_parent;

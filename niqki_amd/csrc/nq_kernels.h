@@ -130,6 +130,12 @@ hipError_t launch_store_compact(const uint16_t *src, uint64_t src_cap, uint32_t 
 // entries; every member below src_cap; ANOTHER store than src)
 hipError_t launch_store_unite(const uint16_t *src, uint64_t src_cap, uint16_t *dst, uint64_t dst_cap, uint32_t f_local, uint32_t n_labels,
                               const uint32_t *off, const uint32_t *members, hipStream_t stream);
+// niqki_registers / niqki_sketch_registers (nq_registers.hip): ADD to hist, u32 [n][2^H + 1] preset by the caller, the
+// register histograms (cell >> M; the last bin: cells outside [0, 2^W)) of store columns [begin, end) over f_local rows,
+// or of n sketch rows of F cells.  d must be regular (mask_m, max_rem as the constructor derives them from H), H <= 6.
+hipError_t launch_store_registers(const Derived &d, const uint16_t *store, uint64_t cap, uint32_t f_local, uint32_t begin, uint32_t end,
+                                  uint32_t *hist, hipStream_t stream);
+hipError_t launch_row_registers(const Derived &d, const int32_t *sketches, uint32_t n, uint32_t *hist, hipStream_t stream);
 // Build, phase 1: units per (tile, slot) -> exclusive prefix per tile in
 // slot_units, tile totals as a prefix (in ids) in tile_base.
 hipError_t launch_build_sizes(const IndexView &v, uint32_t *slot_units, uint64_t *tile_base,

@@ -96,6 +96,7 @@ const struct {
     {{"niqki_set_labels", "niqki_audit"}, "this engine has no label audit"},
     {{"niqki_set_taxonomy", "niqki_staged_query_lca"}, "this engine has no LCA query"},
     {{"niqki_staged_cover"}, "this engine has no cover"},
+    {{"niqki_registers", "niqki_staged_registers"}, "this engine cannot read sketch registers"},
     {{"niqki_set_labels", "niqki_staged_query_collapsed"}, "this engine has no collapsed query"},
     {{"niqki_tally_begin", "niqki_tally_read"}, "this engine has no taxon tally"},
 };
@@ -399,6 +400,7 @@ void Index::staged_insert(const Share &s) {
 
 void Index::staged_hits(const Share &s, Hits &h) {
   h.collapsed = h.lca = false;
+  h.qsize.clear();
   if (grp_) group_query_staged(s, h);
   else query_staged(s.n_entry[0], h);
 }
@@ -550,7 +552,47 @@ void Index::query_staged(size_t n, Hits &h) {
     check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 20, 64), n * N,
                      [&](uint64_t cap) { return niqki_staged_query(h_, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST); }),
           "niqki_staged_query");
+    if (containment) {   // --containment: the plain list with each entry's two shares; the batch's sizes from its staged sketches
+      const auto call = NEED(SIZES, niqki_staged_registers);
+      if (!genome_size_ok_) {
+        genome_size_ = genome_sizes((uint32_t)N);
+        genome_size_ok_ = true;
+      }
+      const uint32_t B = NIQKI_REGISTER_BINS(H);
+      std::vector<uint32_t> hist(std::max<size_t>(n, 1) * B);
+      check(call(h_, hist.data(), NIQKI_MEM_HOST), "niqki_staged_registers");
+      h.qsize.resize(n);
+      for (size_t i = 0; i < n; ++i) h.qsize[i] = nqsize::estimate(hist.data() + i * B, lF, H);
+    }
   }
+}
+
+std::vector<nqsize::Estimate> Index::genome_sizes(uint32_t n) const {
+  const auto call = NEED(SIZES, niqki_registers);
+  const uint32_t B = NIQKI_REGISTER_BINS(H);
+  std::vector<uint32_t> hist((size_t)std::max<uint32_t>(n, 1) * B);
+  check(call(h_, 0, n, hist.data(), NIQKI_MEM_HOST), "niqki_registers");
+  std::vector<nqsize::Estimate> sizes(n);
+  for (uint32_t g = 0; g < n; ++g) sizes[g] = nqsize::estimate(hist.data() + (size_t)g * B, lF, H);
+  return sizes;
+}
+
+void Index::sizes_to_file(const std::string &filestr) {
+  const std::vector<nqsize::Estimate> sizes = genome_sizes((uint32_t)filenames.size());
+  ParallelTextWriter out(filestr, host_threads());
+  std::string text;
+  char num[64];
+  for (size_t g = 0; g < sizes.size(); ++g) {
+    text += filenames[g];
+    text += '\t';
+    text.append(num, (size_t)snprintf(num, sizeof num, "%.0f", sizes[g].kmers));
+    text += '\t';
+    text += nqsize::status_text(sizes[g].status);
+    text += '\n';
+    if (text.size() >= (size_t(4) << 20)) { out.write(text); text.clear(); }
+  }
+  out.write(text);
+  out.close();
 }
 
 // ... written in entry order
@@ -578,6 +620,11 @@ void Index::write_hits(const Hits &h) {
       text += ':';
       const int n = snprintf(num, sizeof num, "%g", (double)h.hc[j] / F);
       text.append(num, (size_t)n);
+      if (!h.qsize.empty()) {   // --containment: :cq:cg behind the jaccard
+        const nqsize::Containment c = nqsize::containment(h.hc[j], lF, h.qsize[i], genome_size_[h.hg[j]]);
+        if (c.defined) text.append(num, (size_t)snprintf(num, sizeof num, ":%g:%g", c.cq, c.cg));
+        else text += ":-:-";
+      }
       text += ' ';
     }
     text += '\n';

@@ -12,6 +12,7 @@
 
 #include "../../include/niqki_hip.h"
 #include "gzio.h"
+#include "size_estimate.h"
 
 namespace nqhost {
 
@@ -61,7 +62,7 @@ class Index {
   // the long options below are looked up at run time, so the program links against any engine, and a run that needs one
   // the engine lacks is refused with the feature's text.  One table in index_host.cpp holds, per feature, the symbols it
   // needs and that text.  All of these work on a single-GPU index only.
-  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, AUDIT, LCA, COVER, COLLAPSE, TALLY };
+  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, AUDIT, LCA, COVER, SIZES, COLLAPSE, TALLY };
   // null where the engine has every call of the feature, else the text that says what is missing
   static const char *lacks(Feature f);
 
@@ -134,6 +135,15 @@ class Index {
   std::string report;
   void write_report();
 
+  // --sizes <file> (niqki_registers + size_estimate.h): a line per indexed genome, in index order, a gzip file like
+  // every output of the program: name<TAB>kmers<TAB>status -- the estimated number of distinct k-mers (%.0f) and ok,
+  // below or above (outside the estimator's range: the number is not to be used).
+  void sizes_to_file(const std::string &filestr);
+  // --containment (niqki_registers once, niqki_staged_registers per batch): with `containment` set every entry of a
+  // plain -Q / -l list is name:jaccard:cq:cg -- the share of the query's k-mers found in the genome and of the genome's
+  // found in the query, "-" each where either size is not ok.  Order, threshold and --top are those of the plain list.
+  bool containment = false;
+
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
 
@@ -166,6 +176,7 @@ class Index {
     std::vector<uint32_t> hc, hg;
     bool collapsed = false;   // hg names each label's best member: the line prints the label's text (--collapse)
     bool lca = false;         // hg holds a taxon (NIQKI_TAXON_NONE: no common one): the line prints the taxon's text (--lca)
+    std::vector<nqsize::Estimate> qsize;   // --containment: the entries' sizes (empty: a plain list)
     // lines mode: the names are header lines of a piece of the input that stays alive until the WRITER thread has
     // taken them (name e = the line at name_base + name_at[e]); `keep` is that piece
     const uint8_t *name_base = nullptr;
@@ -189,6 +200,10 @@ class Index {
   std::vector<uint32_t> taxon_parent_;   // ... and its parent (--report)
   bool tally_open_ = false;              // --report: the engine's tally is open (an index without genomes has no taxonomy to open it on)
   uint64_t untallied_ = 0;               // ... else the entries queried: none of them has a hit
+  // the sizes of the indexed genomes [0, n) from their register histograms (niqki_registers, size_estimate.h)
+  std::vector<nqsize::Estimate> genome_sizes(uint32_t n) const;
+  std::vector<nqsize::Estimate> genome_size_;   // --containment: ... taken once, at the first query batch
+  bool genome_size_ok_ = false;
   std::string out_text_;                // write_hits' lines before they go to the writer
   std::string out_path_;                // the -O file (refuse takes it away again)
   // Lines mode.  stage_lines: one niqki_stage_raw of the whole records at raw[0, size) on h -- at most hdr.size()

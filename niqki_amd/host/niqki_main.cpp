@@ -34,6 +34,13 @@
 //                  audit runs immediately before the index is united, with --collapse where that file is applied
 //   --derep-dump <f>  dereplicate at the -J threshold, keep the representatives only and dump that index into f (as -D);
 //                  the rest of the run (-M, --neighbors, -Q, -l) is answered by the dereplicated index
+//   --sizes <f>    after everything that changes the index in memory and before the queries: a line per indexed genome into
+//                  f, name<TAB>kmers<TAB>status -- its number of distinct k-mers estimated from the HyperLogLog registers in
+//                  the top H bits of its sketch cells (niqki_registers, size_estimate.h), and ok, below or above: outside
+//                  the estimator's range the number is not to be used
+//   --containment  every entry of a plain -Q / -l list is name:jaccard:cq:cg, the share of the query's k-mers found in the
+//                  genome and of the genome's found in the query, from the count and the two estimated sizes
+//                  (niqki_staged_registers per batch); -:- where either size is out of range
 //   --merge <f>    append the genomes of the dump f to the index (niqki_append_*); may be repeated, ALL occurrences are
 //                  taken, in command-line order, after -L / -I / -i and before --remove and -D
 //   --novel <f>    after every index input and merge: dereplicate at the -J threshold with the genomes of -L given
@@ -65,7 +72,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, AUDIT, AUDIT_K, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, AUDIT, AUDIT_K, SIZES, CONTAINMENT, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -113,6 +120,8 @@ const Desc kDesc[] = {
     {REPORT, "", "report", NONEMPTY, "  --report <filename>           With --lca: after the last -Q / -l query, the tally of all their taxa: lines percent<TAB>queries in the clade<TAB>queries on the taxon<TAB>depth<TAB>mean jaccard of their best hits<TAB>taxon, indented by depth, after the two lines unclassified and no_common_taxon."},
     {AUDIT, "", "audit", NONEMPTY, "  --audit <filename>            With --pan or --collapse: check that label file against the index at the -J threshold, a line per indexed genome: name<TAB>label<TAB>verdict<TAB>ownName:jaccard<TAB>otherName:jaccard<TAB>otherLabel<TAB>voteLabel:votes (its nearest other genome under its label, the nearest under another label, the vote of its nearest genomes; - where there is none); verdict is alone, agrees, tied, misplaced or stray."},
     {AUDIT_K, "", "audit-k", NONEMPTY, "  --audit-k <n>                 With --audit: the nearest genomes that vote, 1..63 (1)."},
+    {SIZES, "", "sizes", NONEMPTY, "  --sizes <filename>            Estimated number of distinct k-mers of every indexed genome, after everything that changes the index and before the queries: lines name<TAB>kmers<TAB>status; status is ok, below or above (outside the estimator's range: do not use the number)."},
+    {CONTAINMENT, "", "containment", NONE, "  --containment                 Report each -Q / -q hit as name:jaccard:cq:cg, the share of the query's k-mers found in the genome and of the genome's found in the query (-:- where a size cannot be estimated)."},
 };
 
 struct Parsed {
@@ -297,6 +306,7 @@ const struct { Opt asked_by[3]; Feature feature; } kNeeds[] = {
     {{AUDIT, AUDIT, AUDIT}, Feature::AUDIT},
     {{LCA, LCA, LCA}, Feature::LCA},
     {{COVER, COVER, COVER}, Feature::COVER},
+    {{SIZES, CONTAINMENT, CONTAINMENT}, Feature::SIZES},
     {{COLLAPSE, COLLAPSE, COLLAPSE}, Feature::COLLAPSE},
     {{REPORT, REPORT, REPORT}, Feature::TALLY},
 };
@@ -357,6 +367,14 @@ int main(int argc, char *argv[]) {
   // the union is taken over the whole sketches of one device's store
   if (n_gpus > 1 && o.has(PAN)) return refused("--pan needs a single-GPU index (--gpus 1)");
   if (const char *text = engine_lacks(o, Feature::APPEND, Feature::LINKAGE)) return refused(text);
+  // the two shares belong to the entries of the plain list, and the registers are read from whole sketches on one device
+  if (o.has(CONTAINMENT)) {
+    if (o.has(COVER) || o.has(COLLAPSE) || o.has(LCA))
+      return refused("--containment extends the plain hit list: --cover, --collapse and --lca replace it, choose one");
+    if (n_gpus > 1) return refused("--containment needs a single-GPU index (--gpus 1)");
+  }
+  if (n_gpus > 1 && o.has(SIZES)) return refused("--sizes needs a single-GPU index (--gpus 1)");
+  if (const char *text = engine_lacks(o, Feature::SIZES, Feature::SIZES)) return refused(text);
 
   // --audit-k: how many of a genome's nearest neighbours vote, a plain integer
   uint32_t audit_k = 1;
@@ -423,6 +441,7 @@ int main(int argc, char *argv[]) {
     if (o.has(LOAD)) ix.reset(new nqhost::Index(o.last(LOAD), true, out_file, device, n_gpus, resident_mib, top_k));
     else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib, top_k));
     ix->cover = o.has(COVER);
+    ix->containment = o.has(CONTAINMENT);
     if (o.has(REPORT)) ix->report = o.last(REPORT);
     if (const unsigned expect = (unsigned)int_opt(o, GENOME_SIZE, 0)) ix->select_best_H(expect);   // src/niqki.cpp:303-305
 
@@ -496,6 +515,13 @@ int main(int argc, char *argv[]) {
       audit_end = system_clock::now();
       audit_done();
       clk.index_end += audit_end - audit_begin;   // (the query row does not count it)
+    }
+    if (o.has(SIZES)) {   // a phase of its own: the index is final, the names are those the queries will print
+      const RunClock::tp sizes_begin = system_clock::now();
+      ix->sizes_to_file(o.last(SIZES));
+      const RunClock::tp sizes_end = system_clock::now();
+      RunClock::row("| Sizes lasted (s)                  |", sizes_begin, sizes_end);
+      clk.index_end += sizes_end - sizes_begin;   // (the query row does not count it)
     }
     if (o.has(LCA)) ix->set_lca(o.last(LCA), lca_permille, o.has(COLLAPSE) ? o.last(COLLAPSE) : string());
     else if (o.has(COLLAPSE)) ix->set_collapse(o.last(COLLAPSE));
