@@ -682,6 +682,66 @@ int niqki_query_collapsed(niqki_index *ix, const int32_t *sketches, uint32_t nq,
 int niqki_staged_query_collapsed(niqki_index *ix, uint64_t *hit_off, uint32_t *hit_counts, uint32_t *hit_gids,
                                  uint32_t *hit_members, uint64_t capacity, int mem);
 
+/* Containment search: per query the hits whose SHARE reaches a threshold, ordered by it.  A Jaccard index is the wrong
+ * number for a part against a whole -- a 64 F-k-mer piece of a 256 F-k-mer genome has J near 0.25 with it although every
+ * k-mer of the piece is in the genome -- and niqki_registers only annotates a list that min_score and the count have
+ * already chosen and ordered.  These calls select by the share, order by it and cut to top_k on the device, so a
+ * batch's output stays bounded by nq x top_k.
+ * Sizes.  A size is a uint64_t number of distinct k-mers; 0 means "no usable size"; sizes are below 2^40, a larger one
+ * is NIQKI_E_INVALID.  niqki_set_sizes gives every indexed genome g its size[g] and follows niqki_set_labels in every
+ * respect: n must equal niqki_genome_count (else NIQKI_E_INVALID, the sizes the handle had stay; so they do when a size
+ * does not fit); sizes == NULL or n == 0 removes them; a device array is taken in stream order and the call may
+ * synchronise once; the sizes belong to a genome set, so every call that adds or drops genomes removes them (the calls
+ * named under niqki_set_labels, and niqki_unite).  They are independent of labels and taxonomy.  Stat "sizes" = n, or
+ * 0.  The caller supplies the numbers: the host program takes them from niqki_registers and its estimator, another
+ * caller may know exact ones.
+ * Share.  For a hit with count c (0 <= c <= F = 2^S, S <= 16), query size q, genome size g and a mode: d = q for
+ * NIQKI_CONTAIN_QUERY (the share of the query's k-mers found in the genome), d = g for NIQKI_CONTAIN_GENOME, d = min(q, g)
+ * for NIQKI_CONTAIN_MAX (the larger of the two shares).  Nn = c (q + g), Dd = (F + c) d -- that is |A n B| =
+ * J (|A| + |B|) / (1 + J) with J = c / F, over d; both products are below 2^57.  share = 0xFFFFFFFF if Nn >= Dd, else
+ * floor(Nn 2^32 / Dd).  NIQKI_CONTAIN_ONE = 0xFFFFFFFF stands for a share of 1.  Integers only, checked bit for bit:
+ * 32 rounds of "double Nn; if Nn >= Dd, subtract and set the bit" in 64-bit arithmetic (nq_contain_share.h).  A hit is
+ * UNSIZED when q == 0 or g == 0.
+ * Result.  H(Q) is the list niqki_query returns for Q at the handle's min_score with top_k = 0: count descending, then
+ * gid descending.  The contained list C(Q): drop the unsized entries of H(Q); keep those with share >= min_share;
+ * order by share descending, ties in the order they have in H(Q) (a stable sort: with equal sizes C(Q) is a sub-list of
+ * H(Q) in H's order).  The handle's top_k (0 = all) keeps the first top_k entries of C(Q).  n_unsized[Q] (may be NULL) is
+ * the number of unsized entries of H(Q).  The result depends only on the index, the sizes, qsizes, mode, min_share,
+ * min_score and top_k: batch sizes, splits, tile count, paging, a delta segment, hit lists against counter rows and the
+ * order in which the device works do not change it.
+ * min_score IS THE FLOOR: a genome whose count is below it is never seen, whatever its share.  Lower min_score to what
+ * the smallest share of interest needs (a part of a tenth of a genome has J near 0.1 with it).
+ * Outputs as niqki_query_collapsed's: hit_off holds nq + 1 offsets; hit_shares, hit_counts and hit_gids hold the entries
+ * in C's order.  qsizes has nq entries (the staged form: one per staged entry) and lives in the same memory space as
+ * the outputs.  In both spaces a total above `capacity` returns NIQKI_E_CAPACITY with the true total in hit_off[nq] and
+ * nothing promised of the other arrays; capacity = nq x top_k never fails.  NIQKI_MEM_HOST works in batches of option
+ * "query_batch"; NIQKI_MEM_DEVICE takes the nq sketches in one batch and writes in stream order (a device qsizes entry
+ * of 2^40 or more ends the call with NIQKI_E_INVALID when the kernel meets it).  The staged form leaves the staged batch
+ * usable.  The handle's min_score and top_k are its own again on every exit.
+ * Handles as niqki_query_collapsed: whole-range single-GPU handles, resident or paged, any tile count, lists or rows,
+ * with or without a delta segment, S <= 16; a slot-range shard gets NIQKI_E_STATE.  A mode above 2: NIQKI_E_INVALID.
+ * Without sizes on a non-empty index: NIQKI_E_STATE, and niqki_last_error says to call niqki_set_sizes (again).  No
+ * genomes or nq = 0: NIQKI_OK with zero offsets.  Groups, the _shared calls and the _ahead calls have no such form.
+ * How: per batch the query path runs at top_k = 0 into the handle's hit buffers (option "cluster_ws_mib", halved like
+ * niqki_cluster's batches; stat "contain_splits").  contain_share_kernel, a workgroup of 256 per query, gathers
+ * size[gid], computes the shares and compacts the survivors in list order; contain_order_kernel orders up to 2048
+ * survivors as keys share << 32 | (0xFFFFFFFF - position) under the bitonic network of the hit kernels, and more by four
+ * stable 8-bit radix passes of one wave (stat "contain_long_lists": the queries of the last call on that route); a scan
+ * of the kept counts and an emit that fetches count and gid by position finish the batch.  8 more bytes a hit than the
+ * hit buffers.  While profiling is on: "contain_us_hits", "contain_us_share", "contain_us_order" (microseconds, the last
+ * call).  DESIGN.md 4.5h. */
+#define NIQKI_CONTAIN_QUERY 0u
+#define NIQKI_CONTAIN_GENOME 1u
+#define NIQKI_CONTAIN_MAX 2u
+#define NIQKI_CONTAIN_ONE 0xFFFFFFFFu
+int niqki_set_sizes(niqki_index *ix, const uint64_t *sizes, uint32_t n, int mem);
+int niqki_query_contained(niqki_index *ix, const int32_t *sketches, const uint64_t *qsizes, uint32_t nq, uint32_t mode,
+                          uint32_t min_share, uint64_t *hit_off, uint32_t *hit_shares, uint32_t *hit_counts,
+                          uint32_t *hit_gids, uint32_t *n_unsized, uint64_t capacity, int mem);
+int niqki_staged_query_contained(niqki_index *ix, const uint64_t *qsizes, uint32_t mode, uint32_t min_share,
+                                 uint64_t *hit_off, uint32_t *hit_shares, uint32_t *hit_counts, uint32_t *hit_gids,
+                                 uint32_t *n_unsized, uint64_t capacity, int mem);
+
 /* Taxon of a query: the lowest common ancestor (LCA) of its near-best hits, the rule of Kraken and MEGAN.  Labels are
  * flat; a collection also says that species X lies in genus Y and Y in family Z, and what a read classifier asks of
  * the index is ONE taxon per query: the species when the best hits all lie in it, the genus when several of its

@@ -20,6 +20,9 @@ FILE_GZIP = 0x80
 GROUP_ID_BYTES = 128
 E_CAPACITY = 4
 TAXON_NONE = 0xFFFFFFFF
+# NIQKI_CONTAIN_*: what the share of niqki_query_contained is a share of, and the share of 1
+CONTAIN_QUERY, CONTAIN_GENOME, CONTAIN_MAX = 0, 1, 2
+CONTAIN_ONE = 0xFFFFFFFF
 # NIQKI_AUDIT_*: the verdicts of niqki_audit, named in the order of their values (the rule is the kernel's alone)
 AUDIT_ALONE, AUDIT_AGREES, AUDIT_TIED, AUDIT_MISPLACED, AUDIT_STRAY = 0, 1, 2, 3, 4
 AUDIT_VERDICTS = ("alone", "agrees", "tied", "misplaced", "stray")
@@ -137,6 +140,9 @@ ABI = [
     ("niqki_set_labels", _int, [_vp, _vp, _u32, _int]),
     ("niqki_query_collapsed", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_staged_query_collapsed", _int, [_vp, _vp, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_set_sizes", _int, [_vp, _vp, _u32, _int]),
+    ("niqki_query_contained", _int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _int]),
+    ("niqki_staged_query_contained", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _int]),
     ("niqki_set_taxonomy", _int, [_vp, _vp, _u32, _vp, _u32, _int]),
     ("niqki_query_lca", _int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _int]),
     ("niqki_staged_query_lca", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _int]),
@@ -702,6 +708,58 @@ class Engine:
         return self._cover(lambda off, hc, hg, hm, c: self.L.niqki_staged_query_collapsed(
             self.h, _p(off), _p(hc), _p(hg), _p(hm), c, MEM_HOST), nq, cap, members)
 
+    def set_sizes(self, sizes):
+        """niqki_set_sizes: a uint64 size (distinct k-mers, below 2^40; 0 = none) per indexed genome (a numpy array, or
+        a device tensor of 64-bit elements), None to remove the sizes.  They last until genomes are added or dropped."""
+        if sizes is None:
+            self._ck(self.L.niqki_set_sizes(self.h, None, 0, MEM_HOST))
+        elif hasattr(sizes, "data_ptr"):
+            if sizes.element_size() != 8 or not sizes.is_contiguous():
+                raise ValueError("set_sizes: a device tensor must be contiguous and hold 64-bit sizes")
+            self._ck(self.L.niqki_set_sizes(self.h, _p(sizes), int(sizes.numel()), MEM_DEVICE))
+        else:
+            sz = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+            self._ck(self.L.niqki_set_sizes(self.h, _p(sz) if sz.size else None, sz.size, MEM_HOST))
+
+    def _contained(self, call, nq, capacity, unsized):
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        nu = np.zeros(nq, dtype=np.uint32)
+        while True:
+            hs, hc, hg = (np.empty(max(capacity, 1), dtype=np.uint32) for _ in range(3))
+            rc = call(off, hs, hc, hg, nu if unsized else None, capacity)
+            self._ck(rc, allow=(E_CAPACITY,))
+            if rc == 0:
+                tot = int(off[nq])
+                return (off, hs[:tot], hc[:tot], hg[:tot]) + ((nu,) if unsized else ())
+            capacity = int(off[nq])
+
+    def query_contained(self, sketches, qsizes, mode=0, min_share=0, unsized=False, capacity=None):
+        """niqki_query_contained: per query the hits with a size whose share (CONTAIN_QUERY / _GENOME / _MAX of the
+        sizes of set_sizes and qsizes, a uint64 per query) reaches min_share (CONTAIN_ONE = 1), ordered by share with
+        ties in the full list's order: (off, shares, counts, gids[, n_unsized]).  The handle's min_score is the floor,
+        its top_k the cut."""
+        sk = np.ascontiguousarray(sketches, dtype=np.int32).reshape(-1, self.F)
+        nq = sk.shape[0]
+        qs = np.ascontiguousarray(qsizes, dtype=np.uint64).reshape(-1)
+        if qs.size != nq:
+            raise ValueError("query_contained: %d sizes for %d queries" % (qs.size, nq))
+        cap = capacity if capacity is not None else max(1024, nq * 8)
+        return self._contained(lambda off, hs, hc, hg, nu, c: self.L.niqki_query_contained(
+            self.h, _p(sk), _p(qs), nq, int(mode), int(min_share), _p(off), _p(hs), _p(hc), _p(hg), _p(nu), c, MEM_HOST),
+            nq, cap, unsized)
+
+    def staged_query_contained(self, qsizes, mode=0, min_share=0, unsized=False, capacity=None):
+        """niqki_staged_query_contained: query_contained of the staged batch's sketches (qsizes: one per staged
+        entry); the staged batch stays usable."""
+        nq = self._staged.n_entry
+        qs = np.ascontiguousarray(qsizes, dtype=np.uint64).reshape(-1)
+        if qs.size != nq:
+            raise ValueError("staged_query_contained: %d sizes for %d staged entries" % (qs.size, nq))
+        cap = capacity if capacity is not None else max(1024, nq * 8)
+        return self._contained(lambda off, hs, hc, hg, nu, c: self.L.niqki_staged_query_contained(
+            self.h, _p(qs), int(mode), int(min_share), _p(off), _p(hs), _p(hc), _p(hg), _p(nu), c, MEM_HOST),
+            nq, cap, unsized)
+
     def set_taxonomy(self, genome_taxon, parent):
         """niqki_set_taxonomy: genome_taxon[g] = the taxon of indexed genome g, parent[t] = the parent of taxon t (a
         root is its own parent); numpy arrays, or two device tensors of 32-bit elements.  None for either removes the
@@ -992,6 +1050,12 @@ class Engine:
         total in hit_off[nq] and nothing else written."""
         return self._ck(self.L.niqki_query_collapsed(self.h, _p(sketches), nq, _p(hit_off), _p(hc), _p(hg), _p(hm),
                                                      capacity, MEM_DEVICE), allow=(E_CAPACITY,))
+
+    def query_contained_dev(self, sketches, qsizes, nq, mode, min_share, hit_off, hs, hc, hg, nu, capacity):
+        """niqki_query_contained on device arrays (qsizes: 64-bit elements; nu may be None); returns the status: 0, or
+        E_CAPACITY with the true total in hit_off[nq]."""
+        return self._ck(self.L.niqki_query_contained(self.h, _p(sketches), _p(qsizes), nq, int(mode), int(min_share), _p(hit_off),
+                                                     _p(hs), _p(hc), _p(hg), _p(nu), capacity, MEM_DEVICE), allow=(E_CAPACITY,))
 
     def query_lca_dev(self, sketches, nq, top_permille, taxon, best_count=None, best_gid=None, considered=None):
         """niqki_query_lca on device arrays (each of the last three may be None), written in stream order."""

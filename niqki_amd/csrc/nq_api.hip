@@ -383,7 +383,8 @@ void niqki_destroy(niqki_index *ix) {
                  &ix->ws_hdrpos, &ix->ws_ehdr, &ix->ws_stsk, &ix->ws_order, &ix->ws_pre, &ix->ws_hl, &ix->ws_parent, &ix->ws_useg, &ix->ws_ijob, &ix->ws_xtab,
                  &ix->ws_cv_sk[0], &ix->ws_cv_sk[1], &ix->ws_cv_idx, &ix->ws_cv_log, &ix->ws_cv_out,
                  &ix->tax_nodes, &ix->tax_genome, &ix->ws_lca_out, &ix->ws_lca_info, &ix->tally_acc, &ix->ws_tally_rows,
-                 &ix->ws_audit, &ix->ws_reg, &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage})
+                 &ix->ws_audit, &ix->ws_reg, &ix->lab_dense, &ix->ws_cl_keep, &ix->ws_cl_nk, &ix->ws_cl_off, &ix->ws_cl_tab, &ix->ws_cl_stage,
+                 &ix->sizes_dev, &ix->ws_ct_qs, &ix->ws_ct_tmp, &ix->ws_ct_n, &ix->ws_ct_off, &ix->ws_ct_stage})
     if (b->p) (void)hipFree(b->p);
   for (Buf *b : {&ix->pg_store, &ix->pg_stage})
     if (b->p) (void)hipFree(b->p);
@@ -611,6 +612,13 @@ const StatKey kCallStats[] = {
     NQ_STAT("collapse_us_hits", us(ix->collapse_stats.ms[0])),
     NQ_STAT("collapse_us_first", us(ix->collapse_stats.ms[1])),
     NQ_STAT("collapse_us_emit", us(ix->collapse_stats.ms[2])),
+    // niqki_set_sizes; niqki_query_contained / niqki_staged_query_contained
+    NQ_STAT("sizes", ix->sizes_set ? ix->n_genomes : 0),
+    NQ_STAT("contain_splits", ix->contain_stats.splits),
+    NQ_STAT("contain_long_lists", ix->contain_stats.long_lists),
+    NQ_STAT("contain_us_hits", us(ix->contain_stats.ms[0])),
+    NQ_STAT("contain_us_share", us(ix->contain_stats.ms[1])),
+    NQ_STAT("contain_us_order", us(ix->contain_stats.ms[2])),
     // niqki_set_taxonomy; niqki_query_lca / niqki_staged_query_lca
     NQ_STAT("taxa", ix->tax_set ? ix->n_taxa : 0),
     NQ_STAT("taxonomy_depth", ix->tax_set ? ix->tax_depth : 0),

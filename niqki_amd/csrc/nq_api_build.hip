@@ -206,6 +206,7 @@ int insert_dev(niqki_index *ix, const int32_t *sketches, uint32_t sk_stride, uin
   if (rc) return rc;
   drop_labels(ix);   // (niqki_set_labels: a labelling belongs to a genome set)
   drop_taxonomy(ix);   // (niqki_set_taxonomy: so does a taxonomy)
+  drop_sizes(ix);      // (niqki_set_sizes: and so do the sizes)
   if (ix->resident_bytes) {
     // paged: transpose into a device staging block of all the handle's slots, then rows to the host store
     const uint32_t f_all = ix->full_end - ix->full_begin;

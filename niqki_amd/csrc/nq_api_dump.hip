@@ -365,6 +365,7 @@ int niqki_append_slots(niqki_index *ix, uint32_t slot_begin, uint32_t slot_end, 
     ix->n_genomes += ix->append.n_new;
     drop_labels(ix);
     drop_taxonomy(ix);
+    drop_sizes(ix);
     ix->built = false;
     ix->pg_layout_n = 0xFFFFFFFFu;
     append_drop(ix);

@@ -1,7 +1,7 @@
 // nq_api_lists.hip -- what the calls that consume full hit lists on the device share (nq_handle.h, "full hit lists"):
 // the guard of a call's query parameters, the phase timer, the room of the fixed hit buffers, the halving leaf with its
 // batch loop, and the buffer growth that keeps what a batch has written.  The consumers are nq_api_selfjoin.hip,
-// nq_api_audit.hip, nq_api_cover.hip, nq_api_collapse.hip and nq_api_lca.hip.  DESIGN.md 4.5f.
+// nq_api_audit.hip, nq_api_cover.hip, nq_api_collapse.hip, nq_api_contain.hip and nq_api_lca.hip.  DESIGN.md 4.5f.
 #include "nq_handle.h"
 
 #include <algorithm>

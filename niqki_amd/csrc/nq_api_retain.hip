@@ -84,6 +84,7 @@ int retain_run(niqki_index *ix, const uint8_t *keep, uint32_t *new_ids, uint32_t
   if (n_kept) *n_kept = total;
   drop_labels(ix);   // (niqki_set_labels: also when all are kept, so that the call's effect does not depend on the flags)
   drop_taxonomy(ix);   // (niqki_set_taxonomy: the same)
+  drop_sizes(ix);      // (niqki_set_sizes: the same)
   if (total == N) return NIQKI_OK;   // all kept: the handle, a built index included, stays as it is
 
   release_segments(ix);

@@ -77,6 +77,7 @@ int unite_run(niqki_index *ix, const uint32_t *labels, uint32_t *new_ids, uint32
   if (n_labels) *n_labels = L;
   drop_labels(ix);     // (also when every label is distinct, so that the call's effect does not depend on the labels)
   drop_taxonomy(ix);
+  drop_sizes(ix);
   if (L == N) {        // all distinct: the handle, a built index included, stays as it is
     if (dev && new_ids) NQ_HIP(ix, hipStreamSynchronize(ix->stream));   // (g.ids leaves scope)
     if (ix->prof) ix->unite_ms[0] = ms_since(t0);

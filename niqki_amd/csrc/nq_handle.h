@@ -4,7 +4,8 @@
 //
 // Full hit lists: what the calls that consume a query's full hit lists on the device share -- niqki_cluster,
 // niqki_dereplicate and niqki_linkage (nq_api_selfjoin.hip), niqki_audit (nq_api_audit.hip), niqki_query_collapsed (nq_api_collapse.hip),
-// niqki_query_lca (nq_api_lca.hip) and, without the halving, niqki_cover (nq_api_cover.hip).  Bodies: nq_api_lists.hip.
+// niqki_query_lca (nq_api_lca.hip), niqki_query_contained (nq_api_contain.hip) and, without the halving, niqki_cover
+// (nq_api_cover.hip).  Bodies: nq_api_lists.hip.
 //   CallParams    the call's min_score / top_k on the handle, the handle's own back on every exit
 //   PhaseTimer    HIP events around the phases of a call while the handle is profiling
 //   hit_room      how many hits the fixed hit buffers take (option "cluster_ws_mib")
@@ -52,6 +53,13 @@ struct CollapseStats {
   uint64_t splits = 0;       // batches the call had to halve
   uint64_t long_lists = 0;   // queries whose list took the global-table route
   double ms[3] = {0, 0, 0};  // while profiling is on: hits, first, emit
+};
+
+// what niqki_get_stat reports of the last niqki_query_contained / niqki_staged_query_contained call (nq_api_contain.hip)
+struct ContainStats {
+  uint64_t splits = 0;       // batches the call had to halve
+  uint64_t long_lists = 0;   // queries whose survivors the radix passes ordered
+  double ms[3] = {0, 0, 0};  // while profiling is on: hits, share, order (with the scan and the emit)
 };
 
 // what niqki_get_stat reports of the last niqki_query_lca / niqki_staged_query_lca call (nq_api_lca.hip)
@@ -163,6 +171,14 @@ struct niqki_index {
   // tables, a batch's collapsed entries, its offsets on their way to the host
   nqi::Buf ws_cl_keep, ws_cl_nk, ws_cl_off, ws_cl_tab, ws_cl_stage;
   bool cl_tab_clean = false;   // every entry of ws_cl_tab is cleared (false after growth and while a call is under way)
+  // niqki_set_sizes: a size per genome (device, n_genomes 64-bit words, each below 2^40; 0 = none); every call that
+  // changes the genome set drops them (drop_sizes).  Independent of labels and taxonomy.
+  nqi::Buf sizes_dev;
+  bool sizes_set = false;
+  nqi::ContainStats contain_stats;
+  // niqki_query_contained: a host batch's query sizes; where the radix passes turn round (8 bytes a hit); per query of a
+  // batch the kept and unsized counts, then a leaf's survivors; a leaf's offsets and info words; a batch's entries
+  nqi::Buf ws_ct_qs, ws_ct_tmp, ws_ct_n, ws_ct_off, ws_ct_stage;
   // niqki_set_taxonomy: a node {parent, depth} per taxon and every genome's taxon (device), how many taxa there are and
   // the largest depth; every call that changes the genome set drops them (drop_taxonomy).  Independent of the labels.
   nqi::Buf tax_nodes, tax_genome;
@@ -363,6 +379,8 @@ struct HitLists {
 };
 // ---- nq_api_collapse.hip ----
 void drop_labels(niqki_index *ix);   // the genome set changes: the labelling of niqki_set_labels goes
+// ---- nq_api_contain.hip ----
+void drop_sizes(niqki_index *ix);    // the genome set changes: the sizes of niqki_set_sizes go
 // ---- nq_api_lca.hip ----
 void drop_taxonomy(niqki_index *ix);   // the genome set changes: the taxonomy of niqki_set_taxonomy goes
 // ---- nq_api_tally.hip ----

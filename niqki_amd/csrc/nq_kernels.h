@@ -382,6 +382,38 @@ hipError_t launch_collapse_emit(const unsigned long long *hit_off, const uint32_
 hipError_t launch_collapse_unpack(const CollapsedHit *in, uint64_t n, uint32_t *hit_counts, uint32_t *hit_gids, uint32_t *hit_members,
                                   hipStream_t stream);   // (hit_members may be null)
 
+// ---- hits chosen by share (nq_contain.hip; the batches: nq_api_contain.hip; the share: nq_contain_share.h) ----------
+// One entry of a contained list on its way out.
+struct ContainedHit {
+  uint32_t share, count, gid;
+};
+// info words of a batch: lists ordered by radix passes (more than kContainNetworkMax survivors); gids or lists out of
+// range (a bug: the host ends the call); query sizes of 2^40 or more (the host refuses the call)
+enum : uint32_t { kContainInfoLong = 0, kContainInfoBad = 1, kContainInfoBadSize = 2, kContainInfoWords = 3 };
+constexpr uint32_t kContainNetworkMax = 2048;   // survivors the bitonic network of contain_order_kernel takes
+struct ContainArgs {
+  const unsigned long long *hit_off;   // nq + 1: the full ordered lists (top_k = 0) of the batch
+  const uint32_t *hit_counts, *hit_gids;
+  const unsigned long long *sizes;     // per genome (0: none)
+  const unsigned long long *qsizes;    // per query of the batch (0: none)
+  uint32_t n_genomes, nq, F, mode, min_share, top_k;
+  // per hit place, a query's at [hit_off[q], ...): its survivors' shares and 0xFFFFFFFF - position, in list order after
+  // contain_share, in the contained list's order after contain_order; b_*: where the radix passes turn round
+  uint32_t *a_share, *a_npos, *b_share, *b_npos;
+  uint32_t *n_surv;                    // per query: its sized hits with share >= min_share
+  uint32_t *n_kept;                    // per query: min(n_surv, top_k)
+  uint32_t *n_unsized;                 // per query: its hits without a size
+  uint32_t *info;                      // kContainInfoWords, zeroed by the caller
+};
+// a workgroup per query: the shares, the survivors compacted in list order, n_surv, n_unsized
+hipError_t launch_contain_share(const ContainArgs &a, hipStream_t stream);
+// a workgroup per query: its survivors into the contained list's order (in a_*), n_kept
+hipError_t launch_contain_order(const ContainArgs &a, hipStream_t stream);
+// query q's first n_kept[q] entries to out[off[q] ...), count and gid fetched by position
+hipError_t launch_contain_emit(const ContainArgs &a, const unsigned long long *off, ContainedHit *out, hipStream_t stream);
+hipError_t launch_contain_unpack(const ContainedHit *in, uint64_t n, uint32_t *hit_shares, uint32_t *hit_counts, uint32_t *hit_gids,
+                                 hipStream_t stream);
+
 // ---- taxon of a query: the LCA of its near-best hits (nq_lca.hip; the batches: nq_api_lca.hip) ------------
 // One taxon of the device taxonomy: a step up the tree is one 8-byte load.  A root is its own parent at depth 0.
 struct TaxNode {

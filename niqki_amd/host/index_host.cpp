@@ -97,6 +97,7 @@ const struct {
     {{"niqki_set_taxonomy", "niqki_staged_query_lca"}, "this engine has no LCA query"},
     {{"niqki_staged_cover"}, "this engine has no cover"},
     {{"niqki_registers", "niqki_staged_registers"}, "this engine cannot read sketch registers"},
+    {{"niqki_set_sizes", "niqki_staged_query_contained"}, "this engine cannot select hits by containment"},
     {{"niqki_set_labels", "niqki_staged_query_collapsed"}, "this engine has no collapsed query"},
     {{"niqki_tally_begin", "niqki_tally_read"}, "this engine has no taxon tally"},
 };
@@ -548,23 +549,47 @@ void Index::query_staged(size_t n, Hits &h) {
     check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 16, 8), n * N,
                      [&](uint64_t cap) { return call(h_, top_k, h.off.data(), h.hc.data(), h.hg.data(), nullptr, cap, NIQKI_MEM_HOST); }),
           "niqki_staged_cover");
+  } else if (min_share) {   // --min-containment: the entries chosen, ordered and cut by their share on the device
+    const auto call = NEED(CONTAINED, niqki_staged_query_contained);
+    staged_sizes(n, (uint32_t)N, h);
+    // (an estimate of 2^40 or more is no size the engine takes: such a hit counts as unsized)
+    const auto kmers = [](const nqsize::Estimate &e) { return e.status == nqsize::OK && e.kmers + 0.5 < 1099511627776.0 ? (uint64_t)std::floor(e.kmers + 0.5) : uint64_t(0); };
+    if (!sizes_set_) {   // once, at the first query batch: the index is final by then
+      std::vector<uint64_t> sizes(N);
+      for (uint64_t g = 0; g < N; ++g) sizes[g] = kmers(genome_size_[g]);
+      check(NEED(CONTAINED, niqki_set_sizes)(h_, sizes.empty() ? nullptr : sizes.data(), (uint32_t)N, NIQKI_MEM_HOST), "niqki_set_sizes");
+      sizes_set_ = true;
+    }
+    std::vector<uint64_t> qs(std::max<size_t>(n, 1));
+    for (size_t i = 0; i < n; ++i) qs[i] = kmers(h.qsize[i]);
+    std::vector<uint32_t> shares, unsized(std::max<size_t>(n, 1), 0);
+    check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 16, 8), n * N,
+                     [&](uint64_t cap) {
+                       shares.resize(cap);
+                       return call(h_, qs.data(), contain_mode, min_share, h.off.data(), shares.data(), h.hc.data(), h.hg.data(), unsized.data(), cap,
+                                   NIQKI_MEM_HOST);
+                     }),
+          "niqki_staged_query_contained");
+    for (size_t i = 0; i < n; ++i) unsized_hits += unsized[i];
   } else {
     check(fill_lists(&h, 1, n, first_capacity(n, top_k, N, uint64_t(1) << 20, 64), n * N,
                      [&](uint64_t cap) { return niqki_staged_query(h_, h.off.data(), h.hc.data(), h.hg.data(), cap, NIQKI_MEM_HOST); }),
           "niqki_staged_query");
-    if (containment) {   // --containment: the plain list with each entry's two shares; the batch's sizes from its staged sketches
-      const auto call = NEED(SIZES, niqki_staged_registers);
-      if (!genome_size_ok_) {
-        genome_size_ = genome_sizes((uint32_t)N);
-        genome_size_ok_ = true;
-      }
-      const uint32_t B = NIQKI_REGISTER_BINS(H);
-      std::vector<uint32_t> hist(std::max<size_t>(n, 1) * B);
-      check(call(h_, hist.data(), NIQKI_MEM_HOST), "niqki_staged_registers");
-      h.qsize.resize(n);
-      for (size_t i = 0; i < n; ++i) h.qsize[i] = nqsize::estimate(hist.data() + i * B, lF, H);
-    }
+    if (containment) staged_sizes(n, (uint32_t)N, h);   // --containment: the plain list with each entry's two shares
   }
+}
+
+void Index::staged_sizes(size_t n, uint32_t N, Hits &h) {
+  const auto call = NEED(SIZES, niqki_staged_registers);
+  if (!genome_size_ok_) {
+    genome_size_ = genome_sizes(N);
+    genome_size_ok_ = true;
+  }
+  const uint32_t B = NIQKI_REGISTER_BINS(H);
+  std::vector<uint32_t> hist(std::max<size_t>(n, 1) * B);
+  check(call(h_, hist.data(), NIQKI_MEM_HOST), "niqki_staged_registers");
+  h.qsize.resize(n);
+  for (size_t i = 0; i < n; ++i) h.qsize[i] = nqsize::estimate(hist.data() + i * B, lF, H);
 }
 
 std::vector<nqsize::Estimate> Index::genome_sizes(uint32_t n) const {

@@ -62,7 +62,7 @@ class Index {
   // the long options below are looked up at run time, so the program links against any engine, and a run that needs one
   // the engine lacks is refused with the feature's text.  One table in index_host.cpp holds, per feature, the symbols it
   // needs and that text.  All of these work on a single-GPU index only.
-  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, AUDIT, LCA, COVER, SIZES, COLLAPSE, TALLY };
+  enum class Feature { APPEND, DEREPLICATION_FROM, RETAIN, UNITE, SELF_JOIN, DEREPLICATION, LINKAGE, AUDIT, LCA, COVER, SIZES, CONTAINED, COLLAPSE, TALLY };
   // null where the engine has every call of the feature, else the text that says what is missing
   static const char *lacks(Feature f);
 
@@ -143,6 +143,13 @@ class Index {
   // plain -Q / -l list is name:jaccard:cq:cg -- the share of the query's k-mers found in the genome and of the genome's
   // found in the query, "-" each where either size is not ok.  Order, threshold and --top are those of the plain list.
   bool containment = false;
+  // --min-containment <x>, --containment-of query|genome|either (niqki_set_sizes once + niqki_staged_query_contained):
+  // with min_share > 0 the entries of a -Q / -l list are those whose containment reaches x, ordered by it and cut to
+  // top_k on the device, in --containment's format.  The integer sizes are floor(estimate + 0.5) where the status is ok,
+  // else 0 (such a hit is never listed); min_score stays the floor.  unsized_hits: the hits of all queries so far that
+  // had no size estimate.
+  uint32_t min_share = 0, contain_mode = 0;
+  uint64_t unsized_hits = 0;
 
   void output_query(const query_output &toprint, const std::string &queryname);   // :544-566
   void output_matrix_row(const uint16_t *counts, const std::string &queryname);   // :747-763
@@ -204,6 +211,9 @@ class Index {
   std::vector<nqsize::Estimate> genome_sizes(uint32_t n) const;
   std::vector<nqsize::Estimate> genome_size_;   // --containment: ... taken once, at the first query batch
   bool genome_size_ok_ = false;
+  // ... and the sizes of the n staged entries into h.qsize, from their staged sketches (niqki_staged_registers)
+  void staged_sizes(size_t n, uint32_t N, Hits &h);
+  bool sizes_set_ = false;              // --min-containment: niqki_set_sizes has run
   std::string out_text_;                // write_hits' lines before they go to the writer
   std::string out_path_;                // the -O file (refuse takes it away again)
   // Lines mode.  stage_lines: one niqki_stage_raw of the whole records at raw[0, size) on h -- at most hdr.size()

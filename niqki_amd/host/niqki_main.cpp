@@ -41,6 +41,12 @@
 //   --containment  every entry of a plain -Q / -l list is name:jaccard:cq:cg, the share of the query's k-mers found in the
 //                  genome and of the genome's found in the query, from the count and the two estimated sizes
 //                  (niqki_staged_registers per batch); -:- where either size is out of range
+//   --min-containment <x>  0 < x <= 1: the entries of a -Q / -l list are the hits whose containment reaches x, ordered by it
+//                  and cut by --top on the device (niqki_set_sizes + niqki_staged_query_contained), in --containment's
+//                  format; -J stays the floor -- a genome below it is never seen, so lower -J to what the smallest share of
+//                  interest needs; hits without a size estimate are never listed and are counted on a line of their own
+//   --containment-of query|genome|either  with --min-containment: the share is that of the query's k-mers found in the
+//                  genome (the default), of the genome's found in the query, or the larger of the two
 //   --merge <f>    append the genomes of the dump f to the index (niqki_append_*); may be repeated, ALL occurrences are
 //                  taken, in command-line order, after -L / -I / -i and before --remove and -D
 //   --novel <f>    after every index input and merge: dereplicate at the -J threshold with the genomes of -L given
@@ -53,6 +59,7 @@
 
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -72,7 +79,7 @@ using namespace std::chrono;
 namespace {
 
 enum Opt { LIST, QUERY, LISTLINES, QUERYLINES, KMER, FETCH, OUTPUT, MIN, PRETTY, MATRIX, WORD, GENOME_SIZE, HHL,
-           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, AUDIT, AUDIT_K, SIZES, CONTAINMENT, N_OPT };
+           DUMP, LOAD, DOWNLAD, LOGO, HELP, DEVICE, GPUS, RESIDENT, TOP, NEIGHBORS, CLUSTER, DEREP, REMOVE, PAN, DEREP_DUMP, MERGE, NOVEL, MST, LINKAGE, TREE, COVER, COLLAPSE, LCA, LCA_TOP, REPORT, AUDIT, AUDIT_K, SIZES, CONTAINMENT, MIN_CONTAINMENT, CONTAINMENT_OF, N_OPT };
 enum ArgKind { NONE, NONEMPTY, NUMERIC };
 
 // Same order as the reference's descriptor table: a short option character
@@ -122,6 +129,8 @@ const Desc kDesc[] = {
     {AUDIT_K, "", "audit-k", NONEMPTY, "  --audit-k <n>                 With --audit: the nearest genomes that vote, 1..63 (1)."},
     {SIZES, "", "sizes", NONEMPTY, "  --sizes <filename>            Estimated number of distinct k-mers of every indexed genome, after everything that changes the index and before the queries: lines name<TAB>kmers<TAB>status; status is ok, below or above (outside the estimator's range: do not use the number)."},
     {CONTAINMENT, "", "containment", NONE, "  --containment                 Report each -Q / -q hit as name:jaccard:cq:cg, the share of the query's k-mers found in the genome and of the genome's found in the query (-:- where a size cannot be estimated)."},
+    {MIN_CONTAINMENT, "", "min-containment", NONEMPTY, "  --min-containment <x>         Report the -Q / -q hits whose containment reaches x (0 < x <= 1), ordered by it, as name:jaccard:cq:cg (--top cuts that list); -J stays the floor: a genome below it is never seen, so lower -J to what the smallest share of interest needs."},
+    {CONTAINMENT_OF, "", "containment-of", NONEMPTY, "  --containment-of <which>      With --min-containment: query (the share of the query's k-mers found in the genome; the default), genome (of the genome's found in the query) or either (the larger of the two)."},
 };
 
 struct Parsed {
@@ -307,6 +316,7 @@ const struct { Opt asked_by[3]; Feature feature; } kNeeds[] = {
     {{LCA, LCA, LCA}, Feature::LCA},
     {{COVER, COVER, COVER}, Feature::COVER},
     {{SIZES, CONTAINMENT, CONTAINMENT}, Feature::SIZES},
+    {{MIN_CONTAINMENT, MIN_CONTAINMENT, MIN_CONTAINMENT}, Feature::CONTAINED},
     {{COLLAPSE, COLLAPSE, COLLAPSE}, Feature::COLLAPSE},
     {{REPORT, REPORT, REPORT}, Feature::TALLY},
 };
@@ -375,6 +385,41 @@ int main(int argc, char *argv[]) {
   }
   if (n_gpus > 1 && o.has(SIZES)) return refused("--sizes needs a single-GPU index (--gpus 1)");
   if (const char *text = engine_lacks(o, Feature::SIZES, Feature::SIZES)) return refused(text);
+  // --min-containment: 0 < x <= 1 as a share of 2^32, rounded up (1 is NIQKI_CONTAIN_ONE); --containment-of: whose share
+  uint32_t min_share = 0, contain_mode = NIQKI_CONTAIN_QUERY;
+  if (o.has(MIN_CONTAINMENT)) {
+    const string &a = o.last(MIN_CONTAINMENT);
+    char *end = nullptr;
+    errno = 0;
+    const double x = strtod(a.c_str(), &end);
+    if (a.empty() || a[0] == ' ' || end == a.c_str() || *end != 0 || errno || !(x > 0.0) || !(x <= 1.0)) {
+      fprintf(stderr, "Option 'min-containment' requires a number x with 0 < x <= 1\n");
+      cout << "Bad usage!!!" << endl;
+      return EXIT_FAILURE;
+    }
+    const double scaled = std::ceil(x * 4294967296.0);   // (exact: a power of two times a double)
+    min_share = scaled >= 4294967295.0 ? NIQKI_CONTAIN_ONE : (uint32_t)scaled;
+  }
+  if (o.has(CONTAINMENT_OF)) {
+    if (!o.has(MIN_CONTAINMENT)) return refused("--containment-of needs --min-containment");
+    const string &a = o.last(CONTAINMENT_OF);
+    if (a == "query") contain_mode = NIQKI_CONTAIN_QUERY;
+    else if (a == "genome") contain_mode = NIQKI_CONTAIN_GENOME;
+    else if (a == "either") contain_mode = NIQKI_CONTAIN_MAX;
+    else {
+      fprintf(stderr, "Option 'containment-of' requires query, genome or either\n");
+      cout << "Bad usage!!!" << endl;
+      return EXIT_FAILURE;
+    }
+  }
+  // the shares select from the plain list, on one device from whole counts and the registers of whole sketches
+  if (o.has(MIN_CONTAINMENT)) {
+    if (o.has(COVER) || o.has(COLLAPSE) || o.has(LCA))
+      return refused("--min-containment selects from the plain hit list: --cover, --collapse and --lca replace it, choose one");
+    if (n_gpus > 1) return refused("--min-containment needs a single-GPU index (--gpus 1)");
+    if (const char *text = engine_lacks(o, Feature::CONTAINED, Feature::CONTAINED)) return refused(text);
+    if (const char *text = nqhost::Index::lacks(Feature::SIZES)) return refused(text);   // (the sizes come from the registers)
+  }
 
   // --audit-k: how many of a genome's nearest neighbours vote, a plain integer
   uint32_t audit_k = 1;
@@ -442,6 +487,8 @@ int main(int argc, char *argv[]) {
     else ix.reset(new nqhost::Index(S, K, W, H, out_file, min_jaccard, device, n_gpus, resident_mib, top_k));
     ix->cover = o.has(COVER);
     ix->containment = o.has(CONTAINMENT);
+    ix->min_share = min_share;
+    ix->contain_mode = contain_mode;
     if (o.has(REPORT)) ix->report = o.last(REPORT);
     if (const unsigned expect = (unsigned)int_opt(o, GENOME_SIZE, 0)) ix->select_best_H(expect);   // src/niqki.cpp:303-305
 
@@ -528,6 +575,7 @@ int main(int argc, char *argv[]) {
     if (o.has(NEIGHBORS)) ix->query_neighbors();
     for (const Phase &ph : kQueryPhases) run_phase(*ix, o, ph);
     if (o.has(REPORT)) ix->write_report();
+    if (o.has(MIN_CONTAINMENT)) cout << "Hits without a size estimate: " << ix->unsized_hits << endl;
     ix->outfile->close();
     const RunClock::tp done = system_clock::now();
     RunClock::row("| Query lasted (s)                  |", clk.index_end, done);
